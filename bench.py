@@ -7,13 +7,18 @@
 One step = zero_grad -> forward under bf16 autocast (spectral path fp32, as the reference) ->
 area-weighted MSE loss -> backward -> shared-gradient reduction -> Adam step, on synthetic
 N(0,1) fields of the configuration ``sfno_linear_73chq_sc3_layers8_edim384``
-(/root/reference/config/sfnonet.yaml:162-187: embed_dim 384, 8 layers, scale_factor 3,
+(the reference's config/sfnonet.yaml:162-187: embed_dim 384, 8 layers, scale_factor 3,
 dhconv, instance norm, MLP ratio 2, big skip).  N > 1: latitude sharded over ``h`` =
 N ranks (spatial model parallelism with RCCL all-to-all), global batch N (weak scaling).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-``roofline`` for the dominant hand-written kernel (timed live with HIP events on the launch
-stream inside the timed region) and ``cpu_baseline`` (the oracle on the host cores, N = 1 only).
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up and times K steps.  ``--full`` adds
+the first-step loss check against tests/golden/bench_first_loss.json, the per-kernel table, ``roofline``
+for the dominant hand-written kernel (timed live with HIP events on the launch stream inside the timed
+region), ``step_roofline`` and ``cpu_baseline`` (the oracle on the host cores, N = 1 only).
+``--dump-outputs DIR`` writes what the last timed step returns, its loss, as DIR/loss.npy (float32; with N > 1,
+rank 0's share of the loss, from its latitude shard).  The updated weights, their gradients and the prediction are
+not written: the 1x1-convolution weight gradients are summed with fp32 atomics in no fixed order, and Adam carries
+those last-bit differences into the weights, so after a few dozen steps two runs differ there far beyond rounding.
 """
 import argparse
 import json
@@ -349,21 +354,92 @@ def _golden_first_loss():
         return None
 
 
+def dump_outputs(out_dir, loss):
+    """What the last timed step hands its caller: the loss (float32, as the step returns it)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss.item()], dtype=np.float32))
+
+
+def full_report(args, timer, pre_kernels, n_probe, net, lat_loc, B, elapsed, world, first_loss):
+    """The `--full` fields of the result line: kernel table, rooflines, CPU baseline and the first-step loss check."""
+    kernels = timer.summary(args.steps) if not args.no_kernel_timing else {}
+    timed = dict(kernels)                       # what was recorded inside the timed region
+    if pre_kernels is not None:
+        kernels = dict(pre_kernels)
+        kernels.update(timed)                   # the dominant kernel: timed-region figures
+    roof = None
+    if kernels:
+        dom = max(kernels, key=lambda n: kernels[n]["ms_per_step"])
+        k = kernels[dom]
+        roof = {"kernel": dom, "bound": k["bound"], "achieved": k["achieved"], "peak": k["peak"], "unit": k["unit"],
+                "frac": k["frac"], "traffic": _measured_traffic(dom), "traffic_unit": "HBM bytes per launch (PMC)",
+                "avg_launch_ms": k["avg_launch_ms"]}
+    step_roof = None
+    if kernels:
+        # step-level roofline: sum over the step's op census of (algorithmic work / the peak that binds it), over the
+        # measured step time.  Timed launches bring their own work (KernelTimer); the streaming passes without a
+        # wrapper are counted from the configuration: instance norms (block: norm0 + GELU forward = 3 row passes of the
+        # bf16 field, norm1's forward rides in GEMM epilogues, each backward = 5), Adam (28 bytes per real parameter:
+        # p, g, m, v read, p, m, v written), the loss (pred bf16 + target fp32 read, gradient written: 14 bytes/px)
+        E, nblk = CONFIG["embed_dim"], CONFIG["num_layers"]
+        px_full = lat_loc * 1440
+        px_low = net.h_loc * net.w_loc
+        nreal = sum(p.numel() * (2 if p.is_complex() else 1) for p in net.parameters())
+        census = {n: k["roofline_ms_per_step"] for n, k in kernels.items() if "roofline_ms_per_step" in k}
+        census["instance_norm"] = 13 * E * 2 * B * (px_full + (nblk - 1) * px_low) / (PEAK_HBM_GBS * 1e9) * 1e3
+        census["adam"] = 28.0 * nreal / (PEAK_HBM_GBS * 1e9) * 1e3
+        census["loss"] = 14.0 * 73 * B * px_full / (PEAK_HBM_GBS * 1e9) * 1e3
+        total = sum(census.values())
+        step_roof = {"sum_work_over_peak_ms": round(total, 3), "frac": round(total / (1e3 * elapsed / args.steps), 4),
+                     "census_ms": {n: round(v, 3) for n, v in census.items()}}
+    cpu = None
+    if world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline()
+        if args.full_cpu_baseline:
+            cpu["full_step_s"] = cpu_full_step()
+            cpu["extrapolation_over_full"] = round((1.0 / cpu["value"]) / cpu["full_step_s"], 3)
+    out = {
+        "roofline": roof, "step_roofline": step_roof, "cpu_baseline": cpu, "kernels": kernels,
+        "kernel_timing": ("HIP events: all kernels over the last %d warm-up step(s), the roofline kernel over the timed region"
+                          % n_probe) if n_probe else ("HIP events over an eager pre-pass" if args.graph else
+                                                      "HIP events over the timed region"),
+    }
+    golden = _golden_first_loss()
+    if first_loss is not None:
+        chk = {"first_step_loss": round(first_loss, 6)}
+        if golden is not None:
+            g = golden["bf16_engine_loss"]
+            chk.update(golden=g, oracle_fp32=golden.get("oracle_fp32_loss"), rel_diff=round(abs(first_loss - g) / g, 6),
+                       ok=bool(abs(first_loss - g) <= 2e-3 * g))
+        out["loss_check"] = chk
+    return out
+
+
 # ----------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the first-step loss against the golden value, time every hand-written kernel "
+                         "(kernels, roofline, step_roofline) and run the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returns, its loss, to DIR/loss.npy (float32; "
+                         "with N > 1 rank 0's share of it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timing")
     ap.add_argument("--full-cpu-baseline", action="store_true",
-                    help="also run ONE complete oracle forward+backward of the full configuration on the host cores "
-                         "(minutes, tens of GB of RAM) and report it next to the slice extrapolation")
+                    help="with --full: also run ONE complete oracle forward+backward of the full configuration on the "
+                         "host cores (minutes, tens of GB of RAM) and report it next to the slice extrapolation")
     ap.add_argument("--graph", action="store_true",
                     help="capture forward+loss+backward in a HIP graph and replay it (reference: trainer.py:84-152, "
                          "optimizer step outside the graph); kernel timing then comes from an eager pre-pass")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    kernel_timing = args.full and not args.no_kernel_timing
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks as a torch.distributed.run child BEFORE anything here touches
@@ -414,7 +490,7 @@ def main():
                                                                                # quadrature weight per local latitude row
 
     timer = KernelTimer()
-    if not args.no_kernel_timing:
+    if kernel_timing:
         timer.install()
 
     # MK_BENCH_MICROBATCH=2: two micro-batches on two HIP streams / RCCL communicators, so the distributed-SHT all-to-alls of
@@ -470,7 +546,7 @@ def main():
     # value check of the timed configuration: the loss of the very first step (initial weights) against the value recorded in
     # tests/golden/bench_first_loss.json, which tests/test_parity_gpu.py::test_bench_first_step_loss pins to the fp32 CPU oracle
     first_loss = None
-    if world == 1 and runner is None and args.warmup > 0:
+    if args.full and world == 1 and runner is None and args.warmup > 0:
         first_loss = float(step().item())
         args_warm_left = args.warmup - 1
     else:
@@ -478,7 +554,7 @@ def main():
 
     timed_step = step
     pre_kernels = None
-    n_probe = 0 if (args.no_kernel_timing or args.graph) else min(args_warm_left, 2)
+    n_probe = 0 if (not kernel_timing or args.graph) else min(args_warm_left, 2)
     for i in range(args_warm_left):
         timer.enabled = i >= args_warm_left - n_probe
         step()
@@ -490,7 +566,7 @@ def main():
         timer.only = {max(pre_kernels, key=lambda n: pre_kernels[n]["ms_per_step"])}
 
     if args.graph:
-        if not args.no_kernel_timing:       # events cannot be recorded inside a captured graph
+        if kernel_timing:                   # events cannot be recorded inside a captured graph
             timer.enabled = True
             for _ in range(2):
                 step()
@@ -518,7 +594,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    timer.enabled = not args.no_kernel_timing and not args.graph
+    timer.enabled = kernel_timing and not args.graph
     # Python's cyclic garbage collector is kept out of the timed region (a generation-2 pass over the process's objects
     # stalls one step by 70-90 ms around step 10 of a fresh process: tools/step_times.py); collected before and after.
     import gc
@@ -540,43 +616,10 @@ def main():
         elapsed = t.item()
     assert math.isfinite(loss.item()), "loss is not finite"
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss)
+
     if rank == 0:
-        kernels = timer.summary(args.steps) if not args.no_kernel_timing else {}
-        timed = dict(kernels)                       # what was recorded inside the timed region
-        if pre_kernels is not None:
-            kernels = dict(pre_kernels)
-            kernels.update(timed)                   # the dominant kernel: timed-region figures
-        roof = None
-        if kernels:
-            dom = max(kernels, key=lambda n: kernels[n]["ms_per_step"])
-            k = kernels[dom]
-            roof = {"kernel": dom, "bound": k["bound"], "achieved": k["achieved"], "peak": k["peak"], "unit": k["unit"],
-                    "frac": k["frac"], "traffic": _measured_traffic(dom), "traffic_unit": "HBM bytes per launch (PMC)",
-                    "avg_launch_ms": k["avg_launch_ms"]}
-        step_roof = None
-        if kernels:
-            # step-level roofline: sum over the step's op census of (algorithmic work / the peak that binds it), over the
-            # measured step time.  Timed launches bring their own work (KernelTimer); the streaming passes without a
-            # wrapper are counted from the configuration: instance norms (block: norm0 + GELU forward = 3 row passes of the
-            # bf16 field, norm1's forward rides in GEMM epilogues, each backward = 5), Adam (28 bytes per real parameter:
-            # p, g, m, v read, p, m, v written), the loss (pred bf16 + target fp32 read, gradient written: 14 bytes/px)
-            E, nblk = CONFIG["embed_dim"], CONFIG["num_layers"]
-            px_full = lat_loc * 1440
-            px_low = net.h_loc * net.w_loc
-            nreal = sum(p.numel() * (2 if p.is_complex() else 1) for p in net.parameters())
-            census = {n: k["roofline_ms_per_step"] for n, k in kernels.items() if "roofline_ms_per_step" in k}
-            census["instance_norm"] = 13 * E * 2 * B * (px_full + (nblk - 1) * px_low) / (PEAK_HBM_GBS * 1e9) * 1e3
-            census["adam"] = 28.0 * nreal / (PEAK_HBM_GBS * 1e9) * 1e3
-            census["loss"] = 14.0 * 73 * B * px_full / (PEAK_HBM_GBS * 1e9) * 1e3
-            total = sum(census.values())
-            step_roof = {"sum_work_over_peak_ms": round(total, 3), "frac": round(total / (1e3 * elapsed / args.steps), 4),
-                         "census_ms": {n: round(v, 3) for n, v in census.items()}}
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline()
-            if args.full_cpu_baseline:
-                cpu["full_step_s"] = cpu_full_step()
-                cpu["extrapolation_over_full"] = round((1.0 / cpu["value"]) / cpu["full_step_s"], 3)
         line = {
             "metric": "SFNO fwd+bwd samples/sec, 73ch 721x1440",
             "value": round(B * args.steps / elapsed, 4), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -589,20 +632,10 @@ def main():
                        "micro_batches": nmb, "python_gc": "disabled in the timed region",
                        "adam": ("large tensors updated on a side stream as their gradients arrive, joined in opt.step()"
                                 if (adam_overlap and not args.graph) else "after backward")},
-            "roofline": roof, "step_roofline": step_roof, "cpu_baseline": cpu, "kernels": kernels,
-            "kernel_timing": ("HIP events: all kernels over the last %d warm-up step(s), the roofline kernel over the timed region"
-                              % n_probe) if n_probe else ("HIP events over an eager pre-pass" if args.graph else
-                                                          "HIP events over the timed region"),
             "loss": round(loss.item(), 6),
         }
-        golden = _golden_first_loss()
-        if first_loss is not None:
-            chk = {"first_step_loss": round(first_loss, 6)}
-            if golden is not None:
-                g = golden["bf16_engine_loss"]
-                chk.update(golden=g, oracle_fp32=golden.get("oracle_fp32_loss"), rel_diff=round(abs(first_loss - g) / g, 6),
-                           ok=bool(abs(first_loss - g) <= 2e-3 * g))
-            line["loss_check"] = chk
+        if args.full:
+            line.update(full_report(args, timer, pre_kernels, n_probe, net, lat_loc, B, elapsed, world, first_loss))
         print(json.dumps(line), flush=True)
     if world > 1:
         comm.cleanup()

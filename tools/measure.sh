@@ -5,7 +5,7 @@ set -o pipefail
 tag=${1:-rXX}
 export TMPDIR=/tmp
 out=gpurun_out
-timeout -k 10 500 python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+timeout -k 10 500 python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
 tail -1 $out/${tag}_bench.json | cut -c1-400
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof -o runc -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-timing > $out/${tag}_prof.log 2>&1 || exit 2
 echo "kernel trace done"
