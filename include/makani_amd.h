@@ -318,6 +318,44 @@ int mk_pce_debug_stamps(unsigned long long* out512);
 int mk_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
                  float weight_decay, int step, void* stream);
 
+/* ---- multi-tensor optimizer kernels (optim.hip) ------------------------
+ * The optimizers of the reference trainer's `optimizer_type` switch (makani/utils/trainer.py:448-478: torch AdamW /
+ * Adam, apex FusedLAMB) and the gradient clipping of its `max_grad_norm`.  A tensor list is `T` fp32 runs given as
+ * host arrays: device addresses (4-byte aligned; for the 4-stream calls p, g, m, v of tensor t at [4 t .. 4 t + 3])
+ * and lengths in reals.  The list is passed by value to the kernels (captured launches upload nothing); lists longer
+ * than one argument block take several launches.  Norm partials are fp64, one per chunk of a tensor: a workspace
+ * `partials` holds sum over t of mk_mt_chunks(n[t]) doubles, `tsum` T doubles.  Deterministic: no float atomics.
+ * Step counts: `steps` == NULL -> step_or_slot[t] is the (1-based) step of tensor t; else it is the slot of tensor t
+ * in the float32 device table `steps` (capturable mode), whose slots `inc_slots` are incremented by the norm's
+ * finalize (or by mk_mt_step_inc) before any update reads them.  `lr_dev` != NULL: the learning rate is read there. */
+/* Norm partials a tensor of n reals produces. */
+long long mk_mt_chunks(long long n);
+/* Per-tensor sums of squares tsum[t] (torch.nn.utils.clip_grad_norm_, trainer.py:757-760; apex FusedLAMB's global
+ * norm).  clip_mode 0: tsum only; 1: also the norm G and torch's coefficient min(1, max_norm / (G + 1e-6));
+ * 2: G and apex LAMB's divisor (G > max_norm ? G / max_norm : 1); 3: G alone.  norm_out / coef_out: device floats. */
+int mk_mt_sumsq(int T, const uint64_t* x, const long long* n, double* partials, double* tsum, int clip_mode, float max_norm,
+                float* norm_out, float* coef_out, float* steps, const int* inc_slots, int ninc, void* stream);
+/* The total and the coefficient from tsum (after tsum was summed over the model-parallel groups); same clip_mode. */
+int mk_mt_norm_finish(int T, const double* tsum, int clip_mode, float max_norm, float* norm_out, float* coef_out,
+                      float* steps, const int* inc_slots, int ninc, void* stream);
+/* steps[slots[i]] += 1 (capturable step counter when no norm pass runs before the update). */
+int mk_mt_step_inc(float* steps, const int* slots, int nslots, void* stream);
+/* x *= *coef over every tensor (clip_grad_norm_'s in-place rescale). */
+int mk_mt_scale(int T, const uint64_t* x, const long long* n, const float* coef, void* stream);
+/* torch.optim.AdamW (adamw = 1: p *= 1 - lr wd) or torch.optim.Adam (adamw = 0: g += wd p) in one pass; the gradient
+ * is multiplied by *coef as it is read (coef may be NULL) and is not written.  Bias corrections in double. */
+int mk_mt_adam(int T, const uint64_t* pgmv, const long long* n, const int* step_or_slot, const float* steps, float lr,
+               const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int adamw, const float* coef,
+               void* stream);
+/* apex FusedLAMB (apex/optimizers/fused_lamb.py, csrc/multi_tensor_lamb.cu), gradient divided by *coef (NULL: 1).
+ * Stage 1 updates m, v and leaves the per-tensor sums of squares of the old p (tsum_p) and of the update u (tsum_u);
+ * stage 2 recomputes u from the new moments and applies p -= r u, r = lr |p| / |u| when `trust` and both are non-zero,
+ * else lr.  The gradient is not overwritten. */
+int mk_mt_lamb(int stage, int T, const uint64_t* pgmv, const long long* n, const int* step_or_slot, const float* steps,
+               float lr, const float* lr_dev, float beta1, float beta2, float beta3, float eps, float weight_decay, int adamw,
+               int bias_correction, int trust, const float* coef, double* part_p, double* part_u, double* tsum_p,
+               double* tsum_u, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,14 @@ SIGNATURES = {
     "mk_adam_step": (_c_int, [_vp, _vp, _vp, _vp, ctypes.c_longlong] + [_c_float] * 5 + [_c_int, _vp]),
     "mk_instnorm_bwd": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong,
                                  _c_int, _vp]),
+    "mk_mt_chunks": (ctypes.c_longlong, [ctypes.c_longlong]),
+    "mk_mt_sumsq": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_int, _c_float, _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "mk_mt_norm_finish": (_c_int, [_c_int, _vp, _c_int, _c_float, _vp, _vp, _vp, _vp, _c_int, _vp]),
+    "mk_mt_step_inc": (_c_int, [_vp, _vp, _c_int, _vp]),
+    "mk_mt_scale": (_c_int, [_c_int, _vp, _vp, _vp, _vp]),
+    "mk_mt_adam": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_float, _vp] + [_c_float] * 4 + [_c_int, _vp, _vp]),
+    "mk_mt_lamb": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _vp, _c_float, _vp] + [_c_float] * 5 + [_c_int] * 3
+                   + [_vp] * 6),
 }
 
 
