@@ -356,6 +356,18 @@ int mk_mt_lamb(int stage, int T, const uint64_t* pgmv, const long long* n, const
                int bias_correction, int trust, const float* coef, double* part_p, double* part_u, double* tsum_p,
                double* tsum_u, void* stream);
 
+/* ---- validation metrics (csrc/metrics.hip): geometric L1, RMSE and ACC of the trainer's MetricsHandler
+ * (makani/utils/metrics/functions.py:20-107, makani/utils/metric.py:186-204) as five latitude-weighted integrals per
+ * (sample, channel), written to sums [B][C][5] (fp64) in the order
+ *   sum w |p - t|,  sum w (p - t)^2,  sum w (p - c)(t - c),  sum w (p - c)^2,  sum w (t - c)^2
+ * with w = wrow[h] and c = clim[c][h][w] (c = 0 when clim is NULL).  pred [B][C][H][W] fp32 (dtype 0) or bf16 (1),
+ * tar [B][C][H][W] fp32, clim [C][H][W] fp32 shared by all samples, wrow [H] fp32; any W and any element-aligned
+ * pointers.  The sums add up over spatial shards (the caller slices wrow and clim to its shard).  Deterministic (no
+ * atomics); no allocation, synchronisation or host copy: `workspace` holds mk_geo_metric_workspace(B, C, H) doubles. */
+long long mk_geo_metric_workspace(int B, int C, int H);
+int mk_geo_metric_sums(const void* pred, int dtype, const float* tar, const float* clim, const float* wrow, double* workspace,
+                       double* sums, int B, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

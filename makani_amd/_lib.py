@@ -96,6 +96,8 @@ SIGNATURES = {
     "mk_mt_adam": (_c_int, [_c_int, _vp, _vp, _vp, _vp, _c_float, _vp] + [_c_float] * 4 + [_c_int, _vp, _vp]),
     "mk_mt_lamb": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _vp, _c_float, _vp] + [_c_float] * 5 + [_c_int] * 3
                    + [_vp] * 6),
+    "mk_geo_metric_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "mk_geo_metric_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp]),
 }
 
 

@@ -1071,3 +1071,47 @@ def instance_norm(x, weight, bias, eps=1e-5, fuse_gelu=False, group=None, count=
     """``row_sums``: fp64 ``[B * C, 2]`` LOCAL (sum, sum of squares) of every row of ``x`` when its producer already has
     them (``pce_gemm(..., want_row_sums=True)``); the statistics pass over ``x`` is then skipped."""
     return _InstanceNorm.apply(x, weight, bias, eps, fuse_gelu, group, count, row_sums)
+
+
+# ----------------------------------------------------------------------------
+# validation metrics (csrc/metrics.hip)
+# ----------------------------------------------------------------------------
+GEO_METRIC_SUMS = ("l1", "sq", "cov", "var_p", "var_t")     # order of the last axis of geo_metric_sums
+
+
+@torch.no_grad()
+def geo_metric_sums(prd, tar, clim, wrow):
+    """Latitude-weighted integrals of the validation metrics, ``[B, C, 5]`` float64 in the order of ``GEO_METRIC_SUMS``:
+    sum w |p - t|, sum w (p - t)^2, sum w (p - c)(t - c), sum w (p - c)^2, sum w (t - c)^2 over each ``[H, W]`` field,
+    with w = ``wrow[h]`` and c = ``clim`` (``[C, H, W]``, shared by all samples; ``None``: c = 0).
+
+    CUDA tensors: one streaming HIP pass plus a fixed-order finalize (``mk_geo_metric_sums``; bitwise repeatable,
+    capturable).  The prediction is read as fp32 or bf16, everything else as fp32.  CPU tensors: the same sums in
+    torch float64.  No gradient flows through this op."""
+    if prd.dim() != 4 or tar.shape != prd.shape:
+        raise ValueError(f"geo_metric_sums: prediction {tuple(prd.shape)} and target {tuple(tar.shape)} must be equal [B, C, H, W]")
+    B, C, H, W = prd.shape
+    if wrow.numel() != H:
+        raise ValueError(f"geo_metric_sums: wrow has {wrow.numel()} weights for {H} latitude rows")
+    if clim is not None and tuple(clim.shape[-3:]) != (C, H, W):
+        raise ValueError(f"geo_metric_sums: climatology {tuple(clim.shape)} does not match [C, H, W] = {(C, H, W)}")
+    if not prd.is_cuda:
+        p, t = prd.double(), tar.double()
+        w = wrow.double().reshape(1, 1, H, 1)
+        c = clim.double().reshape(1, C, H, W) if clim is not None else torch.zeros((), dtype=torch.float64)
+        d, pa, ta = p - t, p - c, t - c
+        return torch.stack([(w * d.abs()).sum((-2, -1)), (w * d * d).sum((-2, -1)), (w * pa * ta).sum((-2, -1)),
+                            (w * pa * pa).sum((-2, -1)), (w * ta * ta).sum((-2, -1))], dim=-1)
+    _need_cuda(prd, tar, wrow, *([clim] if clim is not None else []))
+    if prd.dtype not in (torch.float32, torch.bfloat16):
+        prd = prd.float()
+    prd = prd.contiguous()
+    tar = tar.float().contiguous()
+    wrow = wrow.float().contiguous()
+    clim = clim.float().contiguous() if clim is not None else None
+    lib = _lib.load()
+    ws = torch.empty(lib.mk_geo_metric_workspace(B, C, H), dtype=torch.float64, device=prd.device)
+    out = torch.empty(B, C, 5, dtype=torch.float64, device=prd.device)
+    _lib.check(lib.mk_geo_metric_sums(prd.data_ptr(), _pw_dtype(prd), tar.data_ptr(), clim.data_ptr() if clim is not None else None,
+                                      wrow.data_ptr(), ws.data_ptr(), out.data_ptr(), B, C, H, W, _stream()), "mk_geo_metric_sums")
+    return out
