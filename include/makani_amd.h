@@ -368,6 +368,21 @@ long long mk_geo_metric_workspace(int B, int C, int H);
 int mk_geo_metric_sums(const void* pred, int dtype, const float* tar, const float* clim, const float* wrow, double* workspace,
                        double* sums, int B, int C, int H, int W, void* stream);
 
+/* ---- training losses of the Lp family (csrc/lploss.hip): every spelling of GeometricLpLoss
+ * (makani/utils/losses.py:174-271) is a function of two latitude-weighted integrals per (sample, channel), written to
+ * sums [B][C][2] (fp64) in the order
+ *   s0 = sum w |p - t|^P,   s1 = sum w |t|^P,   P = p in {1, 2},   w = wrow[h].
+ * pred [B][C][H][W] fp32 (dtype 0) or bf16 (1), tar [B][C][H][W] fp32, wrow [H] fp32; any W and any element-aligned
+ * pointers.  The sums add up over spatial shards (the caller slices wrow to its shard).  Deterministic (no atomics); no
+ * allocation, synchronisation or host copy: `workspace` holds mk_geo_lp_workspace(B, C, H) doubles.
+ * Backward of s0 with respect to pred, g [B][C] fp32 on the device (the upstream gradient of s0):
+ *   gpred = g[b][c] * wrow[h] * (p == 2 ? 2 (pred - tar) : sign(pred - tar)),  sign(0) = 0,  in pred's dtype. */
+long long mk_geo_lp_workspace(int B, int C, int H);
+int mk_geo_lp_sums(const void* pred, int dtype, const float* tar, const float* wrow, double* workspace, double* sums, int p,
+                   int B, int C, int H, int W, void* stream);
+int mk_geo_lp_bwd(const void* pred, int dtype, const float* tar, const float* wrow, const float* g, void* gpred, int p,
+                  int B, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

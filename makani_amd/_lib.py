@@ -98,6 +98,9 @@ SIGNATURES = {
                    + [_vp] * 6),
     "mk_geo_metric_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "mk_geo_metric_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "mk_geo_lp_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "mk_geo_lp_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
+    "mk_geo_lp_bwd": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
 }
 
 

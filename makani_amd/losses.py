@@ -2,13 +2,20 @@
 
 Interface and arithmetic of ``makani/utils/grids.py:63-115`` (``GridQuadrature``) and ``makani/utils/losses.py:33-271``
 (``LossHandler``, ``GeometricLpLoss``): per-sample, per-channel integrals of ``|prd - tar| ** p`` with the latitude
-quadrature of the model grid, relative or absolute, optionally squared, channel-weighted, summed.  Under spatial model
-parallelism prediction and target are gathered over ``h`` then ``w`` before the integral, as the reference does
-(``losses.py:149-157``).
+quadrature of the model grid, relative or absolute, optionally squared, channel-weighted, summed.
 
-The quadrature weights depend on the latitude only.  For the absolute squared L2 norm with uniform channel weights --
-the loss the bench harness trains with -- the whole thing is one streaming HIP pass over prediction and target
-(``ops.weighted_mse`` / ``mk_wmse_fwd``, ``mk_wmse_bwd``); every other combination runs on torch ops.
+The quadrature weights depend on the latitude only, so for p = 1 and p = 2 every spelling is a function of two sums per
+(sample, channel), ``sum w |prd - tar| ** p`` and ``sum w |tar| ** p``: one streaming HIP pass over prediction and target
+forward and one backward (``ops.geo_lp_sums`` / ``mk_geo_lp_sums``, ``mk_geo_lp_bwd``; torch float64 on CPU tensors),
+followed by the ratio, the root, the channel weights and the reduction on ``[B, C]`` tensors.  The absolute squared L2
+norm with uniform channel weights -- the loss the bench harness trains with -- keeps its own single pass
+(``ops.weighted_mse`` / ``mk_wmse_fwd``, ``mk_wmse_bwd``).  Other ``p`` run on torch ops.
+
+Under spatial model parallelism the reference gathers prediction and target over ``h`` then ``w`` (``losses.py:149-157``)
+and every rank integrates both full fields.  The integrals add up across shards, so here a rank integrates its own shard
+with its slice of the latitude weights and the ``[B, C, 2]`` float64 sums are all-reduced over the ``"spatial"`` group;
+the gradient of the all-reduce is the identity, which leaves every rank with its shard of the global gradient.  Only the
+H1 loss still gathers.
 """
 import math
 
@@ -18,7 +25,7 @@ from torch import nn
 
 from . import comm
 from .distributed import compute_split_shapes
-from .mappings import gather_from_parallel_region
+from .mappings import gather_from_parallel_region, reduce_from_parallel_region
 
 
 def _latitude_weights(rule, nlat):
@@ -78,6 +85,10 @@ class GeometricLpLoss(nn.Module):
         self.quadrature = GridQuadrature(quadrature_rule, img_shape=img_shape, crop_shape=crop_shape, crop_offset=crop_offset,
                                          normalize=True, pole_mask=pole_mask)
         self.uniform_chw = None     # set by the owner of the channel weights when they are all equal (see _fused_abs_sq_l2)
+        # the weights do not vary along a latitude row: one per row, as built (CPU float64 path) and in fp32 (kernels)
+        wrow = self.quadrature.quad_weight[0, 0, :, 0].contiguous()
+        self.register_buffer("wrow", wrow, persistent=False)
+        self.register_buffer("wrow32", wrow.float(), persistent=False)
 
     def _reduce(self, v):
         if not self.reduction:
@@ -101,13 +112,33 @@ class GeometricLpLoss(nn.Module):
                 value = float(c0[0])
         if value is None:
             return None
-        wrow = self.quadrature.quad_weight[0, 0, :, 0].contiguous()        # the weights do not vary along a latitude row
-        return ops.weighted_mse(prd, tar, wrow, value)
+        return ops.weighted_mse(prd, tar, self.wrow32, value)
+
+    def has_sums(self, prd, tar):
+        """True when the loss is formed from ``sums`` (p = 1 or 2 on [B, C, H, W] fields)."""
+        return self.p in (1, 2) and prd.dim() == 4 and tar.shape == prd.shape
+
+    def sums(self, prd, tar, rows=None):
+        """``[B, C, 2]`` float64 integrals of ``|prd - tar| ** p`` and ``|tar| ** p`` over the fields' latitude rows
+        ``rows`` (a slice of the cropped grid's rows; all of them by default) -- they add up over spatial shards."""
+        from . import ops
+        wrow = self.wrow32 if prd.is_cuda else self.wrow
+        return ops.geo_lp_sums(prd, tar, wrow if rows is None else wrow[rows], int(self.p))
+
+    def from_sums(self, sums, chw):
+        """The loss (fp32) from the integrals of the whole field: ratio, root, channel weights, reduction."""
+        s0, s1 = sums.unbind(-1)
+        norms = s0 if self.absolute else s0 / s1
+        if not self.squared:
+            norms = norms ** (1.0 / self.p)
+        return self._reduce(chw * norms).float()
 
     def abs(self, prd, tar, chw):
         fused = self._fused_abs_sq_l2(prd, tar, chw)
         if fused is not None:
             return fused
+        if self.has_sums(prd, tar):
+            return self.from_sums(self.sums(prd, tar), chw)
         num_examples = prd.size()[0]
         all_norms = self.quadrature(torch.abs(prd - tar) ** self.p).reshape(num_examples, -1)
         if not self.squared:
@@ -115,6 +146,8 @@ class GeometricLpLoss(nn.Module):
         return self._reduce(chw * all_norms)
 
     def rel(self, prd, tar, chw):
+        if self.has_sums(prd, tar):
+            return self.from_sums(self.sums(prd, tar), chw)
         num_examples = prd.size()[0]
         diff_norms = self.quadrature(torch.abs(prd - tar) ** self.p).reshape(num_examples, -1)
         tar_norms = self.quadrature(torch.abs(tar) ** self.p).reshape(num_examples, -1)
@@ -179,8 +212,9 @@ class GeometricH1Loss(nn.Module):
 
 class LossHandler(nn.Module):
     """losses.py:33-172 for the Lp family: parses ``params.loss`` ("l2", "geometric l2", "absolute squared geometric l2",
-    "weighted ...", "pole-masked ...", "l1" ...), builds channel / multistep weights, gathers the spatial shards and
-    calls the loss object.  ``params`` is the trainer's parameter object (attribute access)."""
+    "weighted ...", "pole-masked ...", "l1" ...), builds channel / multistep weights and calls the loss object.  Under
+    spatial parallelism the Lp family all-reduces its per-shard sums and the H1 loss gathers the shards.  ``params`` is
+    the trainer's parameter object (attribute access)."""
 
     def __init__(self, params):
         super().__init__()
@@ -243,6 +277,9 @@ class LossHandler(nn.Module):
         if self.do_gather_input:
             self.gather_shapes_h = compute_split_shapes(self.crop_shape[0], comm.get_size("h"))
             self.gather_shapes_w = compute_split_shapes(self.crop_shape[1], comm.get_size("w"))
+            # this rank's latitude rows of the cropped grid (a w shard holds whole rows' weights: nothing to slice)
+            h0 = sum(self.gather_shapes_h[:comm.get_rank("h")])
+            self.shard_rows = slice(h0, h0 + self.gather_shapes_h[comm.get_rank("h")])
 
     def _gather_input(self, x):
         xh = gather_from_parallel_region(x, -2, self.gather_shapes_h, "h")
@@ -252,10 +289,13 @@ class LossHandler(nn.Module):
         return False
 
     def forward(self, prd, tar, inp=None):
-        if self.do_gather_input:
-            prd, tar = self._gather_input(prd), self._gather_input(tar)
         chw = self.channel_weights
         chw = (chw * self.multistep_weight).reshape(1, -1) if self.training else chw.reshape(1, -1)
+        if self.do_gather_input:
+            if isinstance(self.loss_obj, GeometricLpLoss) and self.loss_obj.has_sums(prd, tar):
+                sums = self.loss_obj.sums(prd, tar, self.shard_rows)
+                return self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
+            prd, tar = self._gather_input(prd), self._gather_input(tar)
         if isinstance(self.loss_obj, GeometricLpLoss):
             self.loss_obj.uniform_chw = self._uniform[bool(self.training)]
         if isinstance(self.loss_obj, GeometricH1Loss):

@@ -1115,3 +1115,64 @@ def geo_metric_sums(prd, tar, clim, wrow):
     _lib.check(lib.mk_geo_metric_sums(prd.data_ptr(), _pw_dtype(prd), tar.data_ptr(), clim.data_ptr() if clim is not None else None,
                                       wrow.data_ptr(), ws.data_ptr(), out.data_ptr(), B, C, H, W, _stream()), "mk_geo_metric_sums")
     return out
+
+
+# ----------------------------------------------------------------------------
+# training losses of the Lp family (csrc/lploss.hip)
+# ----------------------------------------------------------------------------
+def _geo_lp_sums_torch(prd, tar, wrow, p):
+    """The two sums in torch float64 on the tensors' device, differentiable in both fields by ordinary autograd."""
+    w = wrow.double().reshape(1, 1, -1, 1)
+    d, t = prd.double() - tar.double(), tar.double()
+    if p == 2:
+        return torch.stack([(w * d * d).sum((-2, -1)), (w * t * t).sum((-2, -1))], dim=-1)
+    return torch.stack([(w * d.abs()).sum((-2, -1)), (w * t.abs()).sum((-2, -1))], dim=-1)
+
+
+class _GeoLpSums(torch.autograd.Function):
+    """[B, C, 2] float64 (sum w |prd - tar|^p, sum w |tar|^p); one streaming pass each way (mk_geo_lp_sums, mk_geo_lp_bwd)."""
+
+    @staticmethod
+    def forward(ctx, prd, tar, wrow, p):
+        B, C, H, W = prd.shape
+        lib = _lib.load()
+        ws = torch.empty(lib.mk_geo_lp_workspace(B, C, H), dtype=torch.float64, device=prd.device)
+        out = torch.empty(B, C, 2, dtype=torch.float64, device=prd.device)
+        _lib.check(lib.mk_geo_lp_sums(prd.data_ptr(), _pw_dtype(prd), tar.data_ptr(), wrow.data_ptr(), ws.data_ptr(),
+                                      out.data_ptr(), p, B, C, H, W, _stream()), "mk_geo_lp_sums")
+        ctx.save_for_backward(prd, tar, wrow)
+        ctx.p = p
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        prd, tar, wrow = ctx.saved_tensors
+        B, C, H, W = prd.shape
+        gp = torch.empty_like(prd)
+        g0 = g[..., 0].float().contiguous()          # the upstream gradient of s0; s1 does not depend on the prediction
+        _lib.check(_lib.load().mk_geo_lp_bwd(prd.data_ptr(), _pw_dtype(prd), tar.data_ptr(), wrow.data_ptr(), g0.data_ptr(),
+                                             gp.data_ptr(), ctx.p, B, C, H, W, _stream()), "mk_geo_lp_bwd")
+        return gp, None, None, None
+
+
+def geo_lp_sums(prd, tar, wrow, p):
+    """Latitude-weighted integrals of the Lp losses, ``[B, C, 2]`` float64: ``sum w |prd - tar| ** p`` and
+    ``sum w |tar| ** p`` over each ``[H, W]`` field, with w = ``wrow[h]`` and ``p`` 1 or 2.
+
+    CUDA tensors: one streaming HIP pass plus a fixed-order finalize (``mk_geo_lp_sums``; bitwise repeatable, capturable)
+    and one streaming pass for the gradient of the prediction (``mk_geo_lp_bwd``).  The prediction is read as fp32 or
+    bf16 and its gradient written in the same dtype; target and weights are read as fp32.  CPU tensors, or a target that
+    requires a gradient: the same sums in torch float64, differentiated by ordinary autograd."""
+    if p not in (1, 2):
+        raise ValueError(f"geo_lp_sums: p must be 1 or 2, got {p}")
+    if prd.dim() != 4 or tar.shape != prd.shape:
+        raise ValueError(f"geo_lp_sums: prediction {tuple(prd.shape)} and target {tuple(tar.shape)} must be equal [B, C, H, W]")
+    if wrow.numel() != prd.shape[-2]:
+        raise ValueError(f"geo_lp_sums: wrow has {wrow.numel()} weights for {prd.shape[-2]} latitude rows")
+    if not prd.is_cuda or tar.requires_grad:
+        return _geo_lp_sums_torch(prd, tar, wrow, int(p))
+    _need_cuda(prd, tar, wrow)
+    if prd.dtype not in (torch.float32, torch.bfloat16):
+        prd = prd.float()
+    return _GeoLpSums.apply(prd.contiguous(), tar.float().contiguous(), wrow.detach().float().contiguous(), int(p))
