@@ -383,6 +383,34 @@ int mk_geo_lp_sums(const void* pred, int dtype, const float* tar, const float* w
 int mk_geo_lp_bwd(const void* pred, int dtype, const float* tar, const float* wrow, const float* g, void* gpred, int p,
                   int B, int C, int H, int W, void* stream);
 
+/* ---- input assembly of the step wrappers (csrc/preproc.hip): what makani/models/stepper.py builds before every model
+ * call, add_static_features(history_normalize(append_unpredicted_features(x))), in one pass that reads every source
+ * once and writes every output element once.
+ *   x    [B][T][C][H][W]   predicted channels, T = n_history + 1, fp32 (dtype 0) or bf16 (1)
+ *   u    [B][T][Cu][H][W]  unpredicted channels, fp32 (NULL exactly when Cu == 0)
+ *   stat [Cs][H][W]        static features, fp32, shared by all samples (NULL exactly when Cs == 0)
+ *   mean, std [B][C + Cu]  fp32, both or neither; given: v -> (v - mean) / std with a correctly rounded division
+ *   mask_chans [n_mask]    int32 on the device: output channels (< T (C + Cu)) multiplied by stat[mask_src] pointwise
+ *                          (entries outside that range match no row); mask_src is checked on the host
+ *   out  [B][T (C + Cu) + Cs][H][W], channel t (C + Cu) + j = step t, channel j of (x | u); fp32 (0) or bf16 (1, RNE)
+ * Any W and any element-aligned pointers.  No allocation, synchronisation or host copy.
+ * Backward, the gradient of x only (statistics are constants):
+ *   gx[b][t][c] = (gout[b][t (C + Cu) + c] * mask) / std[b][c]   (std NULL: no division), gout fp32 / bf16, gx in
+ *   x's dtype. */
+int mk_input_assemble(const void* x, int x_dtype, const float* u, const float* stat, const float* mean, const float* std,
+                      const int* mask_chans, int n_mask, int mask_src, void* out, int out_dtype, int B, int T, int C, int Cu,
+                      int Cs, int H, int W, void* stream);
+int mk_input_assemble_bwd(const void* gout, int g_dtype, const float* stat, const float* std, const int* mask_chans, int n_mask,
+                          int mask_src, void* gx, int x_dtype, int B, int T, int C, int Cu, int Cs, int H, int W, void* stream);
+
+/* History statistics of Preprocessor2D.history_compute_stats as raw sums: sums [B][C + Cu][2] (fp64),
+ *   sum_t wt[t] sum_hw v,   sum_t wt[t] sum_hw v^2,   v = (x | u)[b][t][j][h][w],   wt [T] fp32 on the device.
+ * Accumulated in fp64 throughout, deterministic (no atomics); the sums add up over spatial shards.  No allocation,
+ * synchronisation or host copy: `workspace` holds mk_history_workspace(B, C + Cu, H) doubles. */
+long long mk_history_workspace(int B, int Cn, int H);
+int mk_history_sums(const void* x, int x_dtype, const float* u, const float* wt, double* workspace, double* sums, int B, int T,
+                    int C, int Cu, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,10 @@ SIGNATURES = {
     "mk_geo_lp_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "mk_geo_lp_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
     "mk_geo_lp_bwd": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
+    "mk_input_assemble": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_c_int] * 7 + [_vp]),
+    "mk_input_assemble_bwd": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_c_int] * 7 + [_vp]),
+    "mk_history_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "mk_history_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_vp]),
 }
 
 

@@ -1176,3 +1176,118 @@ def geo_lp_sums(prd, tar, wrow, p):
     if prd.dtype not in (torch.float32, torch.bfloat16):
         prd = prd.float()
     return _GeoLpSums.apply(prd.contiguous(), tar.float().contiguous(), wrow.detach().float().contiguous(), int(p))
+
+
+# ----------------------------------------------------------------------------
+# input assembly of the step wrappers (csrc/preproc.hip)
+# ----------------------------------------------------------------------------
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _history_sums_torch(xa, wt):
+    """``[B, Cn, 2]`` float64 from the concatenated history ``xa`` ``[B, T, Cn, H, W]``, differentiable by autograd."""
+    w = wt.double().reshape(1, -1, 1, 1, 1)
+    v = xa.double()
+    return torch.stack([(v * w).sum((1, 3, 4)), (v * v * w).sum((1, 3, 4))], dim=-1)
+
+
+@torch.no_grad()
+def history_sums(x, u, wt):
+    """Weighted raw sums of the history statistics, ``[B, C + Cu, 2]`` float64: ``sum_t wt[t] sum_hw v`` and
+    ``sum_t wt[t] sum_hw v ** 2`` over the channels of ``x`` ``[B, T, C, H, W]`` (fp32 or bf16) followed by those of ``u``
+    ``[B, T, Cu, H, W]`` (fp32, or ``None``).
+
+    CUDA tensors: one streaming HIP pass in fp64 plus a fixed-order finalize (``mk_history_sums``; bitwise repeatable,
+    capturable).  CPU tensors: the same sums in torch float64.  No gradient flows through this op; a caller that needs
+    one forms the sums with ordinary torch ops."""
+    if x.dim() != 5 or (u is not None and (u.dim() != 5 or u.shape[:2] != x.shape[:2] or u.shape[3:] != x.shape[3:])):
+        raise ValueError(f"history_sums: x {tuple(x.shape)} must be [B, T, C, H, W] and u, if given, [B, T, Cu, H, W]")
+    B, T, C, H, W = x.shape
+    if wt.numel() != T:
+        raise ValueError(f"history_sums: {wt.numel()} weights for {T} history steps")
+    if not x.is_cuda:
+        return _history_sums_torch(x if u is None else torch.cat([x.float(), u], dim=2), wt.reshape(-1))
+    _need_cuda(x, wt, *([u] if u is not None else []))
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    x = x.contiguous()
+    u = u.float().contiguous() if u is not None else None
+    wt = wt.float().reshape(-1).contiguous()
+    Cu = u.shape[2] if u is not None else 0
+    lib = _lib.load()
+    ws = torch.empty(lib.mk_history_workspace(B, C + Cu, H), dtype=torch.float64, device=x.device)
+    out = torch.empty(B, C + Cu, 2, dtype=torch.float64, device=x.device)
+    _lib.check(lib.mk_history_sums(x.data_ptr(), _pw_dtype(x), _ptr(u), wt.data_ptr(), ws.data_ptr(), out.data_ptr(),
+                                   B, T, C, Cu, H, W, _stream()), "mk_history_sums")
+    return out
+
+
+class _InputAssemble(torch.autograd.Function):
+    """One pass each way (mk_input_assemble, mk_input_assemble_bwd); the gradient is that of ``x`` alone, with the
+    statistics taken as constants."""
+
+    @staticmethod
+    def forward(ctx, x, u, stat, mean, std, mask_chans, mask_src, out_dtype):
+        B, T, C, H, W = x.shape
+        Cu = u.shape[2] if u is not None else 0
+        Cs = stat.shape[0] if stat is not None else 0
+        n_mask = mask_chans.numel() if mask_chans is not None else 0
+        out = torch.empty(B, T * (C + Cu) + Cs, H, W, dtype=out_dtype, device=x.device)
+        _lib.check(_lib.load().mk_input_assemble(x.data_ptr(), _pw_dtype(x), _ptr(u), _ptr(stat), _ptr(mean), _ptr(std),
+                                                 _ptr(mask_chans), n_mask, mask_src, out.data_ptr(), _pw_dtype(out),
+                                                 B, T, C, Cu, Cs, H, W, _stream()), "mk_input_assemble")
+        ctx.save_for_backward(stat, std, mask_chans)
+        ctx.meta = (x.dtype, mask_src, B, T, C, Cu, Cs, H, W)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        stat, std, mask_chans = ctx.saved_tensors
+        x_dtype, mask_src, B, T, C, Cu, Cs, H, W = ctx.meta
+        if g.dtype not in (torch.float32, torch.bfloat16):
+            g = g.float()
+        g = g.contiguous()
+        gx = torch.empty(B, T, C, H, W, dtype=x_dtype, device=g.device)
+        n_mask = mask_chans.numel() if mask_chans is not None else 0
+        _lib.check(_lib.load().mk_input_assemble_bwd(g.data_ptr(), _pw_dtype(g), _ptr(stat), _ptr(std), _ptr(mask_chans),
+                                                     n_mask, mask_src, gx.data_ptr(), _pw_dtype(gx), B, T, C, Cu, Cs, H, W,
+                                                     _stream()), "mk_input_assemble_bwd")
+        return gx, None, None, None, None, None, None, None
+
+
+def input_assemble(x, u=None, stat=None, mean=None, std=None, mask_chans=None, mask_src=-1, out_dtype=torch.float32):
+    """The model input of the step wrappers in one HIP pass: ``[B, T (C + Cu) + Cs, H, W]`` in ``out_dtype`` (fp32 or
+    bf16) from the predicted channels ``x`` ``[B, T, C, H, W]`` (fp32 or bf16), the unpredicted channels ``u``
+    ``[B, T, Cu, H, W]``, the static features ``stat`` ``[Cs, H, W]`` shared by all samples, the statistics ``mean`` /
+    ``std`` ``[B, C + Cu]`` (``(v - mean) / std``, both or neither) and ``mask_chans``, an int32 device tensor of output
+    channels that are multiplied by ``stat[mask_src]``.  Everything but ``x`` is read as fp32.
+
+    Differentiable in ``x`` only (``mk_input_assemble_bwd``): the statistics are constants to this op.  A gradient
+    through the statistics is the business of the torch formulation (``Preprocessor2D._assemble_torch``).  CUDA only."""
+    _need_cuda(x, *[t for t in (u, stat, mean, std, mask_chans) if t is not None])
+    if x.dim() != 5:
+        raise ValueError(f"input_assemble: x {tuple(x.shape)} must be [B, T, C, H, W]")
+    B, T, C, H, W = x.shape
+    if u is not None and (u.dim() != 5 or tuple(u.shape[:2]) != (B, T) or tuple(u.shape[3:]) != (H, W)):
+        raise ValueError(f"input_assemble: u {tuple(u.shape)} does not match x {tuple(x.shape)}")
+    if stat is not None and (stat.dim() != 3 or tuple(stat.shape[1:]) != (H, W)):
+        raise ValueError(f"input_assemble: static features {tuple(stat.shape)} must be [Cs, {H}, {W}]")
+    Cn = C + (u.shape[2] if u is not None else 0)
+    if (mean is None) != (std is None) or (mean is not None and (mean.numel() != B * Cn or std.numel() != B * Cn)):
+        raise ValueError(f"input_assemble: mean and std must both be [B, C + Cu] = {(B, Cn)}")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"input_assemble: output dtype {out_dtype} is neither fp32 nor bf16")
+    if mask_chans is not None and mask_chans.numel() == 0:
+        mask_chans = None
+    if mask_chans is not None and mask_chans.dtype != torch.int32:
+        raise ValueError("input_assemble: mask_chans must be int32")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+
+    def f32(t):
+        return t.detach().float().contiguous() if t is not None else None
+
+    return _InputAssemble.apply(x.contiguous(), f32(u), f32(stat), f32(mean), f32(std),
+                                mask_chans.contiguous() if mask_chans is not None else None, int(mask_src), out_dtype)
