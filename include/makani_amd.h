@@ -146,6 +146,13 @@ int mk_irfft_pm(const float* xf, void* x, int x_dtype, const float* twiddles, in
 int mk_irfft_sums(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon, int mmax,
                   float scale0, float scale_m, float scale_h, int xf_layout, int chans, int chans_per_peer, double* rowsums,
                   void* stream);
+/* The same inverse transform with a companion field added in the store epilogue under a per-row affine map:
+ *   x[r] = irfft(xf)[r] + affine[r][0] * z[r] + affine[r][1]     z, x: [bc][nlat][nlon] in x_dtype; affine fp32 [bc][2]
+ * -- a skip connection synthesised from the (channel-mixed) spectrum plus the apply pass of the instance norm of z
+ * (mk_instnorm_coeffs): the synthesised field is never written on its own.  Split kernels only (nlon 480 / 1440, mmax <= 241). */
+int mk_irfft_affine_add(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon,
+                        int mmax, float scale0, float scale_m, float scale_h, int xf_layout, const void* z,
+                        const float* affine, void* stream);
 
 /* ---- spectral filter contraction (K5) ---------------------------------- */
 /* y[l][m][b][o] = sum_i x[l][m][b][i] * w[l][i][o]  (complex), for global m <= l.
@@ -169,6 +176,23 @@ int mk_dhconv_dgrad_x3(const float* gy, const float* w, float* gx, int lloc, int
                        int cin, int cout, int l_off, int m_off, void* stream);
 int mk_dhconv_wgrad_x3(const float* x, const float* gy, float* gw, int lloc, int mloc, int batch,
                        int cin, int cout, int l_off, int m_off, void* stream);
+
+/* ---- real channel mix on the spectrum -------------------------------------------------------
+ * A bias-free 1x1 convolution commutes with the spherical harmonic transform (linear, the same for every
+ * channel): sht(W x) = W sht(x), isht(W c) = W isht(c).  A convolution that sits next to a transform
+ * (the encoder's last one, nn.Conv2d(embed, embed, 1, bias=False) of layers.py:124-131; the outer skip of
+ * the last block, sfnonet.py:223-234) is evaluated on the private spectrum instead of the grid:
+ *   fwd:   y[l][m][b][o]  = sum_i W[o][i] x[l][m][b][i]        W fp32 real [cout][cin], the same for every l
+ *   dgrad: gx[l][m][b][i] = sum_o W[o][i] gy[l][m][b][o]
+ *   wgrad: gw[o][i]      += sum_{m<=l, b} re(gy[l][m][b][o] * conj(x[l][m][b][i]))   (atomic adds: caller zeroes gw)
+ * for global m <= l only (entries with l < m are neither read nor written), l_off / m_off as for dhconv.
+ * bf16x3 engine (fp32-accurate); cin, cout even, operands 16-byte aligned. */
+int mk_spec_mix_fwd(const float* x, const float* w, float* y, int lloc, int mloc, int batch,
+                    int cin, int cout, int l_off, int m_off, void* stream);
+int mk_spec_mix_dgrad(const float* gy, const float* w, float* gx, int lloc, int mloc, int batch,
+                      int cin, int cout, int l_off, int m_off, void* stream);
+int mk_spec_mix_wgrad(const float* x, const float* gy, float* gw, int lloc, int mloc, int batch,
+                      int cin, int cout, int l_off, int m_off, void* stream);
 
 /* ---- "diagonal" spectral filter: one complex weight per (l, m) ---------------------------
  * Public layout, P = L * M contiguous: x [B][I][P], w [I][O][P], y [B][O][P] complex64.
@@ -196,6 +220,10 @@ int mk_bias_gelu_fwd(const void* x, const float* bias, void* y, int dtype, int r
 /* gx = gy * gelu'(x + bias); gbias[c] += sum over (b, p) of gx (caller zeroes gbias; may be NULL). */
 int mk_bias_gelu_bwd(const void* x, const float* bias, const void* gy, void* gx, float* gbias, int dtype,
                      int rows, int C, long long P, void* stream);
+/* y = r + affine[row][0] * z + affine[row][1]: the apply pass of an instance norm (coefficients from mk_instnorm_coeffs)
+ * with the skip add, for a skip that was synthesised from the spectrum (mk_spec_mix_fwd).  affine fp32 [rows][2]. */
+int mk_affine_add(const void* r, const void* z, const float* affine, void* y, int dtype, int rows, long long P,
+                  void* stream);
 /* Instance norm over each row, y = act(((x - mean) * rstd) * weight[c] + bias[c]), biased variance,
  * act = GELU if fuse_gelu else identity.  stats[row] = (mean, rstd) is kept for the backward;
  * workspace: 2*rows doubles (zeroed inside).  Replaces nn.InstanceNorm2d(eps=1e-6, affine=True)

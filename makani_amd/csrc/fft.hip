@@ -14,6 +14,7 @@
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
+#include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -32,6 +33,8 @@ struct XfLayout {
     long long pstride;    // K * M * Bn * Cp
 };
 static thread_local XfLayout g_xl = {0, 0, 0, 0, 0, 0};   // set by the C entry points before they launch
+static thread_local const void* g_addz = nullptr;         // mk_irfft_affine_add: companion field and its per-row (a, b)
+static thread_local const float* g_affine = nullptr;
 static thread_local double* g_rowsums = nullptr;          // mk_irfft_sums: per-row (sum, sum of squares) accumulators of the output
 
 // per-tile channel addressing: all G rows of a split-kernel tile lie in one (batch item, channel block) when Cp % G == 0
@@ -630,5 +633,25 @@ extern "C" int mk_irfft_sums(const float* xf, void* x, int x_dtype, const float*
         ? mk_irfft_pm(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, chans, chans_per_peer, stream)
         : mk_irfft_ex(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xf_layout, stream);
     g_rowsums = nullptr;
+    return rc;
+}
+
+// Inverse transform whose store epilogue adds a companion field under a per-row affine map:
+//   x[r] = irfft(xf)[r] + affine[r][0] * z[r] + affine[r][1]      z, x: [bc][nlat][nlon] in x_dtype, affine fp32 [bc][2]
+// -- a skip connection synthesised from the spectrum plus the apply pass of the instance norm of z (mk_instnorm_coeffs), without
+// the synthesised field ever existing on its own.  Split kernels only (nlon 480 / 1440, mmax <= 241); xf_layout as in mk_irfft_ex.
+extern "C" int mk_irfft_affine_add(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon,
+                                   int mmax, float scale0, float scale_m, float scale_h, int xf_layout, const void* z,
+                                   const float* affine, void* stream) {
+    MK_REQUIRE(z != nullptr && affine != nullptr, "null pointer");
+    MK_REQUIRE(!fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440), "the affine-add epilogue exists in the split kernels only");
+    MK_REQUIRE((((uintptr_t)z | (uintptr_t)x) & 15) == 0, "fields must be 16-byte aligned");
+    MK_REQUIRE(xf_layout == 0 || xf_layout == 1, "xf_layout must be 0 ([M][K][BC]) or 1 ([K][M][BC])");
+    MK_REQUIRE((240LL * (xf_layout ? 1 : nlat) + 1) * bc * 8 < (1LL << 31), "Fourier rows too large for the 32-bit gather offsets");
+    g_addz = z;
+    g_affine = affine;
+    const int rc = mk_irfft_ex(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xf_layout, stream);
+    g_addz = nullptr;
+    g_affine = nullptr;
     return rc;
 }

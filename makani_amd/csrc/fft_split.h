@@ -261,12 +261,25 @@ __global__ __launch_bounds__(STHREADS) void rfft_split_kernel(const TIn* __restr
 template <typename T> struct OutVec;
 template <> struct OutVec<float> {
     static constexpr int E = 4;
+    static __device__ __forceinline__ void load(const float* p, float (&o)[4]) {
+        const float4 v = *reinterpret_cast<const float4*>(p);
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
     static __device__ __forceinline__ void store(float* p, const float (&o)[4]) {
         *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]);
     }
 };
 template <> struct OutVec<__hip_bfloat16> {
     static constexpr int E = 8;
+    static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&o)[8]) {
+        const uint4 u = *reinterpret_cast<const uint4*>(p);
+        const unsigned int w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            o[2 * i] = __uint_as_float(w[i] << 16);
+            o[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+        }
+    }
     static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&o)[8]) {
         __hip_bfloat16 h[8];
 #pragma unroll
@@ -280,11 +293,15 @@ template <> struct OutVec<__hip_bfloat16> {
 // PERSIST = 1: workgroups walk the tiles with the next tile's mode gather in flight under the current tile's passes (32 prefetch
 // registers: 167 VGPRs, two workgroups per CU).  PERSIST = 0: one tile per workgroup, nothing prefetched, the pass twiddles loaded
 // after the merge step -- registers for five waves per SIMD, i.e. three workgroups per CU covering each other like the forward kernel.
-template <int S, typename TOut, bool WIDE, int PERSIST, bool SUMS = false>
+// ADD (mk_irfft_affine_add): the copy-out adds a companion field of the output's layout under a per-row affine map,
+// x = irfft(xf) + affine[row][0] * addz + affine[row][1] -- the apply pass of an instance norm and a skip add in the store
+// epilogue, for one 16-byte companion read per 16-byte store.
+template <int S, typename TOut, bool WIDE, int PERSIST, bool SUMS = false, bool ADD = false>
 __global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(const float2* __restrict__ xf, TOut* __restrict__ x,
                                                                const float2* __restrict__ tw, int BC, int K, int M,
                                                                float scale0, float scale_m, float scale_h, XfLayout xl,
-                                                               double* __restrict__ rowsums) {
+                                                               double* __restrict__ rowsums, const TOut* __restrict__ addz,
+                                                               const float* __restrict__ affine) {
     constexpr int N = 480 * S, G = SNSUB / S, HH = N / 2;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     float* red = reinterpret_cast<float*>(lds + SLDS_F2);      // [24 sub-rows][sum, sum of squares] (rowsums only)
@@ -443,7 +460,16 @@ __global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(
                     r[sq][2 * h + 1] = -z.y;
                 }
             }
-            TOut* dst = x + ((size_t)(bc0 + g) * K + k) * N + (size_t)p * EO * S;
+            const size_t doff = ((size_t)(bc0 + g) * K + k) * N + (size_t)p * EO * S;
+            TOut* dst = x + doff;
+            float za[S][EO];
+            float ca = 0.f, cb = 0.f;
+            if constexpr (ADD) {
+                ca = affine[2 * (bc0 + g)];
+                cb = affine[2 * (bc0 + g) + 1];
+#pragma unroll
+                for (int c = 0; c < S; ++c) OutVec<TOut>::load(addz + doff + c * EO, za[c]);
+            }
 #pragma unroll
             for (int c = 0; c < S; ++c) {
                 float o[EO];
@@ -451,6 +477,7 @@ __global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(
                 for (int e = 0; e < EO; ++e) {
                     const int f = c * EO + e;      // real index S*EO*p + f = S*n + s
                     o[e] = r[f % S][f / S];
+                    if constexpr (ADD) o[e] += fmaf(za[c][e], ca, cb);
                 }
                 OutVec<TOut>::store(dst + c * EO, o);
             }
@@ -504,9 +531,14 @@ int launch_irfft_split(const float* xf, void* x, int x_dtype, const float* tw, i
     const bool wide = ((long long)SH * g_xl.sm + 1) * bcx * 8 >= (1LL << 31);
 #define MK_IRFFT_LAUNCH(T, W, PS, SM)                                                                                  \
     hipLaunchKernelGGL((irfft_split_kernel<S, T, W, PS, SM>), grid, dim3(STHREADS), lds, st, (const float2*)xf, (T*)x,    \
-                       (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl, g_rowsums)
+                       (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl, g_rowsums, (const T*)nullptr, (const float*)nullptr)
 #define MK_IRFFT_PICK(T)                                                                                               \
-    if (g_rowsums) {                                                                                                   \
+    if (g_addz) {                                                                                                      \
+        if (wide) return -1;                                                                                           \
+        hipLaunchKernelGGL((irfft_split_kernel<S, T, false, 0, false, true>), grid, dim3(STHREADS), lds, st,           \
+                           (const float2*)xf, (T*)x, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl, nullptr,     \
+                           (const T*)g_addz, g_affine);                                                                \
+    } else if (g_rowsums) {                                                                                                   \
         if (wide) MK_IRFFT_LAUNCH(T, true, 1, true); else MK_IRFFT_LAUNCH(T, false, 0, true);                          \
     } else {                                                                                                           \
         if (wide) MK_IRFFT_LAUNCH(T, true, 1, false); else MK_IRFFT_LAUNCH(T, false, 0, false);                        \

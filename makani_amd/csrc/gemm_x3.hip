@@ -378,7 +378,8 @@ __device__ __forceinline__ void x3_mfma_step(const char* As, const char* Bs, con
 // loop is unrolled DB times so ring slots are compile-time); the A operand (L2-resident panels) one ahead.
 // EPI: 0 = store (nontemporal), 1 = C += tile (read-modify-write by the one workgroup that owns the tile), 2 = atomic adds
 // (several workgroups contract disjoint k ranges into one tile), 3 = store act(tile + bias[row]) with `rowbias` pointing at the
-// tile's first row (null: no bias) and `act` != 0 the exact (erf) GELU: conv + bias + activation of layers.py:158-206 in one launch
+// tile's first row (null: no bias) and `act` != 0 the exact (erf) GELU: conv + bias + activation of layers.py:158-206 in one launch,
+// 4 = store complex rows: tile rows (2r, 2r + 1) are (re, im) of complex row r (the spectral channel mix)
 template <int DB, class AS, class BS, int EPI = 0>
 __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int kt1, int rvalid, int cvalid, float* cbase,
                                         long long ldc, char* lds, int exp = 0, const float* rowbias = nullptr, int act = 0) {
@@ -449,6 +450,29 @@ __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int
     }
     // C/D map: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     const int col = wc * 64 + 2 * fi;
+    if constexpr (EPI == 4) {
+        // tile rows 2r, 2r + 1 are the real and imaginary part of complex row r (SpecRowStager): registers (r, r + 1) of a lane
+        // are (re, im) of one output, the two column parities two adjacent channels -> one 16-byte store per register pair,
+        // 512 contiguous bytes per wave.  cbase / ldc address the complex rows ([row][channel][2] floats), cvalid is even.
+        if (col < cvalid) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const int row = wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
+                    if (row < rvalid) {
+                        typedef float x3_f4 __attribute__((ext_vector_type(4)));
+                        x3_f4 v4;
+                        v4[0] = acc[a][0][r];
+                        v4[1] = acc[a][0][r + 1];
+                        v4[2] = acc[a][1][r];
+                        v4[3] = acc[a][1][r + 1];
+                        __builtin_nontemporal_store(v4, reinterpret_cast<x3_f4*>(cbase + (long long)(row >> 1) * ldc + 2 * col));
+                    }
+                }
+        }
+        return;
+    }
     if (col < cvalid) {
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -828,6 +852,246 @@ extern "C" int mk_dhconv_wgrad_x3(const float* x, const float* gy, float* gw, in
     const long long nblk = grid_blocks(lloc, p.tiles_m, p.tiles_n);
     MK_REQUIRE(nblk < 2147483647LL, "grid too large");
     hipLaunchKernelGGL(dhconv_wgrad_x3_kernel, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Real, degree-independent channel mix on the private spectrum: y[l][m][b][o] = sum_i W[o][i] x[l][m][b][i], W fp32 [O][I].
+// A 1x1 convolution without bias commutes with the (channel-blind, linear) spherical harmonic transform, so a convolution
+// next to a transform is evaluated here, on ~18x fewer values than on the grid.  Rows (m <= l, b) per degree as in dhconv;
+// entries with l < m are neither read nor written.  The real and the imaginary part of a coefficient are two rows of the
+// A image that meet the same W fragment (contraction length I, not the 2I of a block-diagonal complex form), and come out
+// of the MFMA as adjacent registers of one lane (EPI 4).
+// ---------------------------------------------------------------------------
+namespace {
+
+struct MixParams {
+    const float* a;   // x (fwd), gy (dgrad, wgrad)
+    const float* w;   // W (fwd, dgrad) or x (wgrad)
+    float* dst;
+    int Lloc, Mloc, B, Ca, Cd;   // channels of `a`; channels of dst (fwd, dgrad) or of the second field (wgrad)
+    int l_off, m_off, tiles_m, tiles_n;
+    int G, ngroups;   // wgrad: degrees per workgroup, number of such groups
+};
+
+__device__ __forceinline__ int mix_rows(int Mloc, int B, int l_off, int m_off, int l) {
+    int nm = l_off + l - m_off + 1;  // local modes with global m <= global l
+    nm = nm < 0 ? 0 : (nm > Mloc ? Mloc : nm);
+    return nm * B;
+}
+
+// Complex rows as the A operand: complex row r (64 per tile), channel i contiguous as (re, im) pairs at base[(r * C + i) * 2];
+// image row 2r = real parts, 2r + 1 = imaginary parts, contraction index k = i.  One (row, 8 channels) task per thread:
+// 64 contiguous bytes of global memory, two 16-byte vectors per piece into LDS.
+struct SpecRowStager {
+    const float* base;
+    long long ld;       // floats per complex row (2 C)
+    int rows, cvalid;   // complex rows of the tile, channels (even)
+    typedef float4 Regs[4];
+    static __device__ __forceinline__ int row_off(int r) { return pair_off(r); }
+    __device__ __forceinline__ void gload(int kt, Regs& r, int tid) const {
+        const __amdgpu_buffer_rsrc_t rs = x3_rsrc(base);
+        const int row = (tid >> 6) * 16 + quad_row(tid & 63), i = kt * XK + (tid & 3) * 8;
+        const unsigned off = (unsigned)(((long long)row * ld + 2 * i) * 4);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) r[h] = x3_load16(rs, (row < rows && i + 2 * h < cvalid) ? off + 16 * h : X3_OOB);
+    }
+    __device__ __forceinline__ void sstore(const Regs& r, char* img, int tid) const {
+        const int row = (tid >> 6) * 16 + quad_row(tid & 63), c = tid & 3;
+        const float re[8] = {r[0].x, r[0].z, r[1].x, r[1].z, r[2].x, r[2].z, r[3].x, r[3].z};
+        const float im[8] = {r[0].y, r[0].w, r[1].y, r[1].w, r[2].y, r[2].w, r[3].y, r[3].w};
+        if (row < rows) {
+            split_store8(re, img + row * XPITCH + c * 16);
+            split_store8(im, img + (row + 64) * XPITCH + 128 + c * 16);
+        }
+    }
+};
+
+// Row-major real operand with even (not necessarily multiple-of-4) row length: RowStager on 8-byte loads, rows in the pair
+// layout (it is the B operand here: a fragment reads rows 2j + b).
+struct Row2Stager {
+    const float* base;
+    long long ld;
+    int rows, kvalid;
+    typedef float2 Regs[8];
+    static __device__ __forceinline__ int row_off(int r) { return pair_off(r); }
+    __device__ __forceinline__ void gload(int kt, Regs& r, int tid) const {
+        const __amdgpu_buffer_rsrc_t rs = x3_rsrc(base);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int t = tid + q * XT, row = (t >> 6) * 16 + quad_row(t & 63), k = kt * XK + (t & 3) * 8;
+            const unsigned off = (unsigned)(((long long)row * ld + k) * 4);
+#pragma unroll
+            for (int h = 0; h < 4; ++h)
+                r[4 * q + h] = x3_load8(rs, (row < rows && k + 2 * h < kvalid) ? off + 8 * h : X3_OOB);
+        }
+    }
+    __device__ __forceinline__ void sstore(const Regs& r, char* img, int tid) const {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int t = tid + q * XT, row = (t >> 6) * 16 + quad_row(t & 63);
+            const float v[8] = {r[4 * q].x, r[4 * q].y, r[4 * q + 1].x, r[4 * q + 1].y,
+                                r[4 * q + 2].x, r[4 * q + 2].y, r[4 * q + 3].x, r[4 * q + 3].y};
+            if (row < rows) split_store8(v, img + pair_off(row) + (t & 3) * 16);
+        }
+    }
+};
+
+// Weight-gradient operand: image row c = channel, contraction index k = (complex row, re / im) over the valid rows of SEVERAL
+// degrees: k-step kt of the workgroup is rows [16 j, 16 j + 16) of degree l0 + kt / KPL, j = kt % KPL, with KPL the k-steps of
+// the group's last (longest) degree; rows past a degree's own count read as zero (no load is issued for them).
+template <bool PAIR>
+struct MixKStager {
+    const float* base;    // field + first channel of the tile
+    long long C;          // channels (complex row pitch)
+    long long lpitch;     // floats per degree
+    int l0, KPL, cvalid;
+    int Mloc, B, l_off, m_off;
+    typedef float2 Regs[8];
+    static __device__ __forceinline__ int row_off(int r) { return PAIR ? pair_off(r) : plain_off(r); }
+    __device__ __forceinline__ void gload(int kt, Regs& r, int tid) const {
+        const int w = __builtin_amdgcn_readfirstlane(tid >> 6), t = tid & 63;
+        const int li = kt / KPL, l = l0 + li;
+        const int r0 = (kt - li * KPL) * (XK / 2) + w * 4;
+        const int R = mix_rows(Mloc, B, l_off, m_off, l);
+        const __amdgpu_buffer_rsrc_t rs = x3_rsrc(base + (long long)l * lpitch);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int c = t + 64 * e;
+            const bool cok = c < cvalid;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                r[4 * e + j] = x3_load8(rs, (cok && r0 + j < R) ? (unsigned)((((long long)(r0 + j)) * C + c) * 8) : X3_OOB);
+        }
+    }
+    __device__ __forceinline__ void sstore(const Regs& r, char* img, int tid) const {
+        const int w = tid >> 6, t = tid & 63;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float v[8] = {r[4 * e].x, r[4 * e].y, r[4 * e + 1].x, r[4 * e + 1].y,
+                                r[4 * e + 2].x, r[4 * e + 2].y, r[4 * e + 3].x, r[4 * e + 3].y};
+            split_store8(v, img + row_off(t + 64 * e) + w * 16);
+        }
+    }
+};
+
+// TRANS = false: y = x W^T (forward, W [Cd][Ca]);  TRANS = true: gx = gy W (data gradient, W [Ca][Cd])
+template <bool TRANS>
+__global__ __launch_bounds__(XT, 3) void spec_mix_x3_kernel(MixParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.Lloc, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int l = p.Lloc - 1 - t.batch;  // heaviest degrees first
+    const int R = mix_rows(p.Mloc, p.B, p.l_off, p.m_off, l);
+    const int r0 = t.tm * (XM / 2);
+    if (r0 >= R) return;
+    const int n0 = t.tn * XN;
+    const long long rowbase = (long long)l * p.Mloc * p.B + r0;
+    SpecRowStager as;
+    as.base = p.a + rowbase * 2 * p.Ca;
+    as.ld = 2LL * p.Ca;
+    as.rows = R - r0;
+    as.cvalid = p.Ca;
+    float* cb = p.dst + rowbase * 2 * p.Cd + 2 * n0;
+    const int kts = (p.Ca + XK - 1) / XK;
+    if constexpr (TRANS) {
+        TransStager bs;
+        bs.base = p.w + n0;
+        bs.ldk = p.Cd;
+        bs.k_lo = 0;
+        bs.k_hi = p.Ca;
+        bs.cvalid = p.Cd - n0;
+        x3_tile<X3_DB, SpecRowStager, TransStager, 4>(as, bs, 0, kts, 2 * (R - r0), p.Cd - n0, cb, 2LL * p.Cd, lds_x3);
+    } else {
+        Row2Stager bs;
+        bs.base = p.w + (long long)n0 * p.Ca;
+        bs.ld = p.Ca;
+        bs.rows = p.Cd - n0;
+        bs.kvalid = p.Ca;
+        x3_tile<X3_DB, SpecRowStager, Row2Stager, 4>(as, bs, 0, kts, 2 * (R - r0), p.Cd - n0, cb, 2LL * p.Cd, lds_x3);
+    }
+}
+
+// gW[o][i] += sum over the valid rows of the group's degrees of re(gy[.][o] conj(x[.][i])); a = gy (Ca = O), w = x (Cd = I)
+__global__ __launch_bounds__(XT, 3) void spec_mix_wgrad_x3_kernel(MixParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.ngroups, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int g = p.ngroups - 1 - t.batch;
+    const int l0 = g * p.G, l1 = l0 + p.G < p.Lloc ? l0 + p.G : p.Lloc;
+    const int KPL = (mix_rows(p.Mloc, p.B, p.l_off, p.m_off, l1 - 1) + XK / 2 - 1) / (XK / 2);
+    if (KPL == 0) return;
+    const int o0 = t.tm * XM, i0 = t.tn * XN;
+    MixKStager<false> as;
+    as.base = p.a + 2 * o0;
+    as.C = p.Ca;
+    as.lpitch = 2LL * p.Mloc * p.B * p.Ca;
+    as.cvalid = p.Ca - o0;
+    MixKStager<true> bs;
+    bs.base = p.w + 2 * i0;
+    bs.C = p.Cd;
+    bs.lpitch = 2LL * p.Mloc * p.B * p.Cd;
+    bs.cvalid = p.Cd - i0;
+    as.l0 = bs.l0 = l0;
+    as.KPL = bs.KPL = KPL;
+    as.Mloc = bs.Mloc = p.Mloc;
+    as.B = bs.B = p.B;
+    as.l_off = bs.l_off = p.l_off;
+    as.m_off = bs.m_off = p.m_off;
+    x3_tile<X3_DB, MixKStager<false>, MixKStager<true>, 2>(as, bs, 0, (l1 - l0) * KPL, p.Ca - o0, p.Cd - i0,
+                                                            p.dst + (long long)o0 * p.Cd + i0, p.Cd, lds_x3);
+}
+
+}  // namespace
+
+static int spec_mix_check(const void* a, const void* b, const void* c, int lloc, int mloc, int batch, int cin, int cout, int l_off,
+                          int m_off) {
+    MK_REQUIRE(a && b && c, "null pointer");
+    MK_REQUIRE(lloc > 0 && mloc > 0 && batch > 0 && cin > 0 && cout > 0, "bad sizes");
+    MK_REQUIRE(l_off >= 0 && m_off >= 0, "negative shard offset");
+    MK_REQUIRE(cin % 2 == 0 && cout % 2 == 0, "the spectral channel mix needs even channel counts");
+    MK_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "operands must be 16-byte aligned");
+    const long long cmax = cin > cout ? cin : cout;
+    MK_REQUIRE((long long)mloc * batch * cmax * 8 < (1LL << 31) && 33LL * cmax * 4 < (1LL << 31),
+               "one degree of the spectrum must stay below 2^31 bytes");
+    return 0;
+}
+
+static int spec_mix_launch(bool trans, const float* a, const float* w, float* dst, int lloc, int mloc, int batch, int ca, int cd,
+                           int l_off, int m_off, void* stream) {
+    MixParams p{a, w, dst, lloc, mloc, batch, ca, cd, l_off, m_off, mk::ceil_div(mloc * batch, XM / 2), mk::ceil_div(cd, XN), 1, 0};
+    const long long nblk = grid_blocks(lloc, p.tiles_m, p.tiles_n);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    if (trans) hipLaunchKernelGGL(spec_mix_x3_kernel<true>, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(spec_mix_x3_kernel<false>, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mk_spec_mix_fwd(const float* x, const float* w, float* y, int lloc, int mloc, int batch, int cin, int cout,
+                               int l_off, int m_off, void* stream) {
+    if (int e = spec_mix_check(x, w, y, lloc, mloc, batch, cin, cout, l_off, m_off)) return e;
+    return spec_mix_launch(false, x, w, y, lloc, mloc, batch, cin, cout, l_off, m_off, stream);
+}
+
+extern "C" int mk_spec_mix_dgrad(const float* gy, const float* w, float* gx, int lloc, int mloc, int batch, int cin, int cout,
+                                 int l_off, int m_off, void* stream) {
+    if (int e = spec_mix_check(gy, w, gx, lloc, mloc, batch, cin, cout, l_off, m_off)) return e;
+    return spec_mix_launch(true, gy, w, gx, lloc, mloc, batch, cout, cin, l_off, m_off, stream);
+}
+
+extern "C" int mk_spec_mix_wgrad(const float* x, const float* gy, float* gw, int lloc, int mloc, int batch, int cin, int cout,
+                                 int l_off, int m_off, void* stream) {
+    if (int e = spec_mix_check(x, gy, gw, lloc, mloc, batch, cin, cout, l_off, m_off)) return e;
+    MixParams p{gy, x, gw, lloc, mloc, batch, cout, cin, l_off, m_off, mk::ceil_div(cout, XM), mk::ceil_div(cin, XN), 1, 0};
+    // about three workgroups per CU: a workgroup contracts G consecutive degrees into its tile before the atomic epilogue
+    long long G = (long long)lloc * p.tiles_m * p.tiles_n / 768;
+    p.G = (int)(G < 1 ? 1 : (G > 8 ? 8 : G));
+    p.ngroups = mk::ceil_div(lloc, p.G);
+    const long long nblk = grid_blocks(p.ngroups, p.tiles_m, p.tiles_n);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    hipLaunchKernelGGL(spec_mix_wgrad_x3_kernel, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
     return 0;
 }

@@ -166,6 +166,30 @@ __global__ __launch_bounds__(kT) void bias_gelu_bwd_kernel(const T* __restrict__
     }
 }
 
+// ------------------------------------------------------------------ skip add with the norm's apply pass
+// y = r + a * z + b per row, (a, b) = affine[row] (mk_instnorm_coeffs): the tail of an SFNO block whose skip convolution ran
+// in the spectral domain -- r is the synthesised skip, z the MLP output in front of norm1.
+template <typename T>
+__global__ __launch_bounds__(kT) void affine_add_kernel(const T* __restrict__ r, const T* __restrict__ z,
+                                                        const float* __restrict__ affine, T* __restrict__ y, long long P) {
+    const int row = blockIdx.y;
+    const float a = affine[2 * row], b = affine[2 * row + 1];
+    const long long ro = (long long)row * P;
+    for_chunk<T>(P, [&](long long off, int n) {
+        float v[kE], u[kE];
+        if (n == kE) {
+            IO<T>::load(r + ro + off, v);
+            IO<T>::load(z + ro + off, u);
+#pragma unroll
+            for (int i = 0; i < kE; ++i) v[i] += fmaf(u[i], a, b);
+            IO<T>::store(y + ro + off, v);
+        } else {
+            for (int i = 0; i < n; ++i)
+                IO<T>::st1(y + ro + off + i, IO<T>::ld1(r + ro + off + i) + fmaf(IO<T>::ld1(z + ro + off + i), a, b));
+        }
+    });
+}
+
 // ------------------------------------------------------------------ instance norm
 // pass 1: per-row sums (sum x, sum x^2) accumulated in double across workgroups
 template <typename T>
@@ -366,6 +390,22 @@ extern "C" int mk_bias_gelu_bwd(const void* x, const float* bias, const void* gy
     else
         hipLaunchKernelGGL(bias_gelu_bwd_kernel<__hip_bfloat16>, pw_grid(rows, P), dim3(kT), 0, st,
                            (const __hip_bfloat16*)x, bias, (const __hip_bfloat16*)gy, (__hip_bfloat16*)gx, gbias, C, P);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mk_affine_add(const void* r, const void* z, const float* affine, void* y, int dtype, int rows, long long P,
+                             void* stream) {
+    MK_REQUIRE(r && z && affine && y, "null pointer");
+    const int C = 1;
+    PW_CHECK();
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 0)
+        hipLaunchKernelGGL(affine_add_kernel<float>, pw_grid(rows, P), dim3(kT), 0, st, (const float*)r, (const float*)z, affine,
+                           (float*)y, P);
+    else
+        hipLaunchKernelGGL(affine_add_kernel<__hip_bfloat16>, pw_grid(rows, P), dim3(kT), 0, st, (const __hip_bfloat16*)r,
+                           (const __hip_bfloat16*)z, affine, (__hip_bfloat16*)y, P);
     MK_LAUNCH_CHECK();
     return 0;
 }

@@ -234,6 +234,177 @@ def conv_plus_instance_norm(conv, x, z, sums, norm):
     return y.view(B, conv.out_channels, H, W)
 
 
+class _NormSkipAdd(torch.autograd.Function):
+    """out = r + instance_norm(z): the tail of an SFNO block whose outer skip convolution ran in the spectral domain
+    (``ops.spec_mix`` in front of the synthesis that produced ``r``).  The statistics come with ``z`` as in
+    ``_PceConvNormAdd``; one streaming pass (``mk_affine_add``) applies ``a * z + b`` and adds the skip.  Backward: the
+    gradient of ``r`` is the incoming gradient itself, the norm's comes from ``z`` and the saved (mean, rstd)."""
+
+    @staticmethod
+    def forward(ctx, r4, z4, sums, nw, nb, eps, group, count):
+        from . import ops
+        B, C, H, W = z4.shape
+        if group is not None:
+            torch.distributed.all_reduce(sums, group=group)
+        cnt = H * W if group is None else int(count)
+        wf = None if nw is None else nw.detach().float().contiguous()
+        bf = None if nb is None else nb.detach().float().contiguous()
+        stats, affine = ops.instance_norm_coeffs(sums, wf, bf, B * C, C, cnt, eps)
+        y = ops.affine_add(r4, z4, affine)
+        empty = z4.new_empty(0, dtype=torch.float32)
+        ctx.save_for_backward(z4, stats, wf if wf is not None else empty, bf if bf is not None else empty)
+        ctx.cfg = (None if nw is None else nw.dtype, None if nb is None else nb.dtype, group, cnt)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import ops
+        z4, stats, wf, bf = ctx.saved_tensors
+        nw_dtype, nb_dtype, group, cnt = ctx.cfg
+        gy = gy.contiguous()
+        gz, gnw, gnb = ops.instance_norm_backward(z4, gy, stats, wf if nw_dtype is not None else None,
+                                                  bf if nb_dtype is not None else None, False, group, cnt,
+                                                  grad_dtype=nw_dtype if (nw_dtype is not None and nw_dtype == nb_dtype) else None)
+        return (gy, gz, None, gnw.to(nw_dtype) if nw_dtype is not None else None,
+                gnb.to(nb_dtype) if nb_dtype is not None else None, None, None, None)
+
+
+class _NormSkipAddFFT(torch.autograd.Function):
+    """``_NormSkipAdd`` with the add folded into the inverse FFT that synthesises the skip (``mk_irfft_affine_add``):
+    out = irfft(xf) + instance_norm(z); the synthesised skip is never written.  Backward: the adjoint FFT of the incoming
+    gradient for ``xf`` (as ``ops._IRFFT``), the norm's gradients from ``z`` and the saved (mean, rstd).  Unsharded rows only."""
+
+    @staticmethod
+    def forward(ctx, xf, twiddles, nlon, kmajor, z4, sums, nw, nb, eps):
+        from . import ops
+        B, C, H, W = z4.shape
+        wf = None if nw is None else nw.detach().float().contiguous()
+        bf = None if nb is None else nb.detach().float().contiguous()
+        stats, affine = ops.instance_norm_coeffs(sums, wf, bf, B * C, C, H * W, eps)
+        y = ops.irfft_affine_add_raw(xf, twiddles, nlon, z4, affine, kmajor)
+        empty = z4.new_empty(0, dtype=torch.float32)
+        ctx.save_for_backward(z4, stats, wf if wf is not None else empty, bf if bf is not None else empty, twiddles)
+        ctx.cfg = (None if nw is None else nw.dtype, None if nb is None else nb.dtype, xf.shape[1] if kmajor else xf.shape[0],
+                   bool(kmajor))
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import ops
+        z4, stats, wf, bf, tw = ctx.saved_tensors
+        nw_dtype, nb_dtype, mmax, kmajor = ctx.cfg
+        B, C, H, W = z4.shape
+        gy = gy.contiguous()
+        gxf = ops.rfft_raw(gy.view(B * C, H, W), tw, mmax, 1.0, 2.0, 1.0, kmajor) if ctx.needs_input_grad[0] else None
+        gz, gnw, gnb = ops.instance_norm_backward(z4, gy, stats, wf if nw_dtype is not None else None,
+                                                  bf if nb_dtype is not None else None, False, None, H * W,
+                                                  grad_dtype=nw_dtype if (nw_dtype is not None and nw_dtype == nb_dtype) else None)
+        return (gxf, None, None, None, gz, None, gnw.to(nw_dtype) if nw_dtype is not None else None,
+                gnb.to(nb_dtype) if nb_dtype is not None else None, None)
+
+
+def spectral_skip_supported(conv, z_like):
+    """The outer skip ``conv`` may run on the spectrum: a bias-free ``Conv1x1`` the channel mix takes, in a step on the bf16
+    engine (the conditions ``conv_plus_instance_norm`` checks before it sees the MLP output)."""
+    from . import ops
+    if not isinstance(conv, Conv1x1) or conv.bias is not None or not ops.spec_mix_supported(conv.in_channels, conv.out_channels):
+        return False
+    if os.environ.get("MK_NORM_SKIP_FUSION", "1") == "0" or os.environ.get("MK_CONV_ENGINE", "pce") != "pce":
+        return False
+    if not (z_like.is_cuda and z_like.dim() == 4):
+        return False
+    return z_like.dtype == torch.bfloat16 or (z_like.dtype == torch.float32 and torch.is_autocast_enabled()
+                                              and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+
+def spectral_skip_plus_instance_norm(conv, filt, spec, z, sums, norm):
+    """``isht(conv.weight . spec) + norm(z)``: the skip convolution as a channel mix of the block's input spectrum ``spec``
+    (``filt``: the block's ``SpectralConv``, whose inverse transform synthesises it), the norm's apply pass and the add in one
+    streaming pass -- or None where ``conv_plus_instance_norm`` would decline too (the caller then synthesises the residual)."""
+    from . import comm, ops
+    from .layer_norm import DistributedInstanceNorm2d
+    if sums is None or z.dtype != torch.bfloat16 or not z.is_contiguous() or z.dim() != 4 or not ops.pointwise_supported(z):
+        return None
+    group = count = None
+    if isinstance(norm, DistributedInstanceNorm2d):
+        if comm.get_size("spatial") > 1:
+            group, count = comm.get_group("spatial"), norm._global_count(z)
+        nw, nb = (norm.weight, norm.bias) if norm.affine else (None, None)
+    elif isinstance(norm, InstanceNorm2d) and not norm.track_running_stats:
+        nw, nb = norm.weight, norm.bias
+    else:
+        return None
+    B, C, H, W = z.shape
+    if C != conv.out_channels or (H, W) != (filt.nlat_local, filt.nlon_local):
+        return None
+    from .sht import InverseRealSHT
+    it = filt.inverse_transform
+    with torch.autocast("cuda", enabled=False):
+        cm = ops.spec_mix(spec, conv.weight, B, filt.l_off, filt.m_off)
+        if group is None and type(it) is InverseRealSHT and ops.irfft_affine_add_supported(it.nlon, it.mmax):
+            # the synthesis' inverse FFT applies the norm and adds z while it stores: no residual field, no separate pass
+            km = ops.SPECTRAL_GEMM == "bf16x3"
+            xf = ops.legendre_inv(cm, it.pct, it.nlat, 0, km)
+            return _NormSkipAddFFT.apply(xf, it.twiddles, it.nlon, km, z, sums, nw, nb, norm.eps)
+        r = filt.synthesise(cm, B, z.dtype)
+        return _NormSkipAdd.apply(r.view(B, C, H, W), z, sums, nw, nb, norm.eps, group, count)
+
+
+class _PceConvGelu(torch.autograd.Function):
+    """h = gelu(W @ x + bias) on bf16 ``[B, C, P]`` fields: an encoder in front of its last convolution when that convolution
+    runs in the spectral domain (``ops.spec_mix`` behind the analysis).  Forward: one engine launch that also keeps the
+    pre-activation.  Backward: ``gpre = gh * gelu'(pre)`` with the bias gradient as its row sums in one streaming pass
+    (``mk_bias_gelu_bwd``), the weight gradient from the wgrad kernel, the data gradient (if anyone asks) from the engine."""
+
+    @staticmethod
+    def forward(ctx, x3, w, bias, keep_pre):
+        from . import ops
+        if keep_pre:
+            h, pre = ops.pce_gemm(x3, ops.pce_pack(w), w.shape[0], bias=bias, want_pre=True, gelu=True)
+        else:
+            h, pre = ops.pce_gemm(x3, ops.pce_pack(w), w.shape[0], bias=bias, gelu=True), x3.new_empty(0)
+        ctx.save_for_backward(x3, w, pre)
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.step = _step_items(w)
+        return h
+
+    @staticmethod
+    def backward(ctx, gh):
+        from . import ops
+        x3, w, pre = ctx.saved_tensors
+        (wimg_t, gbuf), ctx.step = (ctx.step or (None, None)), None
+        need_gb = ctx.bias_dtype is not None and ctx.needs_input_grad[2]
+        gpre, gsum = ops.gelu_backward(pre, gh.contiguous(), need_gb)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.pce_gemm(gpre, wimg_t if wimg_t is not None else ops.pce_pack(w, transpose=True), w.shape[1])
+        if ctx.needs_input_grad[1]:
+            gw = ops.conv1x1_wgrad_raw(gpre, x3, out=gbuf).to(w.dtype)
+        if need_gb:
+            gb = gsum.to(ctx.bias_dtype)
+        return gx, gw, gb, None
+
+
+def encoder_head(encoder, x):
+    """``(h, last)`` with ``h`` the field in front of the encoder's last convolution ``last`` -- for a caller that evaluates
+    that convolution behind a spherical harmonic analysis (``ops.spec_mix``) -- or None where the pattern is not the one the
+    engine takes in one launch: ``[Conv1x1, exact GELU, no-ops..., bias-free Conv1x1]`` on a bf16 (or autocast-to-bf16) field."""
+    from . import ops
+    mods = list(encoder.fwd)
+    pat = _mlp_pattern(mods)
+    if pat is None or x.dim() != 4:
+        return None
+    fc1, fc2 = pat
+    if fc2.bias is not None or not ops.spec_mix_supported(fc2.in_channels, fc2.out_channels):
+        return None
+    x3 = _engine_field(x)
+    if x3 is None or not ops.pce_supported_train(fc1.out_channels, fc1.in_channels):
+        return None
+    with torch.autocast("cuda", enabled=False):
+        h = _PceConvGelu.apply(x3, fc1.weight2d(), fc1.bias, torch.is_grad_enabled())
+    return h.view(x.shape[0], fc1.out_channels, x.shape[2], x.shape[3]), fc2
+
+
 class _PceMLP(torch.autograd.Function):
     """y = W2 @ gelu(W1 @ x + b1) (+ b2): the MLP / encoder / decoder of ``layers.py:86-216`` on bf16 ``[B, C, P]``
     fields.  Forward: two engine launches, bias + GELU in the epilogue of the first (which also keeps the

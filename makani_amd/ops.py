@@ -119,6 +119,31 @@ def irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor=False, chans=0, cpp=0):
     return x, sums
 
 
+def irfft_affine_add_supported(nlon, mmax):
+    """The inverse FFT can add ``a * z + b`` per row in its store epilogue (``mk_irfft_affine_add``: the split kernels);
+    ``MK_IRFFT_AFFINE_ADD=0`` keeps the separate streaming pass (``affine_add``) -- the A/B switch of the variant."""
+    return nlon in (480, 1440) and mmax <= 241 and os.environ.get("MK_FFT_LEGACY", "0") != "1" \
+        and os.environ.get("MK_IRFFT_AFFINE_ADD", "1") != "0"
+
+
+def irfft_affine_add_raw(xf, twiddles, nlon, z, affine, kmajor=False):
+    """``irfft(xf) + a * z + b`` per row: ``xf`` as for ``irfft_raw`` (scales 1, 1, 1), ``z`` a contiguous field of ``BC`` rows
+    ``[K, nlon]`` (fp32 / bf16, the dtype of the result), ``affine`` fp32 ``[BC, 2]`` = (a, b) (``instance_norm_coeffs``)."""
+    _need_cuda(xf, twiddles, z, affine)
+    assert xf.dim() == 3 and xf.is_contiguous() and xf.dtype == torch.complex64
+    if kmajor:
+        k, m, bc = xf.shape
+    else:
+        m, k, bc = xf.shape
+    assert z.is_contiguous() and z.numel() == bc * k * nlon and z.dtype in (torch.float32, torch.bfloat16)
+    assert affine.dtype == torch.float32 and affine.is_contiguous() and affine.numel() == 2 * bc
+    x = torch.empty_like(z)
+    _lib.check(_lib.load().mk_irfft_affine_add(xf.data_ptr(), x.data_ptr(), _pw_dtype(z), twiddles.data_ptr(), bc, k, nlon, m,
+                                               1.0, 1.0, 1.0, int(bool(kmajor)), z.data_ptr(), affine.data_ptr(), _stream()),
+               "mk_irfft_affine_add")
+    return x
+
+
 def irfft_raw(xf, twiddles, nlon, s0, sm, sh, out_dtype=torch.float32, kmajor=False):
     """xf complex64 [M, K, BC] ([K, M, BC] with ``kmajor``) -> x [BC, K, nlon] in fp32, or bf16 where the kernel
     fuses the cast."""
@@ -830,6 +855,80 @@ class _Dhconv(torch.autograd.Function):
         return gx, gw, None, None, None
 
 
+def spec_mix_supported(cin, cout):
+    """The spectral channel mix runs on the bf16x3 engine only (even channel counts); ``MK_SPEC_MIX=0`` switches its call
+    sites back to the convolutions on the grid."""
+    return (os.environ.get("MK_SPEC_MIX", "1") != "0" and _gemm_mode(None) == "bf16x3" and cin % 2 == 0 and cout % 2 == 0)
+
+
+def _spec_mix_args(x, batch):
+    _need_cuda(x)
+    assert x.dim() == 3 and x.is_contiguous() and x.dtype == torch.complex64 and x.shape[2] % batch == 0
+    return x.shape[0], x.shape[1], x.shape[2] // batch
+
+
+def spec_mix_fwd_raw(x, w, batch, l_off=0, m_off=0):
+    """y[l, m, b, o] = sum_i w[o, i] x[l, m, b, i] on the private spectrum ``[L, M, B * I]``; ``w`` fp32 ``[O, I]``."""
+    lloc, mloc, cin = _spec_mix_args(x, batch)
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 2 and w.shape[1] == cin
+    cout = w.shape[0]
+    y = torch.empty(lloc, mloc, batch * cout, dtype=torch.complex64, device=x.device)
+    _lib.check(_lib.load().mk_spec_mix_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), lloc, mloc, batch, cin, cout, l_off, m_off,
+                                           _stream()), "mk_spec_mix_fwd")
+    return y
+
+
+def spec_mix_dgrad_raw(gy, w, batch, l_off=0, m_off=0):
+    """gx[l, m, b, i] = sum_o w[o, i] gy[l, m, b, o]."""
+    lloc, mloc, cout = _spec_mix_args(gy, batch)
+    assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 2 and w.shape[0] == cout
+    cin = w.shape[1]
+    gx = torch.empty(lloc, mloc, batch * cin, dtype=torch.complex64, device=gy.device)
+    _lib.check(_lib.load().mk_spec_mix_dgrad(gy.data_ptr(), w.data_ptr(), gx.data_ptr(), lloc, mloc, batch, cin, cout, l_off,
+                                             m_off, _stream()), "mk_spec_mix_dgrad")
+    return gx
+
+
+def spec_mix_wgrad_raw(x, gy, batch, l_off=0, m_off=0):
+    """gw[o, i] = sum over the valid (l, m, b) of re(gy[l, m, b, o] conj(x[l, m, b, i])) -> fp32 ``[O, I]``."""
+    lloc, mloc, cin = _spec_mix_args(x, batch)
+    l2, m2, cout = _spec_mix_args(gy, batch)
+    assert (l2, m2) == (lloc, mloc)
+    gw = torch.zeros(cout, cin, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().mk_spec_mix_wgrad(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), lloc, mloc, batch, cin, cout, l_off,
+                                             m_off, _stream()), "mk_spec_mix_wgrad")
+    return gw
+
+
+class _SpecMix(torch.autograd.Function):
+    """A bias-free 1x1 convolution moved across a spherical harmonic transform: the real ``[O, I]`` weight mixes the
+    channels of every coefficient of the private spectrum (``mk_spec_mix_*``).  Saves the input spectrum and the weight."""
+
+    @staticmethod
+    def forward(ctx, x, w, batch, l_off, m_off):
+        wf = w.detach().float().contiguous()
+        ctx.save_for_backward(x, wf)
+        ctx.args = (batch, l_off, m_off, w.dtype, tuple(w.shape))
+        return spec_mix_fwd_raw(x, wf.view(wf.shape[0], -1), batch, l_off, m_off)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, wf = ctx.saved_tensors
+        batch, l_off, m_off, wdt, wshape = ctx.args
+        gy = gy.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = spec_mix_dgrad_raw(gy, wf.view(wf.shape[0], -1), batch, l_off, m_off)
+        if ctx.needs_input_grad[1]:
+            gw = spec_mix_wgrad_raw(x, gy, batch, l_off, m_off).view(wshape).to(wdt)
+        return gx, gw, None, None, None
+
+
+def spec_mix(x, w, batch, l_off=0, m_off=0):
+    """``w``: the convolution's weight, ``[O, I]`` or ``[O, I, 1, 1]`` (the fp32 master, used as it is)."""
+    return _SpecMix.apply(x, w, batch, l_off, m_off)
+
+
 def rfft(x, twiddles, mmax, kmajor=False):
     return _RFFT.apply(x, twiddles, mmax, kmajor)
 
@@ -1065,6 +1164,32 @@ def row_sums(t3):
 
 def bias_gelu(x, bias):
     return _BiasGelu.apply(x, bias)
+
+
+def gelu_backward(pre, gy, want_row_sums=False):
+    """``gy * gelu'(pre)`` on contiguous ``[B, C, P]`` fp32 / bf16 fields (``pre`` holds the bias already), and, with
+    ``want_row_sums``, its sum over (batch, pixels) as fp32 ``[C]`` -- the bias gradient (``mk_bias_gelu_bwd``)."""
+    _need_cuda(pre, gy)
+    assert pre.dim() == 3 and pre.is_contiguous() and gy.is_contiguous() and gy.shape == pre.shape and gy.dtype == pre.dtype
+    b, c, p = pre.shape
+    gx = torch.empty_like(pre)
+    gsum = torch.zeros(c, dtype=torch.float32, device=pre.device) if want_row_sums else None
+    _lib.check(_lib.load().mk_bias_gelu_bwd(pre.data_ptr(), 0, gy.data_ptr(), gx.data_ptr(), 0 if gsum is None else gsum.data_ptr(),
+                                            _pw_dtype(pre), b * c, c, p, _stream()), "mk_bias_gelu_bwd")
+    return gx, gsum
+
+
+def affine_add(r, z, affine):
+    """``r + a * z + b`` per row of two contiguous ``[B, C, H, W]`` fields of one dtype (fp32 / bf16), ``affine`` fp32
+    ``[B * C, 2]`` = (a, b) from ``instance_norm_coeffs`` (``mk_affine_add``)."""
+    _need_cuda(r, z, affine)
+    assert r.is_contiguous() and z.is_contiguous() and r.shape == z.shape and r.dtype == z.dtype and z.dim() == 4
+    B, C, H, W = z.shape
+    assert affine.dtype == torch.float32 and affine.is_contiguous() and affine.numel() == 2 * B * C
+    y = torch.empty_like(z)
+    _lib.check(_lib.load().mk_affine_add(r.data_ptr(), z.data_ptr(), affine.data_ptr(), y.data_ptr(), _pw_dtype(z), B * C, H * W,
+                                         _stream()), "mk_affine_add")
+    return y
 
 
 def instance_norm(x, weight, bias, eps=1e-5, fuse_gelu=False, group=None, count=None, row_sums=None):

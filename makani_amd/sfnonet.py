@@ -28,7 +28,8 @@ from . import comm
 from .distributed import DistributedInverseRealFFT2, DistributedInverseRealSHT, DistributedRealFFT2, DistributedRealSHT
 from .layer_norm import DistributedInstanceNorm2d, DistributedLayerNorm
 from .layers import (Conv1x1, DropPath, EncoderDecoder, InstanceNorm2d, InverseRealFFT2, MLP, RealFFT2, _engine_field,
-                     _is_exact_gelu, conv_plus_instance_norm)
+                     _is_exact_gelu, _is_noop, conv_plus_instance_norm, encoder_head, spectral_skip_plus_instance_norm,
+                     spectral_skip_supported)
 from .sht import InverseRealSHT, RealSHT
 from .spectral_convolution import FactorizedSpectralConv, SpectralAttention, SpectralConv
 
@@ -74,11 +75,19 @@ class SpectralFilterLayer(nn.Module):
             self.filter = FactorizedSpectralConv(forward_transform, inverse_transform, embed_dim, embed_dim, rank=rank,
                                                  factorization=factorization, **common)
 
-    def forward(self, x, want_row_sums=False):
+    def forward(self, x, want_row_sums=False, **spectral):
+        """``spectral``: ``premix`` / ``spectrum_residual`` of ``SpectralConv.forward``, for a filter that ``takes_spectral_mix()``."""
+        spectral = {k: v for k, v in spectral.items() if v}
+        if spectral:
+            out = self.filter(x, want_row_sums=want_row_sums, **spectral)
+            return out
         if want_row_sums and isinstance(self.filter, SpectralConv) and type(self.filter).forward is SpectralConv.forward:
             return self.filter(x, want_row_sums=True)
         out = self.filter(x)
         return (out[0], out[1], None) if want_row_sums else out
+
+    def takes_spectral_mix(self):
+        return isinstance(self.filter, SpectralConv) and self.filter.takes_spectral_mix()
 
 
 class FourierNeuralOperatorBlock(nn.Module):
@@ -124,13 +133,33 @@ class FourierNeuralOperatorBlock(nn.Module):
         return (isinstance(norm, (nn.InstanceNorm2d, DistributedInstanceNorm2d))
                 and not getattr(norm, "track_running_stats", False))
 
-    def forward(self, x):
+    def _spectral_outer_skip(self, x):
+        """The outer skip convolution may run as a channel mix of the block's input spectrum: its input is a synthesis of that
+        spectrum onto a LARGER grid (on a smaller one the convolution on the grid is the cheaper side) and the block's tail is
+        the one ``conv_plus_instance_norm`` fuses."""
+        outer = getattr(self, "outer_skip", None)
+        return (outer is not None and hasattr(self, "mlp") and not hasattr(self, "inner_skip")
+                and isinstance(self.filter, SpectralFilterLayer) and self.filter.takes_spectral_mix()
+                and self.filter.filter.scale_residual
+                and self.output_shape_loc[0] * self.output_shape_loc[1] > self.input_shape_loc[0] * self.input_shape_loc[1]
+                and isinstance(self.norm1, (InstanceNorm2d, DistributedInstanceNorm2d))
+                and isinstance(self.drop_path, nn.Identity) and not hasattr(self, "act_layer1")
+                and getattr(self.mlp, "checkpointing", 0) < 2 and spectral_skip_supported(outer, x))
+
+    def forward(self, x, premix=None):
+        """``premix``: a bias-free ``Conv1x1`` the caller left out in front of the block (the encoder's last); the filter applies
+        it to the spectrum.  Only for a block whose filter ``takes_spectral_mix()`` and whose residual is a scaled one."""
         inner = getattr(self, "inner_skip", None)
         hip_norm0 = isinstance(self.norm0, (InstanceNorm2d, DistributedInstanceNorm2d)) \
             and not getattr(self.norm0, "track_running_stats", False)
         sums0 = None
+        batch, in_dtype = x.shape[0], x.dtype
+        spec_skip = self._spectral_outer_skip(x)
         if hip_norm0 and isinstance(self.filter, SpectralFilterLayer):
-            x, residual, sums0 = self.filter(x, want_row_sums=True)   # norm0's statistics come out of the inverse FFT
+            # norm0's statistics come out of the inverse FFT
+            x, residual, sums0 = self.filter(x, want_row_sums=True, premix=premix, spectrum_residual=spec_skip)
+        elif premix is not None or spec_skip:
+            x, residual = self.filter(x, premix=premix, spectrum_residual=spec_skip)
         else:
             x, residual = self.filter(x)
         if inner is None and hip_norm0 and _is_exact_gelu(self.act_layer0):
@@ -153,6 +182,12 @@ class FourierNeuralOperatorBlock(nn.Module):
             else:
                 x = self.mlp(x, skip_last_bias=self._removes_channel_constants(self.norm1))
         outer = getattr(self, "outer_skip", None)
+        if spec_skip:
+            # outer skip in the spectral domain: isht(W c) instead of W isht(c), then norm1's apply pass and the add in one pass
+            y = spectral_skip_plus_instance_norm(outer, self.filter.filter, residual, x, sums, self.norm1)
+            if y is not None:
+                return y
+            residual = self.filter.filter.residual_from_spectrum(residual, batch, in_dtype)
         if sums is not None and isinstance(self.drop_path, nn.Identity) and not hasattr(self, "act_layer1"):
             # norm1 + outer skip: the norm's apply pass rides in the epilogue of the skip convolution
             y = conv_plus_instance_norm(outer, residual, x, sums, self.norm1)
@@ -301,11 +336,25 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
         with torch.autocast(device_type=x.device.type, enabled=False):     # resample the input to the output grid
             return self.itrans_up(self.trans_down(x.float()).contiguous()).to(x.dtype)
 
-    def _forward_features(self, x):
+    def _forward_features(self, x, premix=None):
         for _ in range(self.repeat_layers):
-            for blk in self.blocks:
-                x = checkpoint(blk, x, use_reentrant=False) if self.checkpointing >= 3 else blk(x)
+            for i, blk in enumerate(self.blocks):
+                if i == 0 and premix is not None:
+                    x = blk(x, premix=premix)
+                else:
+                    x = checkpoint(blk, x, use_reentrant=False) if self.checkpointing >= 3 else blk(x)
         return x
+
+    def _spectral_encoder(self, x):
+        """``(h, conv)`` when the encoder's last convolution can run behind block 0's analysis instead of in front of it
+        (``sht(W x) = W sht(x)``): its output has no other consumer (no position embedding, no dropout, block 0's residual is
+        synthesised from the spectrum, the big skip takes the raw input) -- else None."""
+        blk = self.blocks[0] if len(self.blocks) else None
+        if (blk is None or hasattr(self, "pos_embed") or not _is_noop(self.pos_drop) or self.checkpointing != 0
+                or self.repeat_layers != 1 or not blk.filter.takes_spectral_mix() or not blk.filter.filter.scale_residual
+                or hasattr(blk, "inner_skip")):
+            return None
+        return encoder_head(self.encoder, x)
 
     def _engine_arena(self, x):
         """The per-step arena of the pointwise stack (``ops.EngineArena``) when this call runs on the bf16 engine, else None."""
@@ -340,10 +389,14 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
             if x3 is not None and x3.dtype != x.dtype:
                 x = x3.view(x.shape)
         skip_in = self._big_skip_input(x) if self.big_skip else None
-        x = checkpoint(self.encoder, x, use_reentrant=False) if self.checkpointing >= 1 else self.encoder(x)
-        if hasattr(self, "pos_embed"):
-            x = x + self._position_field(x)
-        x = self._forward_features(self.pos_drop(x))
+        head = self._spectral_encoder(x)
+        if head is not None:
+            x = self._forward_features(head[0], premix=head[1])       # the encoder's last convolution rides on block 0's spectrum
+        else:
+            x = checkpoint(self.encoder, x, use_reentrant=False) if self.checkpointing >= 1 else self.encoder(x)
+            if hasattr(self, "pos_embed"):
+                x = x + self._position_field(x)
+            x = self._forward_features(self.pos_drop(x))
         x = checkpoint(self.decoder, x, use_reentrant=False) if self.checkpointing >= 1 else self.decoder(x)
         if skip_in is not None:
             x = self.residual_transform(skip_in, addend=x)     # big skip folded into the GEMM epilogue

@@ -114,7 +114,23 @@ class SpectralConv(nn.Module):
     def _weight_tensor(self):
         return self.weight
 
-    def _forward_fused(self, x, dtype, want_row_sums=False):
+    def synthesise(self, c, B, odt):
+        """Private spectrum ``[L, M, B * C]`` -> ``[B * C, nlat, nlon]`` rows in ``odt`` through the inverse transform."""
+        it = self.inverse_transform
+        return it.inverse_packed(c, B, odt) if self._distributed else it.inverse_packed(c, odt)
+
+    def residual_from_spectrum(self, c, B, dtype):
+        """The scaled residual of ``forward`` from the spectrum it handed out instead (``spectrum_residual``)."""
+        with torch.autocast(device_type="cuda", enabled=False):
+            r = self.synthesise(c, B, dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32)
+        return r.view(B, -1, r.shape[-2], r.shape[-1]).to(dtype)
+
+    def takes_spectral_mix(self):
+        """A bias-free 1x1 convolution next to one of this layer's transforms can be handed over as a channel mix of the
+        spectrum (``premix`` / ``spectrum_residual``): the plain class on its fused path only."""
+        return type(self) is SpectralConv and self._fused
+
+    def _forward_fused(self, x, dtype, want_row_sums=False, premix=None, spectrum_residual=False):
         B, C = x.shape[0], x.shape[1]
         ft, it = self.forward_transform, self.inverse_transform
         xin = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
@@ -123,11 +139,17 @@ class SpectralConv(nn.Module):
             c = ft.forward_packed(xin)
         else:
             c = ft.forward_packed(xin.view(B * C, xin.shape[2], xin.shape[3]))
+        if premix is not None:
+            # the bias-free convolution in front of this layer commutes with the analysis: sht(W x) = W sht(x)
+            c = ops.spec_mix(c, premix.weight, B, self.l_off, self.m_off)
+            C = premix.out_channels
         # the inverse FFT writes its rows directly in the layer's activation dtype (fp32, or bf16 under AMP)
         odt = dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32
         residual = x
-        if self.scale_residual:
-            r = it.inverse_packed(c, B, odt) if self._distributed else it.inverse_packed(c, odt)
+        if self.scale_residual and spectrum_residual:
+            residual = c        # the caller mixes the channels of the spectrum before it synthesises the residual
+        elif self.scale_residual:
+            r = self.synthesise(c, B, odt)
             residual = r.view(B, C, r.shape[-2], r.shape[-1]).to(dtype)
         y = ops.dhconv(c, self._weight_tensor(), B, self.l_off, self.m_off)
         sums = None
@@ -138,15 +160,21 @@ class SpectralConv(nn.Module):
         out = out.view(B, self.out_channels, out.shape[-2], out.shape[-1])
         return out, residual, sums
 
-    def forward(self, x, want_row_sums=False):
+    def forward(self, x, want_row_sums=False, premix=None, spectrum_residual=False):
         """``want_row_sums`` (this package's blocks only): a third result, the fp64 ``[B*C, 2]`` sums / sums of squares of the rows
-        of the filtered field for the instance norm behind the filter, or None where the path cannot deliver them."""
+        of the filtered field for the instance norm behind the filter, or None where the path cannot deliver them.
+        ``premix``: a bias-free ``Conv1x1`` the caller left out in front of this layer; it is applied to the spectrum
+        (``ops.spec_mix``).  ``spectrum_residual``: where the residual is a synthesis of the input spectrum, return the
+        private spectrum in its place (see ``residual_from_spectrum``).  Both only where ``takes_spectral_mix()``."""
         dtype = x.dtype
         residual = x
         sums = None
+        if premix is not None or spectrum_residual:
+            assert self.takes_spectral_mix() and x.is_cuda and x.dim() == 4 and (premix is None or self.scale_residual)
         if self._fused and x.is_cuda and x.dim() == 4:
             with torch.autocast(device_type="cuda", enabled=False):
-                x, residual, sums = self._forward_fused(x, dtype, want_row_sums and not hasattr(self, "bias"))
+                x, residual, sums = self._forward_fused(x, dtype, want_row_sums and not hasattr(self, "bias"), premix,
+                                                        spectrum_residual)
             if sums is not None and x.dtype != dtype:
                 sums = None                         # a cast behind the kernel: the statistics are those of other values
         else:
