@@ -439,6 +439,18 @@ long long mk_history_workspace(int B, int Cn, int H);
 int mk_history_sums(const void* x, int x_dtype, const float* u, const float* wt, double* workspace, double* sums, int B, int T,
                     int C, int Cu, int H, int W, void* stream);
 
+/* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
+ * per-time scalars: fp32, all on the device,
+ *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],
+ *   out [n][H][W] = sin_lat[i] sin dec + (cos_lat[i] cos dec) cos((GMST + lon_rad[j]) - ra)
+ * with every product and sum rounded on its own in that order (the file is compiled with fp contraction off: a
+ * v_mul and a v_add per point, no fma outside cosf itself) and the accurate cosf, which is the arithmetic of
+ * makani/third_party/climt/zenith_angle.py.  A point depends on its (time, row, column) only: a launch on slices of the
+ * tables gives the slice of the full field bit for bit.  Any W, any element-aligned out; n == 0 launches nothing.  Writes
+ * only; no atomics, allocation, synchronisation or host copy. */
+int mk_cos_zenith(const float* eph, const float* sin_lat, const float* cos_lat, const float* lon_rad, float* out, long long n,
+                  int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

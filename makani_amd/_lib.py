@@ -111,6 +111,7 @@ SIGNATURES = {
     "mk_input_assemble_bwd": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_c_int] * 7 + [_vp]),
     "mk_history_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "mk_history_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_vp]),
+    "mk_cos_zenith": (_c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _c_int, _c_int, _vp]),
 }
 
 

@@ -1416,3 +1416,38 @@ def input_assemble(x, u=None, stat=None, mean=None, std=None, mask_chans=None, m
 
     return _InputAssemble.apply(x.contiguous(), f32(u), f32(stat), f32(mean), f32(std),
                                 mask_chans.contiguous() if mask_chans is not None else None, int(mask_src), out_dtype)
+
+
+# ----------------------------------------------------------------------------
+# cosine of the solar zenith angle (csrc/zenith.hip)
+# ----------------------------------------------------------------------------
+@torch.no_grad()
+def cos_zenith(eph, sin_lat, cos_lat, lon_rad, out=None):
+    """The zenith channel ``[..., H, W]`` fp32 from ``eph`` ``[..., 4]`` = (sin dec, cos dec, GMST, right ascension) per
+    time and the grid's tables ``sin_lat``, ``cos_lat`` ``[H]`` and ``lon_rad`` ``[W]``:
+    ``sin_lat sin dec + (cos_lat cos dec) cos((GMST + lon_rad) - ra)``, every product and sum an fp32 rounding of its
+    own (the kernel is compiled with fp contraction off) (``mk_cos_zenith``; see ``makani_amd/zenith.py`` for the scalars and the tables).  One store-only HIP pass on the
+    current stream; slices of the tables give the slice of the field bit for bit.  ``out``, if given, is a contiguous
+    fp32 tensor of that many elements on the same device at any element-aligned address.  CUDA only, no gradient."""
+    _need_cuda(eph, sin_lat, cos_lat, lon_rad, *([out] if out is not None else []))
+    if eph.dim() < 1 or eph.shape[-1] != 4:
+        raise ValueError(f"cos_zenith: eph {tuple(eph.shape)} must be [..., 4]")
+    if sin_lat.dim() != 1 or cos_lat.shape != sin_lat.shape or lon_rad.dim() != 1:
+        raise ValueError(f"cos_zenith: tables {tuple(sin_lat.shape)}, {tuple(cos_lat.shape)}, {tuple(lon_rad.shape)} must be [H], [H], [W]")
+    H, W = sin_lat.shape[0], lon_rad.shape[0]
+    n = eph.numel() // 4
+    if out is None:
+        out = torch.empty(*eph.shape[:-1], H, W, dtype=torch.float32, device=eph.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * H * W or out.device != eph.device:
+        raise ValueError(f"cos_zenith: out must be a contiguous fp32 tensor of {n} x {H} x {W} elements on {eph.device}")
+    for t in (sin_lat, cos_lat, lon_rad):
+        if t.device != eph.device:
+            raise ValueError(f"cos_zenith: tables on {t.device}, eph on {eph.device}")
+
+    def f32(t):
+        return t.detach().float().contiguous()
+
+    eph, sin_lat, cos_lat, lon_rad = f32(eph), f32(sin_lat), f32(cos_lat), f32(lon_rad)
+    _lib.check(_lib.load().mk_cos_zenith(eph.data_ptr(), sin_lat.data_ptr(), cos_lat.data_ptr(), lon_rad.data_ptr(),
+                                         out.data_ptr(), n, H, W, _stream()), "mk_cos_zenith")
+    return out

@@ -3,7 +3,9 @@
 Constructor, buffers (``static_features`` and ``history_normalization_weights``, both non-persistent), method names and
 results of ``makani/models/preprocessor.py`` (``Preprocessor2D``, ``get_preprocessor``).  ``params`` is the trainer's
 parameter object (attribute access).  The methods of the reference are views, small copies or calls the trainer makes
-outside the model and stay torch ops.
+outside the model and stay torch ops.  ``cache_unpredicted_times`` is an addition: it fills the unpredicted channel
+with the cosine of the solar zenith angle computed on the device from sample times (``zenith.py``), where the reference
+takes fields from its data loader.
 
 The hot path is one method the reference does not have, ``assemble(inp, out_dtype=None)``: what both wrappers do before
 every model call,
@@ -45,6 +47,8 @@ Where the reference (a fork with local edits) cannot be followed literally, the 
 * ``netCDF4`` / ``h5py`` readers: a path ending in ``.npy`` is read with numpy, any other path imports the reference's
   reader library lazily and raises a clear ``ImportError`` if it is absent.
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 from torch import nn
@@ -123,6 +127,11 @@ class Preprocessor2D(nn.Module):
         self.unpredicted_tar_train = None
         self.unpredicted_inp_eval = None
         self.unpredicted_tar_eval = None
+        # the grid of this rank's shard, kept (the constructor keeps no params) for cache_unpredicted_times, which alone
+        # builds anything from it
+        self._zenith_grid = SimpleNamespace(**{k: getattr(params, k) for k in (
+            "lat", "lon", "img_shape_x", "img_shape_y", "img_local_offset_x", "img_local_offset_y", "img_local_shape_x",
+            "img_local_shape_y") if hasattr(params, k)})
 
         # static features, sliced to this rank's shard
         static_features = None
@@ -329,6 +338,39 @@ class Preprocessor2D(nn.Module):
             else:
                 setattr(self, name, z)
         return x, y
+
+    def cache_unpredicted_times(self, inp_times, tar_times=None, exact=False, device=None):
+        """``cache_unpredicted_features`` fed with sample times in place of fields: the unpredicted channel is the cosine
+        of the solar zenith angle (``zenith.CosZenith`` on this rank's shard of ``params.lat`` / ``params.lon``, or of
+        the loaders' default grid), evaluated on the device.
+
+        ``inp_times`` ``[B, n_history + 1]`` and ``tar_times`` ``[B, n_future + 1]`` (``[T]`` means one sample) hold
+        tz-aware datetimes or ``numpy.datetime64``, as ``zenith.sample_times`` returns them; ``exact`` is
+        ``zenith.solar_ephemeris``'s.  Either may instead be a ready ``[B, T, 4]`` tensor of ephemeris scalars on the
+        device: nothing is uploaded then, so inside a captured graph the call re-evaluates the channel from whatever the
+        tensor holds at replay.  The device is that of the tensors already cached, else of a tensor argument, else
+        ``device``, else of the static features.  The fields go through ``cache_unpredicted_features`` (copied into the
+        cached tensors if there are any), which ``append_history`` then rolls as usual."""
+        from . import zenith
+        uinp, utar = self._unpredicted()
+        if device is None:
+            known = [t for t in (uinp, utar, inp_times, tar_times, getattr(self, "static_features", None)) if torch.is_tensor(t)]
+            device = known[0].device if known else torch.device("cpu")
+        device = torch.empty(0, device=device).device               # with its index: "cuda" and "cuda:0" are one key
+        built = self.__dict__.setdefault("_cos_zenith", {})         # device -> CosZenith, made here only
+        if device not in built:
+            built[device] = zenith.CosZenith.from_params(self._zenith_grid).to(device)
+        cosz = built[device]
+
+        def field(times):
+            if times is None:
+                return None
+            if not torch.is_tensor(times):
+                eph = np.atleast_2d(zenith.solar_ephemeris(times, exact=exact))
+                times = torch.from_numpy(eph[None] if eph.ndim == 2 else eph)
+            return cosz(times.to(device))
+
+        return self.cache_unpredicted_features(None, None, field(inp_times), field(tar_times))
 
     def append_unpredicted_features(self, inp):
         uinp, _ = self._unpredicted()
