@@ -32,10 +32,12 @@ struct XfLayout {
     int C, Cp, Bn;        // Cp = 0: plain layouts
     long long pstride;    // K * M * Bn * Cp
 };
-static thread_local XfLayout g_xl = {0, 0, 0, 0, 0, 0};   // set by the C entry points before they launch
-static thread_local const void* g_addz = nullptr;         // mk_irfft_affine_add: companion field and its per-row (a, b)
-static thread_local const float* g_affine = nullptr;
-static thread_local double* g_rowsums = nullptr;          // mk_irfft_sums: per-row (sum, sum of squares) accumulators of the output
+// What only the inverse transform takes besides its layout; at most one of the two is set.
+struct IrfftExtras {
+    double* rowsums = nullptr;        // mk_irfft_sums: per-row (sum, sum of squares) accumulators of the output
+    const void* addz = nullptr;       // mk_irfft_affine_add: companion field and its per-row (a, b)
+    const float* affine = nullptr;
+};
 
 // per-tile channel addressing: all G rows of a split-kernel tile lie in one (batch item, channel block) when Cp % G == 0
 struct XfChan {
@@ -459,64 +461,77 @@ __global__ __launch_bounds__(kThreads) void irdft_generic_kernel(const float2* _
 }
 
 template <int H, int G>
-int launch_rfft(const void* x, int x_dtype, float* xf, const float* tw, int bc, int nlat, int mmax, float s0,
-                float sm, float sh, hipStream_t st) {
+void launch_rfft(const void* x, int x_dtype, float* xf, const float* tw, int bc, int nlat, int mmax, float s0, float sm,
+                 float sh, const XfLayout& xl, hipStream_t st) {
     const int ntile = mk::ceil_div(bc, G);
     const dim3 grid((unsigned)(ntile * nlat));
     const size_t lds = sizeof(float2) * G * (H + 1);
     if (x_dtype == 0)
         hipLaunchKernelGGL((rfft_kernel<H, G, float>), grid, dim3(kThreads), lds, st, (const float*)x, (float2*)xf,
-                           (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl);
+                           (const float2*)tw, bc, nlat, mmax, s0, sm, sh, xl);
     else
         hipLaunchKernelGGL((rfft_kernel<H, G, __hip_bfloat16>), grid, dim3(kThreads), lds, st,
-                           (const __hip_bfloat16*)x, (float2*)xf, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl);
-    return 0;
+                           (const __hip_bfloat16*)x, (float2*)xf, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, xl);
 }
 
 template <int H, int G>
-int launch_irfft(const float* xf, float* x, const float* tw, int bc, int nlat, int mmax, float s0, float sm,
-                 float sh, hipStream_t st) {
+void launch_irfft(const float* xf, float* x, const float* tw, int bc, int nlat, int mmax, float s0, float sm, float sh,
+                  const XfLayout& xl, hipStream_t st) {
     const int ntile = mk::ceil_div(bc, G);
     const dim3 grid((unsigned)(ntile * nlat));
     const size_t lds = sizeof(float2) * G * (H + 1);
     hipLaunchKernelGGL((irfft_kernel<H, G>), grid, dim3(kThreads), lds, st, (const float2*)xf, x, (const float2*)tw,
-                       bc, nlat, mmax, s0, sm, sh, g_xl);
-    return 0;
+                       bc, nlat, mmax, s0, sm, sh, xl);
 }
 
 #include "fft_split.h"
-
-}  // namespace
 
 #define MK_FFT_SIZES(X) \
     X(8, 16) X(16, 16) X(32, 16) X(45, 16) X(48, 16) X(64, 16) X(90, 16) X(120, 16) X(128, 16) X(180, 16) \
     X(240, 16) X(256, 16) X(360, 8) X(720, 8)
 
-extern "C" int mk_rfft(const void* x, int x_dtype, float* xf, const float* twiddles, int bc, int nlat, int nlon,
-                       int mmax, float scale0, float scale_m, float scale_h, void* stream) {
-    return mk_rfft_ex(x, x_dtype, xf, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, 0, stream);
+// The layouts of the C ABI.  Every entry point builds its XfLayout (and IrfftExtras) from its own arguments and hands them
+// down by reference, through fft_analysis / fft_synthesis into the launcher and by value into the kernel: nothing about a
+// call is kept anywhere once it returns.
+int xf_plain(int xf_layout, int nlat, int mmax, XfLayout& xl) {
+    MK_REQUIRE(xf_layout == 0 || xf_layout == 1, "xf_layout must be 0 ([M][K][BC]) or 1 ([K][M][BC])");
+    xl = xf_layout ? XfLayout{1, mmax, 0, 0, 0, 0} : XfLayout{nlat, 1, 0, 0, 0, 0};
+    return 0;
 }
 
-extern "C" int mk_rfft_ex(const void* x, int x_dtype, float* xf, const float* twiddles, int bc, int nlat, int nlon,
-                          int mmax, float scale0, float scale_m, float scale_h, int xf_layout, void* stream) {
-    MK_REQUIRE(xf_layout == 0 || xf_layout == 1, "xf_layout must be 0 ([M][K][BC]) or 1 ([K][M][BC])");
-    g_xl = xf_layout ? XfLayout{1, mmax, 0, 0, 0, 0} : XfLayout{nlat, 1, 0, 0, 0, 0};
-    MK_REQUIRE(x && xf && twiddles, "null pointer");
+// Peer-major Fourier rows (see XfLayout): bc = batch * chans rows, channel blocks of chans_per_peer.
+int xf_peer_major(int bc, int nlat, int nlon, int mmax, int chans, int chans_per_peer, XfLayout& xl) {
+    MK_REQUIRE(chans > 0 && chans_per_peer > 0 && bc % chans == 0 && chans % chans_per_peer == 0, "bad channel blocking");
+    MK_REQUIRE(chans_per_peer % 24 == 0, "channel blocks must be multiples of 24 (tiles of 8 / 24 rows must not straddle them)");
+    MK_REQUIRE(fft_split_applies(nlon, mmax), "peer-major rows exist for the split kernels only");
+    const int Bn = bc / chans;
+    xl = XfLayout{1, mmax, chans, chans_per_peer, Bn, (long long)nlat * mmax * Bn * chans_per_peer};
+    return 0;
+}
+
+// what both directions require of their common arguments
+int fft_check(const void* x, const void* xf, const float* tw, int x_dtype, int bc, int nlat, int nlon, int mmax) {
+    MK_REQUIRE(x && xf && tw, "null pointer");
     MK_REQUIRE(bc > 0 && nlat > 0 && nlon >= 2 && nlon % 2 == 0, "bad sizes (nlon must be even)");
     MK_REQUIRE(mmax >= 1 && mmax <= nlon / 2 + 1, "mmax out of range");
     MK_REQUIRE(x_dtype == 0 || x_dtype == 1, "x_dtype must be 0 (fp32) or 1 (bf16)");
     MK_REQUIRE((long long)nlat * mk::ceil_div(bc, 8) < 2147483647LL, "grid too large");
-    hipStream_t st = (hipStream_t)stream;
-    const bool split = !fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440);
-    if (split && nlon == 480) {
-        launch_rfft_split<1>(x, x_dtype, xf, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, st);
-    } else if (split) {
-        launch_rfft_split<3>(x, x_dtype, xf, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, st);
+    return 0;
+}
+
+// Analysis x -> xf of every entry point: the common checks, then the split kernels, a planned Stockham kernel
+// (MK_FFT_SIZES) or the generic DFT.
+int fft_analysis(const void* x, int x_dtype, float* xf, const float* tw, int bc, int nlat, int nlon, int mmax, float s0,
+                 float sm, float sh, const XfLayout& xl, hipStream_t st) {
+    if (int e = fft_check(x, xf, tw, x_dtype, bc, nlat, nlon, mmax)) return e;
+    if (fft_split_applies(nlon, mmax)) {
+        if (nlon == 480) launch_rfft_split<1>(x, x_dtype, xf, tw, bc, nlat, mmax, s0, sm, sh, xl, st);
+        else launch_rfft_split<3>(x, x_dtype, xf, tw, bc, nlat, mmax, s0, sm, sh, xl, st);
     } else
     switch (nlon / 2) {
 #define X(H, G) \
     case H:     \
-        launch_rfft<H, G>(x, x_dtype, xf, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, st); \
+        launch_rfft<H, G>(x, x_dtype, xf, tw, bc, nlat, mmax, s0, sm, sh, xl, st); \
         break;
         MK_FFT_SIZES(X)
 #undef X
@@ -526,15 +541,60 @@ extern "C" int mk_rfft_ex(const void* x, int x_dtype, float* xf, const float* tw
             const size_t lds = sizeof(float) * nlon;
             if (x_dtype == 0)
                 hipLaunchKernelGGL((rdft_generic_kernel<float>), grid, dim3(kThreads), lds, st, (const float*)x,
-                                   (float2*)xf, (const float2*)twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, g_xl);
+                                   (float2*)xf, (const float2*)tw, bc, nlat, nlon, mmax, s0, sm, sh, xl);
             else
                 hipLaunchKernelGGL((rdft_generic_kernel<__hip_bfloat16>), grid, dim3(kThreads), lds, st,
-                                   (const __hip_bfloat16*)x, (float2*)xf, (const float2*)twiddles, bc, nlat, nlon,
-                                   mmax, scale0, scale_m, scale_h, g_xl);
+                                   (const __hip_bfloat16*)x, (float2*)xf, (const float2*)tw, bc, nlat, nlon, mmax, s0, sm,
+                                   sh, xl);
         }
     }
     MK_LAUNCH_CHECK();
     return 0;
+}
+
+// Synthesis xf -> x of every entry point, likewise; bf16 rows and the extras exist in the split kernels only.
+int fft_synthesis(const float* xf, void* x, int x_dtype, const float* tw, int bc, int nlat, int nlon, int mmax, float s0,
+                  float sm, float sh, const XfLayout& xl, const IrfftExtras& ex, hipStream_t st) {
+    if (int e = fft_check(x, xf, tw, x_dtype, bc, nlat, nlon, mmax)) return e;
+    const bool split = fft_split_applies(nlon, mmax);
+    MK_REQUIRE(x_dtype == 0 || split, "bf16 output rows are built for the production lengths only (nlon 480 / 1440, mmax <= 241)");
+    if (split) {
+        const bool wide = irfft_split_wide(xl, bc);
+        MK_REQUIRE(!(wide && ex.addz), "Fourier rows too large for the 32-bit gather offsets");
+        if (nlon == 480) launch_irfft_split<1>(xf, x, x_dtype, tw, bc, nlat, mmax, s0, sm, sh, xl, ex, wide, st);
+        else launch_irfft_split<3>(xf, x, x_dtype, tw, bc, nlat, mmax, s0, sm, sh, xl, ex, wide, st);
+    } else
+    switch (nlon / 2) {
+#define X(H, G) \
+    case H:     \
+        launch_irfft<H, G>(xf, (float*)x, tw, bc, nlat, mmax, s0, sm, sh, xl, st); \
+        break;
+        MK_FFT_SIZES(X)
+#undef X
+        default: {
+            MK_REQUIRE((long long)nlat * bc < 2147483647LL, "grid too large");
+            const dim3 grid((unsigned)(nlat * bc));
+            const size_t lds = sizeof(float2) * mmax;
+            hipLaunchKernelGGL(irdft_generic_kernel, grid, dim3(kThreads), lds, st, (const float2*)xf, (float*)x,
+                               (const float2*)tw, bc, nlat, nlon, mmax, s0, sm, sh, xl);
+        }
+    }
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mk_rfft(const void* x, int x_dtype, float* xf, const float* twiddles, int bc, int nlat, int nlon,
+                       int mmax, float scale0, float scale_m, float scale_h, void* stream) {
+    return mk_rfft_ex(x, x_dtype, xf, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, 0, stream);
+}
+
+extern "C" int mk_rfft_ex(const void* x, int x_dtype, float* xf, const float* twiddles, int bc, int nlat, int nlon,
+                          int mmax, float scale0, float scale_m, float scale_h, int xf_layout, void* stream) {
+    XfLayout xl;
+    if (int e = xf_plain(xf_layout, nlat, mmax, xl)) return e;
+    return fft_analysis(x, x_dtype, xf, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl, (hipStream_t)stream);
 }
 
 extern "C" int mk_irfft(const float* xf, void* xout, int x_dtype, const float* twiddles, int bc, int nlat, int nlon,
@@ -544,78 +604,23 @@ extern "C" int mk_irfft(const float* xf, void* xout, int x_dtype, const float* t
 
 extern "C" int mk_irfft_ex(const float* xf, void* xout, int x_dtype, const float* twiddles, int bc, int nlat, int nlon,
                            int mmax, float scale0, float scale_m, float scale_h, int xf_layout, void* stream) {
-    MK_REQUIRE(xf_layout == 0 || xf_layout == 1, "xf_layout must be 0 ([M][K][BC]) or 1 ([K][M][BC])");
-    g_xl = xf_layout ? XfLayout{1, mmax, 0, 0, 0, 0} : XfLayout{nlat, 1, 0, 0, 0, 0};
-    float* x = (float*)xout;
-    MK_REQUIRE(x_dtype == 0 || x_dtype == 1, "x_dtype must be 0 (fp32) or 1 (bf16)");
-    MK_REQUIRE(x_dtype == 0 || (!fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440)),
-               "bf16 output rows are built for the production lengths only (nlon 480 / 1440, mmax <= 241)");
-    MK_REQUIRE(x && xf && twiddles, "null pointer");
-    MK_REQUIRE(bc > 0 && nlat > 0 && nlon >= 2 && nlon % 2 == 0, "bad sizes (nlon must be even)");
-    MK_REQUIRE(mmax >= 1 && mmax <= nlon / 2 + 1, "mmax out of range");
-    MK_REQUIRE((long long)nlat * mk::ceil_div(bc, 8) < 2147483647LL, "grid too large");
-    hipStream_t st = (hipStream_t)stream;
-    const bool split = !fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440);
-    if (split && nlon == 480) {
-        launch_irfft_split<1>(xf, xout, x_dtype, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, st);
-    } else if (split) {
-        launch_irfft_split<3>(xf, xout, x_dtype, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, st);
-    } else
-    switch (nlon / 2) {
-#define X(H, G) \
-    case H:     \
-        launch_irfft<H, G>(xf, x, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, st); \
-        break;
-        MK_FFT_SIZES(X)
-#undef X
-        default: {
-            MK_REQUIRE((long long)nlat * bc < 2147483647LL, "grid too large");
-            const dim3 grid((unsigned)(nlat * bc));
-            const size_t lds = sizeof(float2) * mmax;
-            hipLaunchKernelGGL(irdft_generic_kernel, grid, dim3(kThreads), lds, st, (const float2*)xf, x,
-                               (const float2*)twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, g_xl);
-        }
-    }
-    MK_LAUNCH_CHECK();
-    return 0;
-}
-
-// Peer-major Fourier rows (see XfLayout): bc = batch * chans rows, channel blocks of chans_per_peer.
-static int fft_pm_setup(int bc, int nlat, int nlon, int mmax, int chans, int chans_per_peer) {
-    MK_REQUIRE(chans > 0 && chans_per_peer > 0 && bc % chans == 0 && chans % chans_per_peer == 0, "bad channel blocking");
-    MK_REQUIRE(chans_per_peer % 24 == 0, "channel blocks must be multiples of 24 (tiles of 8 / 24 rows must not straddle them)");
-    MK_REQUIRE(!fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440), "peer-major rows exist for the split kernels only");
-    const int Bn = bc / chans;
-    g_xl = XfLayout{1, mmax, chans, chans_per_peer, Bn, (long long)nlat * mmax * Bn * chans_per_peer};
-    return 0;
+    XfLayout xl;
+    if (int e = xf_plain(xf_layout, nlat, mmax, xl)) return e;
+    return fft_synthesis(xf, xout, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl, {}, (hipStream_t)stream);
 }
 
 extern "C" int mk_rfft_pm(const void* x, int x_dtype, float* xf, const float* twiddles, int bc, int nlat, int nlon, int mmax,
                           float scale0, float scale_m, float scale_h, int chans, int chans_per_peer, void* stream) {
-    MK_REQUIRE(x && xf && twiddles, "null pointer");
-    MK_REQUIRE(bc > 0 && nlat > 0 && mmax >= 1, "bad sizes");
-    MK_REQUIRE(x_dtype == 0 || x_dtype == 1, "x_dtype must be 0 (fp32) or 1 (bf16)");
-    if (int e = fft_pm_setup(bc, nlat, nlon, mmax, chans, chans_per_peer)) return e;
-    if (nlon == 480)
-        launch_rfft_split<1>(x, x_dtype, xf, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, (hipStream_t)stream);
-    else
-        launch_rfft_split<3>(x, x_dtype, xf, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, (hipStream_t)stream);
-    MK_LAUNCH_CHECK();
-    return 0;
+    XfLayout xl;
+    if (int e = xf_peer_major(bc, nlat, nlon, mmax, chans, chans_per_peer, xl)) return e;
+    return fft_analysis(x, x_dtype, xf, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl, (hipStream_t)stream);
 }
 
 extern "C" int mk_irfft_pm(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon, int mmax,
                            float scale0, float scale_m, float scale_h, int chans, int chans_per_peer, void* stream) {
-    MK_REQUIRE(x && xf && twiddles, "null pointer");
-    MK_REQUIRE(bc > 0 && nlat > 0 && mmax >= 1, "bad sizes");
-    MK_REQUIRE(x_dtype == 0 || x_dtype == 1, "x_dtype must be 0 (fp32) or 1 (bf16)");
-    if (int e = fft_pm_setup(bc, nlat, nlon, mmax, chans, chans_per_peer)) return e;
-    if (nlon == 480)
-        launch_irfft_split<1>(xf, x, x_dtype, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, (hipStream_t)stream);
-    else
-        launch_irfft_split<3>(xf, x, x_dtype, twiddles, bc, nlat, mmax, scale0, scale_m, scale_h, (hipStream_t)stream);
-    MK_LAUNCH_CHECK();
-    return 0;
+    XfLayout xl;
+    if (int e = xf_peer_major(bc, nlat, nlon, mmax, chans, chans_per_peer, xl)) return e;
+    return fft_synthesis(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl, {}, (hipStream_t)stream);
 }
 
 // Inverse transform that also delivers the statistics of its output: rowsums[2 r], rowsums[2 r + 1] += sum / sum of squares of
@@ -627,13 +632,13 @@ extern "C" int mk_irfft_sums(const float* xf, void* x, int x_dtype, const float*
                              float scale0, float scale_m, float scale_h, int xf_layout, int chans, int chans_per_peer,
                              double* rowsums, void* stream) {
     MK_REQUIRE(rowsums != nullptr, "null pointer");
-    MK_REQUIRE(!fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440), "row statistics come from the split kernels only");
-    g_rowsums = rowsums;
-    const int rc = chans_per_peer > 0
-        ? mk_irfft_pm(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, chans, chans_per_peer, stream)
-        : mk_irfft_ex(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xf_layout, stream);
-    g_rowsums = nullptr;
-    return rc;
+    MK_REQUIRE(fft_split_applies(nlon, mmax), "row statistics come from the split kernels only");
+    XfLayout xl;
+    if (int e = chans_per_peer > 0 ? xf_peer_major(bc, nlat, nlon, mmax, chans, chans_per_peer, xl)
+                                   : xf_plain(xf_layout, nlat, mmax, xl))
+        return e;
+    return fft_synthesis(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl, {.rowsums = rowsums},
+                         (hipStream_t)stream);
 }
 
 // Inverse transform whose store epilogue adds a companion field under a per-row affine map:
@@ -644,14 +649,10 @@ extern "C" int mk_irfft_affine_add(const float* xf, void* x, int x_dtype, const 
                                    int mmax, float scale0, float scale_m, float scale_h, int xf_layout, const void* z,
                                    const float* affine, void* stream) {
     MK_REQUIRE(z != nullptr && affine != nullptr, "null pointer");
-    MK_REQUIRE(!fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440), "the affine-add epilogue exists in the split kernels only");
+    MK_REQUIRE(fft_split_applies(nlon, mmax), "the affine-add epilogue exists in the split kernels only");
     MK_REQUIRE((((uintptr_t)z | (uintptr_t)x) & 15) == 0, "fields must be 16-byte aligned");
-    MK_REQUIRE(xf_layout == 0 || xf_layout == 1, "xf_layout must be 0 ([M][K][BC]) or 1 ([K][M][BC])");
-    MK_REQUIRE((240LL * (xf_layout ? 1 : nlat) + 1) * bc * 8 < (1LL << 31), "Fourier rows too large for the 32-bit gather offsets");
-    g_addz = z;
-    g_affine = affine;
-    const int rc = mk_irfft_ex(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xf_layout, stream);
-    g_addz = nullptr;
-    g_affine = nullptr;
-    return rc;
+    XfLayout xl;
+    if (int e = xf_plain(xf_layout, nlat, mmax, xl)) return e;
+    return fft_synthesis(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl,
+                         {.addz = z, .affine = affine}, (hipStream_t)stream);
 }

@@ -288,16 +288,17 @@ template <> struct OutVec<__hip_bfloat16> {
     }
 };
 
-// WIDE: mode offsets of one tile may exceed 2^31 bytes (mode-major Fourier rows of a very large batch): 64-bit pointer
-// arithmetic per gather instead of 32-bit buffer offsets.
-// PERSIST = 1: workgroups walk the tiles with the next tile's mode gather in flight under the current tile's passes (32 prefetch
-// registers: 167 VGPRs, two workgroups per CU).  PERSIST = 0: one tile per workgroup, nothing prefetched, the pass twiddles loaded
-// after the merge step -- registers for five waves per SIMD, i.e. three workgroups per CU covering each other like the forward kernel.
+// WIDE = false, the kernel every production shape runs: one tile per workgroup, 32-bit buffer offsets in the mode gather, the pass
+// twiddles loaded after the merge step -- registers for five waves per SIMD, i.e. three workgroups per CU covering each other like
+// the forward kernel.  WIDE = true: the mode offsets of one tile may reach 2^31 bytes (mode-major Fourier rows of a very large
+// batch), so every gather does 64-bit pointer arithmetic; this variant also keeps the tile loop of the earlier persistent form
+// (the next tile's gather issued under the current tile's passes, pass twiddles loaded once, three waves per SIMD).  It is
+// launched with one workgroup per tile like the other, so the loop body runs once.
 // ADD (mk_irfft_affine_add): the copy-out adds a companion field of the output's layout under a per-row affine map,
 // x = irfft(xf) + affine[row][0] * addz + affine[row][1] -- the apply pass of an instance norm and a skip add in the store
 // epilogue, for one 16-byte companion read per 16-byte store.
-template <int S, typename TOut, bool WIDE, int PERSIST, bool SUMS = false, bool ADD = false>
-__global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(const float2* __restrict__ xf, TOut* __restrict__ x,
+template <int S, typename TOut, bool WIDE, bool SUMS = false, bool ADD = false>
+__global__ __launch_bounds__(STHREADS, WIDE ? 3 : 5) void irfft_split_kernel(const float2* __restrict__ xf, TOut* __restrict__ x,
                                                                const float2* __restrict__ tw, int BC, int K, int M,
                                                                float scale0, float scale_m, float scale_h, XfLayout xl,
                                                                double* __restrict__ rowsums, const TOut* __restrict__ addz,
@@ -309,23 +310,23 @@ __global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(
     const int ntile = (BC + G - 1) / G;
     const int total = ntile * K;
     const float2* tw2 = tw + HH;
-    // persistent: this workgroup walks the schedule indices blockIdx.x, + gridDim.x, ... (tiles via pair_tile)
+    // WIDE: this workgroup walks the schedule indices blockIdx.x, + gridDim.x, ... (tiles via pair_tile)
     const int total16 = (total + 15) & ~15;
     auto next_valid = [&](int i) {
         while (i < total16 && pair_tile(i) >= total) i += (int)gridDim.x;
         return i;
     };
-    int sched = PERSIST ? next_valid(blockIdx.x) : (int)blockIdx.x;
+    int sched = WIDE ? next_valid(blockIdx.x) : (int)blockIdx.x;
     if (sched >= total16) return;
     int tile = pair_tile(sched);
-    if (!PERSIST && tile >= total) return;
+    if (!WIDE && tile >= total) return;
 
     float2 tw15[15];
     auto load_tw15 = [&]() {
 #pragma unroll
         for (int r = 0; r < 15; ++r) tw15[r] = tw[((tid & 15) * r) * S];
     };
-    if constexpr (PERSIST != 0) load_tw15();
+    if constexpr (WIDE) load_tw15();
 
     float2 wfirst[S];        // exp(-2 pi i s' (tid / G) / N), s' = S, 1, 2: merge-step twiddles of this thread's first item
     wfirst[0] = tw2[S * (tid / G)];
@@ -423,9 +424,9 @@ __global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(
             if (jp != 0 && j1 != jp) zs[j1] = make_float2(e.x + t.y, e.y - t.x);
         }
     }
-    if constexpr (PERSIST == 0) load_tw15();      // issued before the barrier: the latency sits under the wait for the other waves
+    if constexpr (!WIDE) load_tw15();      // issued before the barrier: the latency sits under the wait for the other waves
     __syncthreads();
-    const int next = PERSIST ? next_valid(sched + (int)gridDim.x) : total16;
+    const int next = WIDE ? next_valid(sched + (int)gridDim.x) : total16;
     if (next < total16) gather(pair_tile(next), opaque(tid));
     if constexpr (SUMS) split_passes<true, TOut>(lds, tl, S, tw15, red);
     else split_passes(lds, tl, S, tw15);
@@ -492,7 +493,7 @@ __global__ __launch_bounds__(STHREADS, PERSIST ? 3 : 5) void irfft_split_kernel(
 
 // Inverse kernel: one workgroup per tile (three per CU covering each other, as in the forward kernel).  Two persistent
 // workgroups per CU with the next tile's mode gather prefetched in registers measured 15-21 % slower (0.595 vs 0.505 ms at
-// 721 x 1440, 0.094 vs 0.074 ms at 240 x 480) and were removed; PERSIST = 1 survives only as the loop of the WIDE variant.
+// 721 x 1440, 0.094 vs 0.074 ms at 240 x 480) and were removed; their tile loop survives inside the WIDE variant only.
 static inline unsigned split_grid(long long tiles) { return (unsigned)((tiles + 15) / 16 * 16); }
 
 // ablation switches for the forward kernel (MK_FFT_EXP): 1 no row loads, 2 no FFT passes, 4 no mode stores,
@@ -502,9 +503,26 @@ static inline int fft_exp() {
     return v;
 }
 
+static inline bool fft_legacy() {
+    static const bool v = [] {
+        const char* e = getenv("MK_FFT_LEGACY");
+        return e && e[0] == '1';
+    }();
+    return v;
+}
+
+// the split kernels apply: a production length, no mode above 240, not switched off (MK_FFT_LEGACY=1: planned Stockham kernels)
+static inline bool fft_split_applies(int nlon, int mmax) { return !fft_legacy() && mmax <= 241 && (nlon == 480 || nlon == 1440); }
+
+// 32-bit mode offsets inside a tile's buffer descriptor: (240 modes + one row of channels) * 8 bytes must stay below 2^31
+static inline bool irfft_split_wide(const XfLayout& xl, int bc) {
+    const long long bcx = xl.Cp ? (long long)xl.Bn * xl.Cp : (long long)bc;
+    return ((long long)SH * xl.sm + 1) * bcx * 8 >= (1LL << 31);
+}
+
 template <int S>
-int launch_rfft_split(const void* x, int x_dtype, float* xf, const float* tw, int bc, int nlat, int mmax, float s0,
-                      float sm, float sh, hipStream_t st) {
+void launch_rfft_split(const void* x, int x_dtype, float* xf, const float* tw, int bc, int nlat, int mmax, float s0,
+                       float sm, float sh, const XfLayout& xl, hipStream_t st) {
     constexpr int G = SNSUB / S;
     // one workgroup per tile, rounded up to whole XCD pair groups.  Persistence was measured twice: with a prefetch of
     // the next rows it costs 70 VGPRs; as a plain loop over tiles at 2-4 workgroups per CU it is 13-33 % slower than this
@@ -513,50 +531,33 @@ int launch_rfft_split(const void* x, int x_dtype, float* xf, const float* tw, in
     const size_t lds = sizeof(float2) * SLDS_F2;
     if (x_dtype == 0)
         hipLaunchKernelGGL((rfft_split_kernel<S, float>), grid, dim3(STHREADS), lds, st, (const float*)x, (float2*)xf,
-                           (const float2*)tw, bc, nlat, mmax, s0, sm, sh, fft_exp(), g_xl);
+                           (const float2*)tw, bc, nlat, mmax, s0, sm, sh, fft_exp(), xl);
     else
         hipLaunchKernelGGL((rfft_split_kernel<S, __hip_bfloat16>), grid, dim3(STHREADS), lds, st,
-                           (const __hip_bfloat16*)x, (float2*)xf, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, fft_exp(), g_xl);
-    return 0;
+                           (const __hip_bfloat16*)x, (float2*)xf, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, fft_exp(), xl);
 }
 
+// `wide` = irfft_split_wide(xl, bc); the affine-add epilogue exists in the narrow variant only (the caller has refused wide rows)
 template <int S>
-int launch_irfft_split(const float* xf, void* x, int x_dtype, const float* tw, int bc, int nlat, int mmax, float s0,
-                       float sm, float sh, hipStream_t st) {
+void launch_irfft_split(const float* xf, void* x, int x_dtype, const float* tw, int bc, int nlat, int mmax, float s0,
+                        float sm, float sh, const XfLayout& xl, const IrfftExtras& ex, bool wide, hipStream_t st) {
     constexpr int G = SNSUB / S;
     const dim3 grid(split_grid(mk::ceil_div(bc, G) * (long long)nlat));
     const size_t lds = sizeof(float2) * SLDS_F2 + 2 * SNSUB * sizeof(float);
-    // 32-bit mode offsets inside a tile's buffer descriptor: (240 modes + one row of channels) * 8 bytes must stay below 2^31
-    const long long bcx = g_xl.Cp ? (long long)g_xl.Bn * g_xl.Cp : (long long)bc;
-    const bool wide = ((long long)SH * g_xl.sm + 1) * bcx * 8 >= (1LL << 31);
-#define MK_IRFFT_LAUNCH(T, W, PS, SM)                                                                                  \
-    hipLaunchKernelGGL((irfft_split_kernel<S, T, W, PS, SM>), grid, dim3(STHREADS), lds, st, (const float2*)xf, (T*)x,    \
-                       (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl, g_rowsums, (const T*)nullptr, (const float*)nullptr)
+#define MK_IRFFT_LAUNCH(T, WIDE, SUMS, ADD)                                                                            \
+    hipLaunchKernelGGL((irfft_split_kernel<S, T, WIDE, SUMS, ADD>), grid, dim3(STHREADS), lds, st, (const float2*)xf,  \
+                       (T*)x, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, xl, ex.rowsums, (const T*)ex.addz, ex.affine)
 #define MK_IRFFT_PICK(T)                                                                                               \
-    if (g_addz) {                                                                                                      \
-        if (wide) return -1;                                                                                           \
-        hipLaunchKernelGGL((irfft_split_kernel<S, T, false, 0, false, true>), grid, dim3(STHREADS), lds, st,           \
-                           (const float2*)xf, (T*)x, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, g_xl, nullptr,     \
-                           (const T*)g_addz, g_affine);                                                                \
-    } else if (g_rowsums) {                                                                                                   \
-        if (wide) MK_IRFFT_LAUNCH(T, true, 1, true); else MK_IRFFT_LAUNCH(T, false, 0, true);                          \
-    } else {                                                                                                           \
-        if (wide) MK_IRFFT_LAUNCH(T, true, 1, false); else MK_IRFFT_LAUNCH(T, false, 0, false);                        \
-    }
+    if (ex.addz) MK_IRFFT_LAUNCH(T, false, false, true);                                                               \
+    else if (ex.rowsums && wide) MK_IRFFT_LAUNCH(T, true, true, false);                                                \
+    else if (ex.rowsums) MK_IRFFT_LAUNCH(T, false, true, false);                                                       \
+    else if (wide) MK_IRFFT_LAUNCH(T, true, false, false);                                                             \
+    else MK_IRFFT_LAUNCH(T, false, false, false)
     if (x_dtype == 0) {
-        MK_IRFFT_PICK(float)
+        MK_IRFFT_PICK(float);
     } else {
-        MK_IRFFT_PICK(__hip_bfloat16)
+        MK_IRFFT_PICK(__hip_bfloat16);
     }
 #undef MK_IRFFT_PICK
 #undef MK_IRFFT_LAUNCH
-    return 0;
-}
-
-static inline bool fft_legacy() {
-    static const bool v = [] {
-        const char* e = getenv("MK_FFT_LEGACY");
-        return e && e[0] == '1';
-    }();
-    return v;
 }

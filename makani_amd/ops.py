@@ -71,71 +71,68 @@ def fft_twiddles(nlon):
 # ----------------------------------------------------------------------------
 # raw (non-differentiable) launches
 # ----------------------------------------------------------------------------
+def _fft_split(nlon, mmax):
+    """The split FFT kernels apply: a production length, no mode above 240, not switched off (``MK_FFT_LEGACY=1``).  They alone
+    have bf16 output rows, the peer-major layout, the row statistics and the affine-add epilogue."""
+    return nlon in (480, 1440) and mmax <= 241 and os.environ.get("MK_FFT_LEGACY", "0") != "1"
+
+
+def _xf_dims(xf, kmajor=False, chans=0, cpp=0):
+    """(m, k, bc) of contiguous complex64 Fourier rows ``[M, K, BC]``, ``[K, M, BC]`` (``kmajor``) or peer-major
+    ``[chans / cpp, K, M, B * cpp]`` (``cpp`` > 0)."""
+    assert xf.dim() == (4 if cpp else 3) and xf.is_contiguous() and xf.dtype == torch.complex64
+    if cpp:
+        _, k, m, bcp = xf.shape
+        return m, k, (bcp // cpp) * chans
+    return (xf.shape[1], xf.shape[0], xf.shape[2]) if kmajor else tuple(xf.shape)
+
+
 def rfft_raw(x, twiddles, mmax, s0, sm, sh, kmajor=False):
     """x real [BC, K, N] (fp32 or bf16) -> xf complex64 [mmax, K, BC], or [K, mmax, BC] with ``kmajor``."""
     _need_cuda(x, twiddles)
     assert x.dim() == 3 and x.is_contiguous()
     bc, k, n = x.shape
-    if x.dtype == torch.float32:
-        dt = 0
-    elif x.dtype == torch.bfloat16:
-        dt = 1
-    else:
-        raise TypeError(f"mk_rfft: unsupported dtype {x.dtype}")
     xf = torch.empty((k, mmax, bc) if kmajor else (mmax, k, bc), dtype=torch.complex64, device=x.device)
-    _lib.check(_lib.load().mk_rfft_ex(x.data_ptr(), dt, xf.data_ptr(), twiddles.data_ptr(), bc, k, n, mmax,
+    _lib.check(_lib.load().mk_rfft_ex(x.data_ptr(), _pw_dtype(x), xf.data_ptr(), twiddles.data_ptr(), bc, k, n, mmax,
                                       s0, sm, sh, int(bool(kmajor)), _stream()), "mk_rfft")
     return xf
 
 
 def irfft_bf16_rows(nlon, mmax):
     """bf16 output rows are built for the production lengths (the split kernels) only."""
-    return nlon in (480, 1440) and mmax <= 241
+    return _fft_split(nlon, mmax)
 
 
 def irfft_sums_supported(nlon, mmax):
     """The inverse FFT can deliver the row statistics of its output (``mk_irfft_sums``: the split kernels)."""
-    return nlon in (480, 1440) and mmax <= 241 and os.environ.get("MK_FFT_LEGACY", "0") != "1" \
-        and os.environ.get("MK_IRFFT_SUMS", "1") != "0"
+    return _fft_split(nlon, mmax) and os.environ.get("MK_IRFFT_SUMS", "1") != "0"
 
 
 def irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor=False, chans=0, cpp=0):
     """``irfft`` (scales 1, 1, 1) of plain (``[M, K, BC]`` / ``[K, M, BC]``) or peer-major (``cpp`` > 0:
     ``[chans / cpp, K, M, B * cpp]``) Fourier rows -> (x ``[BC, K, nlon]``, fp64 ``[BC, 2]`` sums and sums of squares of its rows)."""
     _need_cuda(xf, twiddles)
-    assert xf.is_contiguous() and xf.dtype == torch.complex64 and out_dtype in (torch.float32, torch.bfloat16)
-    if cpp:
-        p, k, m, bcp = xf.shape
-        bc = (bcp // cpp) * chans
-    elif kmajor:
-        k, m, bc = xf.shape
-    else:
-        m, k, bc = xf.shape
+    m, k, bc = _xf_dims(xf, kmajor, chans, cpp)
     x = torch.empty(bc, k, nlon, dtype=out_dtype, device=xf.device)
     sums = torch.zeros(bc, 2, dtype=torch.float64, device=xf.device)
-    _lib.check(_lib.load().mk_irfft_sums(xf.data_ptr(), x.data_ptr(), 1 if out_dtype == torch.bfloat16 else 0, twiddles.data_ptr(),
-                                         bc, k, nlon, m, 1.0, 1.0, 1.0, int(bool(kmajor)), int(chans), int(cpp), sums.data_ptr(),
-                                         _stream()), "mk_irfft_sums")
+    _lib.check(_lib.load().mk_irfft_sums(xf.data_ptr(), x.data_ptr(), _pw_dtype(x), twiddles.data_ptr(), bc, k, nlon, m,
+                                         1.0, 1.0, 1.0, int(bool(kmajor)), int(chans), int(cpp), sums.data_ptr(), _stream()),
+               "mk_irfft_sums")
     return x, sums
 
 
 def irfft_affine_add_supported(nlon, mmax):
     """The inverse FFT can add ``a * z + b`` per row in its store epilogue (``mk_irfft_affine_add``: the split kernels);
     ``MK_IRFFT_AFFINE_ADD=0`` keeps the separate streaming pass (``affine_add``) -- the A/B switch of the variant."""
-    return nlon in (480, 1440) and mmax <= 241 and os.environ.get("MK_FFT_LEGACY", "0") != "1" \
-        and os.environ.get("MK_IRFFT_AFFINE_ADD", "1") != "0"
+    return _fft_split(nlon, mmax) and os.environ.get("MK_IRFFT_AFFINE_ADD", "1") != "0"
 
 
 def irfft_affine_add_raw(xf, twiddles, nlon, z, affine, kmajor=False):
     """``irfft(xf) + a * z + b`` per row: ``xf`` as for ``irfft_raw`` (scales 1, 1, 1), ``z`` a contiguous field of ``BC`` rows
     ``[K, nlon]`` (fp32 / bf16, the dtype of the result), ``affine`` fp32 ``[BC, 2]`` = (a, b) (``instance_norm_coeffs``)."""
     _need_cuda(xf, twiddles, z, affine)
-    assert xf.dim() == 3 and xf.is_contiguous() and xf.dtype == torch.complex64
-    if kmajor:
-        k, m, bc = xf.shape
-    else:
-        m, k, bc = xf.shape
-    assert z.is_contiguous() and z.numel() == bc * k * nlon and z.dtype in (torch.float32, torch.bfloat16)
+    m, k, bc = _xf_dims(xf, kmajor)
+    assert z.is_contiguous() and z.numel() == bc * k * nlon
     assert affine.dtype == torch.float32 and affine.is_contiguous() and affine.numel() == 2 * bc
     x = torch.empty_like(z)
     _lib.check(_lib.load().mk_irfft_affine_add(xf.data_ptr(), x.data_ptr(), _pw_dtype(z), twiddles.data_ptr(), bc, k, nlon, m,
@@ -148,44 +145,37 @@ def irfft_raw(xf, twiddles, nlon, s0, sm, sh, out_dtype=torch.float32, kmajor=Fa
     """xf complex64 [M, K, BC] ([K, M, BC] with ``kmajor``) -> x [BC, K, nlon] in fp32, or bf16 where the kernel
     fuses the cast."""
     _need_cuda(xf, twiddles)
-    assert xf.dim() == 3 and xf.is_contiguous() and xf.dtype == torch.complex64
-    if kmajor:
-        k, m, bc = xf.shape
-    else:
-        m, k, bc = xf.shape
+    m, k, bc = _xf_dims(xf, kmajor)
     fused = out_dtype == torch.bfloat16 and irfft_bf16_rows(nlon, m)
     x = torch.empty(bc, k, nlon, dtype=torch.bfloat16 if fused else torch.float32, device=xf.device)
-    _lib.check(_lib.load().mk_irfft_ex(xf.data_ptr(), x.data_ptr(), 1 if fused else 0, twiddles.data_ptr(), bc, k, nlon, m,
+    _lib.check(_lib.load().mk_irfft_ex(xf.data_ptr(), x.data_ptr(), int(fused), twiddles.data_ptr(), bc, k, nlon, m,
                                        s0, sm, sh, int(bool(kmajor)), _stream()), "mk_irfft")
     return x if x.dtype == out_dtype else x.to(out_dtype)
 
 
 def fft_pm_supported(nlon, mmax, chans, chans_per_peer):
     """Peer-major Fourier rows (mk_rfft_pm / mk_irfft_pm): split kernels, even channel blocks that are multiples of 24."""
-    return (irfft_bf16_rows(nlon, mmax) and chans_per_peer > 0 and chans % chans_per_peer == 0 and chans_per_peer % 24 == 0
-            and os.environ.get("MK_FFT_LEGACY") != "1")
+    return _fft_split(nlon, mmax) and chans_per_peer > 0 and chans % chans_per_peer == 0 and chans_per_peer % 24 == 0
 
 
 def rfft_pm_raw(x, twiddles, mmax, s0, sm, sh, chans, chans_per_peer):
     """x real [B*chans, K, N] -> xf complex64 [chans / cpp, K, mmax, B * cpp] (peer-major, see the header)."""
     _need_cuda(x, twiddles)
-    assert x.dim() == 3 and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
+    assert x.dim() == 3 and x.is_contiguous()
     bc, k, n = x.shape
     xf = torch.empty(chans // chans_per_peer, k, mmax, (bc // chans) * chans_per_peer, dtype=torch.complex64, device=x.device)
-    _lib.check(_lib.load().mk_rfft_pm(x.data_ptr(), 0 if x.dtype == torch.float32 else 1, xf.data_ptr(), twiddles.data_ptr(),
-                                      bc, k, n, mmax, s0, sm, sh, chans, chans_per_peer, _stream()), "mk_rfft_pm")
+    _lib.check(_lib.load().mk_rfft_pm(x.data_ptr(), _pw_dtype(x), xf.data_ptr(), twiddles.data_ptr(), bc, k, n, mmax,
+                                      s0, sm, sh, chans, chans_per_peer, _stream()), "mk_rfft_pm")
     return xf
 
 
 def irfft_pm_raw(xf, twiddles, nlon, s0, sm, sh, chans, chans_per_peer, out_dtype=torch.float32):
     """xf complex64 [chans / cpp, K, M, B * cpp] -> x [B*chans, K, nlon] (fp32 or bf16 rows)."""
     _need_cuda(xf, twiddles)
-    assert xf.dim() == 4 and xf.is_contiguous() and xf.dtype == torch.complex64
-    p, k, m, bcp = xf.shape
-    bc = (bcp // chans_per_peer) * chans
+    m, k, bc = _xf_dims(xf, True, chans, chans_per_peer)
     fused = out_dtype == torch.bfloat16
     x = torch.empty(bc, k, nlon, dtype=torch.bfloat16 if fused else torch.float32, device=xf.device)
-    _lib.check(_lib.load().mk_irfft_pm(xf.data_ptr(), x.data_ptr(), 1 if fused else 0, twiddles.data_ptr(), bc, k, nlon, m,
+    _lib.check(_lib.load().mk_irfft_pm(xf.data_ptr(), x.data_ptr(), int(fused), twiddles.data_ptr(), bc, k, nlon, m,
                                        s0, sm, sh, chans, chans_per_peer, _stream()), "mk_irfft_pm")
     return x if x.dtype == out_dtype else x.to(out_dtype)
 
@@ -703,83 +693,57 @@ def pce_gemm(x3, wimg, m, bias=None, addend=None, aux_in=None, want_pre=False, g
 # differentiable operators (all linear in the data: backward = adjoint launch)
 # ----------------------------------------------------------------------------
 class _RFFT(torch.autograd.Function):
-    """x [BC, K, N] -> xf [mmax, K, BC] = 2 pi rfft(x, norm="forward")[..., :mmax] (K1)."""
+    """x [BC, K, N] -> 2 pi rfft(x, norm="forward")[..., :mmax] (K1) as Fourier rows [mmax, K, BC], [K, mmax, BC] (``kmajor``) or,
+    with ``pm`` = (chans, cpp), peer-major; the adjoint is the inverse launch from the same layout."""
 
     @staticmethod
-    def forward(ctx, x, twiddles, mmax, kmajor=False):
+    def forward(ctx, x, twiddles, mmax, kmajor=False, pm=None):
         ctx.save_for_backward(twiddles)
-        ctx.nlon = x.shape[-1]
-        ctx.in_dtype = x.dtype
-        ctx.kmajor = kmajor
-        s = 2.0 * math.pi / ctx.nlon
+        ctx.cfg = (x.shape[-1], x.dtype, kmajor, pm)
+        s = 2.0 * math.pi / x.shape[-1]
+        if pm:
+            return rfft_pm_raw(x, twiddles, mmax, s, s, s, *pm)
         return rfft_raw(x, twiddles, mmax, s, s, s, kmajor)
 
     @staticmethod
     def backward(ctx, gxf):
         (tw,) = ctx.saved_tensors
-        n = ctx.nlon
-        gx = irfft_raw(gxf.contiguous(), tw, n, 2.0 * math.pi / n, math.pi / n, 2.0 * math.pi / n, ctx.in_dtype, ctx.kmajor)
-        return gx, None, None, None
+        n, dt, kmajor, pm = ctx.cfg
+        s = (2.0 * math.pi / n, math.pi / n, 2.0 * math.pi / n)
+        if pm:
+            gx = irfft_pm_raw(gxf.contiguous(), tw, n, *s, *pm, dt)
+        else:
+            gx = irfft_raw(gxf.contiguous(), tw, n, *s, dt, kmajor)
+        return gx, None, None, None, None
 
 
 class _IRFFT(torch.autograd.Function):
-    """xf [M, K, BC] -> x [BC, K, nlon] = irfft(xf, n=nlon, norm="forward") (K4)."""
+    """Fourier rows (layouts as for ``_RFFT``) -> x [BC, K, nlon] = irfft(xf, n=nlon, norm="forward") (K4)."""
 
     @staticmethod
-    def forward(ctx, xf, twiddles, nlon, out_dtype, kmajor=False, want_sums=False):
+    def forward(ctx, xf, twiddles, nlon, out_dtype, kmajor=False, want_sums=False, pm=None):
         ctx.save_for_backward(twiddles)
-        ctx.mmax = xf.shape[1] if kmajor else xf.shape[0]
-        ctx.kmajor = kmajor
+        chans, cpp = pm or (0, 0)
+        ctx.cfg = (_xf_dims(xf, kmajor, chans, cpp)[0], kmajor, pm)
         if want_sums:            # (x, row statistics): the sums are data for the norm's kernel, not a differentiable output
-            x, sums = irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor)
+            x, sums = irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor, chans, cpp)
             ctx.mark_non_differentiable(sums)
             return x, sums
+        if pm:
+            return irfft_pm_raw(xf, twiddles, nlon, 1.0, 1.0, 1.0, chans, cpp, out_dtype)
         return irfft_raw(xf, twiddles, nlon, 1.0, 1.0, 1.0, out_dtype, kmajor)
 
     @staticmethod
     def backward(ctx, gx, *_):
         (tw,) = ctx.saved_tensors
+        mmax, kmajor, pm = ctx.cfg
         if gx.dtype not in (torch.float32, torch.bfloat16):
             gx = gx.float()
-        return rfft_raw(gx.contiguous(), tw, ctx.mmax, 1.0, 2.0, 1.0, ctx.kmajor), None, None, None, None, None
-
-
-class _RFFTpm(torch.autograd.Function):
-    """rfft into peer-major Fourier rows; adjoint = irfft from them."""
-
-    @staticmethod
-    def forward(ctx, x, twiddles, mmax, chans, cpp):
-        ctx.save_for_backward(twiddles)
-        ctx.cfg = (x.shape[-1], x.dtype, chans, cpp)
-        s = 2.0 * math.pi / x.shape[-1]
-        return rfft_pm_raw(x, twiddles, mmax, s, s, s, chans, cpp)
-
-    @staticmethod
-    def backward(ctx, gxf):
-        (tw,) = ctx.saved_tensors
-        n, dt, chans, cpp = ctx.cfg
-        gx = irfft_pm_raw(gxf.contiguous(), tw, n, 2.0 * math.pi / n, math.pi / n, 2.0 * math.pi / n, chans, cpp, dt)
-        return gx, None, None, None, None
-
-
-class _IRFFTpm(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, xf, twiddles, nlon, out_dtype, chans, cpp, want_sums=False):
-        ctx.save_for_backward(twiddles)
-        ctx.cfg = (xf.shape[2], chans, cpp)
-        if want_sums:
-            x, sums = irfft_sums_raw(xf, twiddles, nlon, out_dtype, True, chans, cpp)
-            ctx.mark_non_differentiable(sums)
-            return x, sums
-        return irfft_pm_raw(xf, twiddles, nlon, 1.0, 1.0, 1.0, chans, cpp, out_dtype)
-
-    @staticmethod
-    def backward(ctx, gx, *_):
-        (tw,) = ctx.saved_tensors
-        mmax, chans, cpp = ctx.cfg
-        if gx.dtype not in (torch.float32, torch.bfloat16):
-            gx = gx.float()
-        return rfft_pm_raw(gx.contiguous(), tw, mmax, 1.0, 2.0, 1.0, chans, cpp), None, None, None, None, None, None
+        if pm:
+            gxf = rfft_pm_raw(gx.contiguous(), tw, mmax, 1.0, 2.0, 1.0, *pm)
+        else:
+            gxf = rfft_raw(gx.contiguous(), tw, mmax, 1.0, 2.0, 1.0, kmajor)
+        return gxf, None, None, None, None, None, None
 
 
 class _LegendreFwd(torch.autograd.Function):
@@ -939,11 +903,11 @@ def irfft(xf, twiddles, nlon, out_dtype=torch.float32, kmajor=False, want_sums=F
 
 
 def rfft_pm(x, twiddles, mmax, chans, cpp):
-    return _RFFTpm.apply(x, twiddles, mmax, chans, cpp)
+    return _RFFT.apply(x, twiddles, mmax, True, (chans, cpp))
 
 
 def irfft_pm(xf, twiddles, nlon, out_dtype, chans, cpp, want_sums=False):
-    return _IRFFTpm.apply(xf, twiddles, nlon, out_dtype, chans, cpp, want_sums)
+    return _IRFFT.apply(xf, twiddles, nlon, out_dtype, True, want_sums, (chans, cpp))
 
 
 def legendre_fwd(xf, table, lmax, m_off=0, kmajor=False):

@@ -8,8 +8,10 @@ same constructor arguments, the attributes ``nlat, nlon, lmax, mmax, grid`` that
 checkpoints load with ``strict=True``), arbitrary leading dims, autograd.
 
 The arithmetic is two HIP launches per direction through the C ABI: the batched
-longitudinal real FFT (``mk_rfft`` / ``mk_irfft``) and the Legendre contraction on
-fp32 MFMA (``mk_legendre_fwd`` / ``mk_legendre_inv``); ``forward_packed`` /
+longitudinal real FFT (``mk_rfft_ex`` / ``mk_irfft_ex``, or ``mk_irfft_sums`` where the
+row statistics are wanted) and the Legendre contraction (``mk_legendre_fwd_x3_ex`` /
+``mk_legendre_inv_x3_ex`` on the bf16x3 engine, ``mk_legendre_fwd`` / ``mk_legendre_inv``
+on fp32 MFMA with ``MK_SPECTRAL_GEMM=f32``); ``forward_packed`` /
 ``inverse_packed`` expose the channels-last spectrum ``[L, M, BC]`` that the fused
 ``SpectralConv`` path consumes without a layout round trip.
 """

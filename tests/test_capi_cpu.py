@@ -67,6 +67,50 @@ def test_twiddles():
         assert np.abs(b[:, 0] + 1j * b[:, 1] - np.exp(-2j * np.pi * np.arange(h + 1) / n)).max() < 1e-7
 
 
+_P = 4096      # a non-null, 16-byte aligned address that is never dereferenced: validation returns before any launch
+
+# entry point -> its arguments behind (bc, nlat, nlon, mmax, scale0, scale_m, scale_h), as names looked up in the case
+_FFT_TAILS = {"mk_rfft": (), "mk_rfft_ex": ("xf_layout",), "mk_irfft_ex": ("xf_layout",), "mk_rfft_pm": ("chans", "cpp"),
+              "mk_irfft_pm": ("chans", "cpp"), "mk_irfft_sums": ("xf_layout", "chans", "cpp", "rowsums"),
+              "mk_irfft_affine_add": ("xf_layout", "z", "affine")}
+_FFT_DEFAULTS = dict(a=_P, b=_P, x_dtype=0, tw=_P, bc=48, nlat=4, nlon=480, mmax=33, xf_layout=0, chans=48, cpp=24, rowsums=_P,
+                     z=_P, affine=_P)
+FFT_REJECTED = [      # entry point, the input it must refuse (everything else valid)
+    ("mk_rfft_ex", dict(nlon=481)),
+    ("mk_rfft_ex", dict(mmax=242)),
+    ("mk_rfft_ex", dict(xf_layout=2)),
+    ("mk_rfft_ex", dict(x_dtype=2)),
+    ("mk_rfft", dict(a=None)),
+    ("mk_irfft_ex", dict(x_dtype=1, nlon=64)),
+    ("mk_irfft_ex", dict(mmax=0)),
+    ("mk_rfft_pm", dict(cpp=20)),
+    ("mk_rfft_pm", dict(nlon=64)),
+    ("mk_irfft_pm", dict(bc=50)),
+    ("mk_irfft_sums", dict(rowsums=None)),
+    ("mk_irfft_sums", dict(nlon=64)),
+    ("mk_irfft_sums", dict(xf_layout=1, cpp=20)),
+    ("mk_irfft_affine_add", dict(z=None)),
+    ("mk_irfft_affine_add", dict(b=_P + 4)),
+    ("mk_irfft_affine_add", dict(xf_layout=3)),
+    ("mk_irfft_affine_add", dict(bc=1200, nlat=933, mmax=3)),      # (240 * 933 + 1) * 1200 * 8 >= 2^31
+]
+
+
+@pytest.mark.parametrize("name,bad", FFT_REJECTED, ids=[f"{n}-{'-'.join(f'{k}={v}' for k, v in b.items())}" for n, b in FFT_REJECTED])
+def test_fft_entry_points_reject_bad_input(name, bad):
+    """Every FFT entry point validates before it launches: code 1 (a refused argument, not a launch failure) and a message."""
+    lib = _lib.load()
+    a = dict(_FFT_DEFAULTS, **bad)
+    if name == "mk_irfft_sums" and "cpp" not in bad:
+        a.update(chans=0, cpp=0)      # plain Fourier rows unless the case is about the peer-major ones
+    head = (a["a"], a["x_dtype"], a["b"]) if name.startswith("mk_rfft") else (a["a"], a["b"], a["x_dtype"])
+    args = head + (a["tw"], a["bc"], a["nlat"], a["nlon"], a["mmax"], 1.0, 1.0, 1.0) + tuple(a[k] for k in _FFT_TAILS[name])
+    lib.mk_quadrature(7, 10, 0, 0)      # leaves a message of another function behind: the one below must replace it
+    assert getattr(lib, name)(*args, None) == 1
+    msg = lib.mk_last_error()
+    assert msg and b"unknown grid" not in msg
+
+
 def test_errors_are_loud():
     lib = _lib.load()
     assert lib.mk_quadrature(7, 10, 0, 0) != 0

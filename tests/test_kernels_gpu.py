@@ -516,6 +516,115 @@ def test_irfft_row_statistics(dev, nlat, nlon, mmax, B, C, cpp, dtype):
     assert torch.equal(xf2.grad, xf3.grad)
 
 
+def _row_stats(x):
+    """float64 (sum, sum of squares) of the rows of x and the scale the 2e-6 bound of the statistics is relative to."""
+    xd = x.double()
+    sq = (xd * xd).sum(dim=(1, 2))
+    return torch.stack([xd.sum(dim=(1, 2)), sq], dim=1), torch.stack([xd.abs().sum(dim=(1, 2)), sq], dim=1)
+
+
+FFT_STATE_CASES = [(5, 480, 33, 2, 48, 24), (3, 1440, 241, 1, 48, 24)]      # nlat, nlon, mmax, B, C, cpp
+_fft_state_cache = {}
+
+
+def _fft_state_case(dev, case):
+    """Inputs of one case and the result of every FFT variant from a call of its own (computed once, never modified)."""
+    if case in _fft_state_cache:
+        return _fft_state_cache[case]
+    from makani_amd import ops
+    nlat, nlon, mmax, B, C, cpp = case
+    g = torch.Generator().manual_seed(23)
+    bc, s = B * C, 2 * math.pi / nlon
+    i = dict(tw=ops.fft_twiddles(nlon).to(dev), x=torch.randn(bc, nlat, nlon, generator=g).to(dev),
+             z=torch.randn(bc, nlat, nlon, generator=g).to(dev), affine=torch.randn(bc, 2, generator=g).to(dev),
+             xf=torch.complex(torch.randn(nlat, mmax, bc, generator=g), torch.randn(nlat, mmax, bc, generator=g)).to(dev))
+    i["pm"] = i["xf"].view(nlat, mmax, B, C // cpp, cpp).permute(3, 0, 1, 2, 4).reshape(C // cpp, nlat, mmax, B * cpp).contiguous()
+    calls = dict(
+        irfft=lambda: ops.irfft_raw(i["xf"], i["tw"], nlon, 1.0, 1.0, 1.0, kmajor=True),
+        irfft_pm=lambda: ops.irfft_pm_raw(i["pm"], i["tw"], nlon, 1.0, 1.0, 1.0, C, cpp),
+        irfft_sums=lambda: ops.irfft_sums_raw(i["pm"], i["tw"], nlon, torch.float32, True, C, cpp),
+        irfft_affine_add=lambda: ops.irfft_affine_add_raw(i["xf"], i["tw"], nlon, i["z"], i["affine"], kmajor=True),
+        rfft=lambda: ops.rfft_raw(i["x"], i["tw"], mmax, s, s, s),
+        rfft_kmajor=lambda: ops.rfft_raw(i["x"], i["tw"], mmax, s, s, s, kmajor=True),
+        rfft_pm=lambda: ops.rfft_pm_raw(i["x"], i["tw"], mmax, s, s, s, C, cpp))
+    alone = {name: fn() for name, fn in calls.items()}
+    torch.cuda.synchronize()
+    _fft_state_cache[case] = (i, calls, alone)
+    return _fft_state_cache[case]
+
+
+@pytest.mark.parametrize("case", FFT_STATE_CASES)
+def test_fft_calls_leave_no_state(dev, case):
+    """Each FFT entry point gets its layout, statistics pointer and companion field from its own arguments alone: in a
+    sequence that alternates the variants every output is bit-equal to that of a call on its own, and the statistics of
+    the first call are not added to by any later one."""
+    i, calls, alone = _fft_state_case(dev, case)
+    stats, scale = _row_stats(alone["irfft"])
+    assert torch.equal(alone["irfft_sums"][0], alone["irfft"]) and torch.equal(alone["irfft_pm"], alone["irfft"])
+    assert torch.equal(alone["rfft_kmajor"], alone["rfft"].permute(1, 0, 2))
+    assert ((alone["irfft_sums"][1] - stats).abs() / scale).max().item() < 2e-6
+    first_sums = None
+    for name in ("irfft_sums", "irfft", "irfft_affine_add", "irfft", "rfft_pm", "rfft", "irfft_pm", "irfft"):
+        got = calls[name]()
+        if name == "irfft_sums":
+            got, first_sums = got
+            torch.cuda.synchronize()
+            kept = first_sums.clone()
+            assert ((first_sums - stats).abs() / scale).max().item() < 2e-6
+        want = alone[name][0] if name == "irfft_sums" else alone[name]
+        assert torch.equal(got, want), name
+    torch.cuda.synchronize()
+    assert torch.equal(first_sums, kept)
+
+
+def test_refused_fft_call_leaves_no_state(dev):
+    """A call that validation refuses launches nothing and leaves nothing behind: the statistics tensor it was given is
+    untouched by the plain inverse transform that follows."""
+    from makani_amd import _lib, ops
+    nlat, nlon, mmax, B, C, cpp = FFT_STATE_CASES[0]
+    i, calls, alone = _fft_state_case(dev, FFT_STATE_CASES[0])
+    sums = torch.full((B * C, 2), 7.0, dtype=torch.float64, device=dev)
+    tw64 = ops.fft_twiddles(64).to(dev)
+    x = torch.empty(B * C, nlat, 64, device=dev)
+    rc = _lib.load().mk_irfft_sums(i["xf"].data_ptr(), x.data_ptr(), 0, tw64.data_ptr(), B * C, nlat, 64, mmax, 1.0, 1.0, 1.0, 1,
+                                   0, 0, sums.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc != 0 and _lib.load().mk_last_error()
+    got = calls["irfft"]()
+    torch.cuda.synchronize()
+    assert torch.equal(got, alone["irfft"])
+    assert torch.equal(sums, torch.full_like(sums, 7.0))
+
+
+def test_irfft_wide_offsets(dev):
+    """The WIDE variant of the split inverse kernel (64-bit mode offsets, chosen when (240 * nlat + 1) * bc * 8 >= 2^31 in the
+    mode-major layout) writes exactly the rows of the narrow variant, which the same numbers in the latitude-major layout
+    (mode stride 1) select -- plain and with the row statistics, bf16 rows, a ragged last tile."""
+    from makani_amd import ops
+    nlat, nlon, mmax, bc = 933, 480, 3, 1205
+    assert (240 * nlat + 1) * bc * 8 >= 2 ** 31 and (240 + 1) * bc * 8 < 2 ** 31
+    g = torch.Generator().manual_seed(29)
+    tw = ops.fft_twiddles(nlon).to(dev)
+    xf = torch.complex(torch.randn(mmax, nlat, bc, generator=g), torch.randn(mmax, nlat, bc, generator=g)).to(dev)
+    xk = xf.permute(1, 0, 2).contiguous()
+    narrow = ops.irfft_raw(xk, tw, nlon, 1.0, 1.0, 1.0, torch.bfloat16, kmajor=True)
+    wide = ops.irfft_raw(xf, tw, nlon, 1.0, 1.0, 1.0, torch.bfloat16, kmajor=False)
+    plain_equal = torch.equal(wide, narrow)
+    del wide
+    xw, sw = ops.irfft_sums_raw(xf, tw, nlon, torch.bfloat16, False)
+    sums_rows_equal = torch.equal(xw, narrow)
+    del xw
+    xn, sn = ops.irfft_sums_raw(xk, tw, nlon, torch.bfloat16, True)
+    narrow_rows_equal = torch.equal(xn, narrow)
+    del xn
+    stats, scale = _row_stats(narrow)
+    del narrow
+    err_pair, err_wide = ((sw - sn).abs() / scale).max().item(), ((sw - stats).abs() / scale).max().item()
+    print(f"wide irfft: rows equal {plain_equal} / {sums_rows_equal} / {narrow_rows_equal}, sums wide vs narrow {err_pair:.2e}, "
+          f"wide vs fp64 {err_wide:.2e}")
+    assert plain_equal and sums_rows_equal and narrow_rows_equal
+    assert err_pair < 2e-6 and err_wide < 2e-6
+
+
 @pytest.mark.parametrize("M,K,P,B,bias,gelu", [(384, 384, 1000, 2, True, True), (768, 73, 520, 1, True, False), (73, 384, 264, 3, False, True),
                                                  (130, 200, 136, 1, True, True)])
 def test_conv1x1_x3_bias_gelu_epilogue(dev, M, K, P, B, bias, gelu):
