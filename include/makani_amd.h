@@ -451,6 +451,31 @@ int mk_history_sums(const void* x, int x_dtype, const float* u, const float* wt,
 int mk_cos_zenith(const float* eph, const float* sin_lat, const float* cos_lat, const float* lon_rad, float* out, long long n,
                   int H, int W, void* stream);
 
+/* ---- layer norm over the CHANNEL axis of an NCHW field (csrc/chnorm.hip): DistributedLayerNorm
+ * (makani/mpu/layer_norm.py:117-155; normalization_layer = "layer_norm", makani/models/networks/sfnonet.py:371-382) without
+ * the transposes around nn.LayerNorm.  x [B][C][P] contiguous, P = H W, fp32 (dtype 0) or bf16 (1); per (b, p)
+ *   mean = sum_c x / C,  var = sum_c (x - mean)^2 / C (biased, two passes),  rstd = 1 / sqrt(var + eps),
+ *   y_c = act(weight[c] (x_c - mean) rstd + bias[c]),  act = exact GELU if fuse_gelu else identity,
+ * computed in fp32 and rounded once on the store to y's dtype (0 / 1, independent of x's).  weight, bias fp32 [C], each may
+ * be NULL (1 / 0).  stats [B][P][2] = (mean, rstd) fp32 is kept for the backward (NULL: not written).  Any B, C, P >= 1 and any
+ * element-aligned pointers: 16-byte vectors when P is a multiple of 16 / sizeof(x element) and x, y (gy, gx) are 16-byte
+ * aligned, single elements otherwise; a pixel tile over all channels stays in LDS between its uses while it fits, else it is
+ * read again (L2).  x is read once and y written once from / to HBM.  The channel sums of a pixel are formed in an order
+ * that depends on C only, so a launch on a spatial slice gives the bits of the slice of the full result.
+ * Backward: gy [B][C][P] fp32 / bf16 (its own dtype), with xh = (x - mean) rstd, g = gy (fused: gy gelu'(weight xh + bias),
+ * recomputed), s1 = sum_c weight g, s2 = sum_c weight g xh:
+ *   gx_c = rstd (weight[c] g_c - s1 / C - xh_c s2 / C)   in x's dtype,
+ *   gwb [2][C] fp32:  row 0 = sum_{b,p} g_c xh_c (weight gradient),  row 1 = sum_{b,p} g_c (bias gradient);
+ * gwb NULL: not formed.  Deterministic (no atomics): per-workgroup fp32 partials in `workspace`
+ * (mk_chan_layernorm_workspace(B, C, P) floats, no need to clear it), added in a fixed order in fp64 by a finishing launch.
+ * No allocation, synchronisation or host copy; the launch configuration depends on the shape and dtypes only. */
+long long mk_chan_layernorm_workspace(int B, int C, long long P);
+int mk_chan_layernorm_fwd(const void* x, int x_dtype, const float* weight, const float* bias, void* y, int y_dtype,
+                          float* stats, int B, int C, long long P, float eps, int fuse_gelu, void* stream);
+int mk_chan_layernorm_bwd(const void* x, int x_dtype, const void* gy, int gy_dtype, const float* stats, const float* weight,
+                          const float* bias, void* gx, float* workspace, float* gwb, int B, int C, long long P, int fuse_gelu,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

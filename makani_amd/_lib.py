@@ -112,6 +112,11 @@ SIGNATURES = {
     "mk_history_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "mk_history_sums": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 6 + [_vp]),
     "mk_cos_zenith": (_c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _c_int, _c_int, _vp]),
+    "mk_chan_layernorm_workspace": (ctypes.c_longlong, [_c_int, _c_int, ctypes.c_longlong]),
+    "mk_chan_layernorm_fwd": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _c_int, _vp, _c_int, _c_int, ctypes.c_longlong, _c_float,
+                                       _c_int, _vp]),
+    "mk_chan_layernorm_bwd": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong,
+                                       _c_int, _vp]),
 }
 
 

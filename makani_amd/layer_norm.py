@@ -89,8 +89,10 @@ class DistributedInstanceNorm2d(nn.Module):
 class DistributedLayerNorm(nn.Module):
     """``makani/mpu/layer_norm.py:117-155``: layer norm over the CHANNEL axis of an NCHW field, per grid point (so it needs no
     communication under spatial sharding; the reference notes that it breaks equivariance).  Same parameters
-    (``norm.weight`` / ``norm.bias``, shared over the ``model`` group) and the same arithmetic: transpose channels last,
-    ``nn.LayerNorm``, transpose back.  Outside the benchmarked configuration (instance norm): torch ops, no HIP kernel."""
+    (``norm.weight`` / ``norm.bias``, shared over the ``model`` group).  On the GPU (fp32 / bf16 NCHW fields of any shape)
+    the norm runs on the HIP channel-norm kernels (``ops.channel_layer_norm``): one pass over the field each way, the
+    block's GELU fused on request, no transposed copy.  ``_forward_torch`` is the reference's formulation -- transpose
+    channels last, ``nn.LayerNorm``, transpose back -- and the CPU / other-dtype path."""
 
     def __init__(self, normalized_shape, eps=1e-05, elementwise_affine=True, bias=True, device=None, dtype=None):
         super().__init__()
@@ -104,5 +106,18 @@ class DistributedLayerNorm(nn.Module):
                 self.norm.bias.is_shared_mp = ["model"]
                 self.norm.bias.sharded_dims_mp = [None]
 
-    def forward(self, x):
+    def forward(self, x, fuse_gelu=False, out_dtype=None):
+        """``out_dtype`` None: the dtype ``_forward_torch`` returns in the same context (``x.dtype``; fp32 under CUDA
+        autocast, where ``layer_norm`` is one of torch's fp32 ops)."""
+        from . import ops
+        if ops.channel_layer_norm_supported(x):
+            if out_dtype is None:
+                out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
+            return ops.channel_layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps, fuse_gelu, out_dtype)
+        y = self._forward_torch(x)
+        if fuse_gelu:
+            y = torch.nn.functional.gelu(y)
+        return y if out_dtype is None else y.to(out_dtype)
+
+    def _forward_torch(self, x):
         return torch.transpose(self.norm(torch.transpose(x, 1, 3)), 1, 3).contiguous()

@@ -1163,6 +1163,75 @@ def instance_norm(x, weight, bias, eps=1e-5, fuse_gelu=False, group=None, count=
 
 
 # ----------------------------------------------------------------------------
+# layer norm over the channel axis of an NCHW field (csrc/chnorm.hip)
+# ----------------------------------------------------------------------------
+def channel_layer_norm_supported(x):
+    """NCHW on the GPU in fp32 / bf16; any H * W, any C (``channel_layer_norm`` makes the field contiguous itself)."""
+    return x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0
+
+
+class _ChannelLayerNorm(torch.autograd.Function):
+    """Layer norm over C per (b, h, w) with optional fused GELU, one HBM pass each way; statistics in fp32.
+
+    Saves ``x`` and the per-pixel (mean, rstd); the GELU pre-activation is recomputed.  The weight / bias gradients
+    returned are the LOCAL sums over this rank's pixels (shared-weight reduction sums them later).
+    """
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, fuse_gelu, out_dtype):
+        _need_cuda(x)
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        y = torch.empty(x.shape, dtype=x.dtype if out_dtype is None else out_dtype, device=x.device)
+        wf = None if weight is None else weight.detach().float().contiguous()
+        bf = None if bias is None else bias.detach().float().contiguous()
+        stats = torch.empty(B, H * W, 2, dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().mk_chan_layernorm_fwd(x.data_ptr(), _pw_dtype(x), 0 if wf is None else wf.data_ptr(),
+                                                     0 if bf is None else bf.data_ptr(), y.data_ptr(), _pw_dtype(y),
+                                                     stats.data_ptr(), B, C, H * W, float(eps), int(fuse_gelu), _stream()),
+                   "mk_chan_layernorm_fwd")
+        empty = x.new_empty(0, dtype=torch.float32)
+        ctx.save_for_backward(x, stats, wf if wf is not None else empty, bf if bf is not None else empty)
+        ctx.cfg = (weight is not None, bias is not None, bool(fuse_gelu), None if weight is None else weight.dtype,
+                   None if bias is None else bias.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, stats, wf, bf = ctx.saved_tensors
+        has_w, has_b, fuse, wdt, bdt = ctx.cfg
+        B, C, H, W = x.shape
+        if gy.dtype not in (torch.float32, torch.bfloat16):
+            gy = gy.float()
+        gy = gy.contiguous()
+        gx = torch.empty_like(x)
+        lib = _lib.load()
+        want = (has_w and ctx.needs_input_grad[1]) or (has_b and ctx.needs_input_grad[2])
+        ws = gwb = None
+        if want:
+            ws = torch.empty(lib.mk_chan_layernorm_workspace(B, C, H * W), dtype=torch.float32, device=x.device)
+            gwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
+        _lib.check(lib.mk_chan_layernorm_bwd(x.data_ptr(), _pw_dtype(x), gy.data_ptr(), _pw_dtype(gy), stats.data_ptr(),
+                                             wf.data_ptr() if has_w else 0, bf.data_ptr() if has_b else 0, gx.data_ptr(),
+                                             0 if ws is None else ws.data_ptr(), 0 if gwb is None else gwb.data_ptr(), B, C,
+                                             H * W, int(fuse), _stream()), "mk_chan_layernorm_bwd")
+        gw = gwb[0].to(wdt) if (has_w and ctx.needs_input_grad[1]) else None
+        gb = gwb[1].to(bdt) if (has_b and ctx.needs_input_grad[2]) else None
+        return gx, gw, gb, None, None, None
+
+
+def channel_layer_norm(x, weight, bias, eps=1e-5, fuse_gelu=False, out_dtype=None):
+    """``act(weight * (x - mean) * rstd + bias)`` with mean / biased variance over the CHANNELS of ``x [B, C, H, W]`` at every
+    grid point (``nn.LayerNorm(C)`` on the channels-last view, without the transposes), ``act`` = exact GELU when
+    ``fuse_gelu``.  ``weight`` / ``bias`` may be None; ``out_dtype`` (fp32 / bf16) defaults to ``x.dtype``."""
+    if not channel_layer_norm_supported(x):
+        raise RuntimeError("makani_amd: channel_layer_norm needs a 4-D fp32 / bf16 field on a HIP device; there is no fallback")
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise TypeError(f"makani_amd channel_layer_norm: unsupported out_dtype {out_dtype}")
+    return _ChannelLayerNorm.apply(x, weight, bias, eps, fuse_gelu, out_dtype)
+
+
+# ----------------------------------------------------------------------------
 # validation metrics (csrc/metrics.hip)
 # ----------------------------------------------------------------------------
 GEO_METRIC_SUMS = ("l1", "sq", "cov", "var_p", "var_t")     # order of the last axis of geo_metric_sums

@@ -162,7 +162,21 @@ class FourierNeuralOperatorBlock(nn.Module):
             x, residual = self.filter(x, premix=premix, spectrum_residual=spec_skip)
         else:
             x, residual = self.filter(x)
-        if inner is None and hip_norm0 and _is_exact_gelu(self.act_layer0):
+        ln_dtype = None
+        if x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled()
+                                                        and torch.get_autocast_dtype("cuda") == torch.bfloat16)):
+            ln_dtype = torch.bfloat16     # bf16-engine step: the layer norms hand the MLP / skip convolution the engine's field
+        if isinstance(self.norm0, DistributedLayerNorm):
+            # channel layer norm (+ GELU) on one HIP pass.  Fused, the result is rounded once to the dtype the convolution behind
+            # it takes; with an inner skip in between, an engine step rounds the norm's result to bf16 BEFORE the skip add and
+            # the activation (one bf16 rounding more than autocast makes there, which keeps both in fp32)
+            fuse = inner is None and _is_exact_gelu(self.act_layer0)
+            x = self.norm0(x, fuse_gelu=fuse, out_dtype=ln_dtype)
+            if not fuse:
+                if inner is not None:
+                    x = x + inner(residual)
+                x = self.act_layer0(x)
+        elif inner is None and hip_norm0 and _is_exact_gelu(self.act_layer0):
             x = self.norm0(x, fuse_gelu=True, row_sums=sums0)  # norm0 + GELU: (no statistics pass,) one apply pass
         elif hip_norm0:
             x = self.norm0(x, row_sums=sums0)
@@ -193,7 +207,10 @@ class FourierNeuralOperatorBlock(nn.Module):
             y = conv_plus_instance_norm(outer, residual, x, sums, self.norm1)
             if y is not None:
                 return y
-        x = self.drop_path(self.norm1(x, row_sums=sums) if sums is not None else self.norm1(x))
+        if isinstance(self.norm1, DistributedLayerNorm):
+            x = self.drop_path(self.norm1(x, out_dtype=ln_dtype))
+        else:
+            x = self.drop_path(self.norm1(x, row_sums=sums) if sums is not None else self.norm1(x))
         if isinstance(outer, Conv1x1):
             x = outer(residual, addend=x)                     # skip add folded into the GEMM epilogue
         elif outer is not None:
@@ -265,7 +282,7 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
             return partial(InstanceNorm2d, num_features=embed_dim, eps=1e-6, affine=True, track_running_stats=False)
         if kind == "none":
             return nn.Identity
-        if kind == "layer_norm":       # sfnonet.py:371-373: channel-wise layer norm per grid point (torch ops; not the benchmarked norm)
+        if kind == "layer_norm":       # sfnonet.py:371-373: channel-wise layer norm per grid point (HIP channel-norm passes on the GPU)
             return partial(DistributedLayerNorm, normalized_shape=(embed_dim), elementwise_affine=True, eps=1e-6)
         raise NotImplementedError(f"Error, normalization {kind} not implemented.")
 
