@@ -476,6 +476,22 @@ int mk_chan_layernorm_bwd(const void* x, int x_dtype, const void* gy, int gy_dty
                           const float* bias, void* gx, float* workspace, float* gwb, int B, int C, long long P, int fuse_gelu,
                           void* stream);
 
+/* ---- per-degree power of a packed spectrum (csrc/specnorm.hip): the degree sums of GeometricH1Loss
+ * (makani/utils/losses.py:306-318) without the public layout.  c [L][M][BC] complex64 (the private spectrum; rows with
+ * l_off + l < m_off + m may hold anything, they are never loaded), l_off / m_off the shard's global offsets as for
+ * mk_spec_unpack:
+ *   P[l][bc] = sum_m w(m_off + m) |c[l][m][bc]|^2,   w(0) = 1, w(m > 0) = 2,   P [L][BC] fp64.
+ * re and im are converted to double before squaring and added in double in ascending m, in chunks of a fixed number of
+ * local orders that a finishing launch adds in order: deterministic (no atomics), independent of l_off, so the rows of an
+ * l slice carry the bits of the same rows of the whole; the sums add up over m shards.  Any L, M, BC >= 1.  No allocation,
+ * synchronisation or host copy: `workspace` holds mk_degree_power_workspace(L, M, BC) doubles (no need to clear it).
+ * Backward, gP [L][BC] fp64 on the device (the upstream gradient of P):
+ *   gc[l][m][bc] = 2 w(m_off + m) gP[l][bc] c[l][m][bc]   (product in double, rounded once to fp32),
+ * exact zeros where l_off + l < m_off + m: the complex gradient in torch's convention (d/d re + i d/d im), in c's layout. */
+long long mk_degree_power_workspace(int L, int M, int BC);
+int mk_degree_power(const float* c, double* workspace, double* P, int L, int M, int BC, int l_off, int m_off, void* stream);
+int mk_degree_power_bwd(const float* c, const double* gP, float* gc, int L, int M, int BC, int l_off, int m_off, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

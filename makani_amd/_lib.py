@@ -117,6 +117,9 @@ SIGNATURES = {
                                        _c_int, _vp]),
     "mk_chan_layernorm_bwd": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong,
                                        _c_int, _vp]),
+    "mk_degree_power_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "mk_degree_power": (_c_int, [_vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
+    "mk_degree_power_bwd": (_c_int, [_vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
 }
 
 

@@ -14,8 +14,15 @@ norm with uniform channel weights -- the loss the bench harness trains with -- k
 Under spatial model parallelism the reference gathers prediction and target over ``h`` then ``w`` (``losses.py:149-157``)
 and every rank integrates both full fields.  The integrals add up across shards, so here a rank integrates its own shard
 with its slice of the latitude weights and the ``[B, C, 2]`` float64 sums are all-reduced over the ``"spatial"`` group;
-the gradient of the all-reduce is the identity, which leaves every rank with its shard of the global gradient.  Only the
-H1 loss still gathers.
+the gradient of the all-reduce is the identity, which leaves every rank with its shard of the global gradient.
+
+The H1 loss (``GeometricH1Loss``) is a function of the per-degree power of the spherical-harmonic coefficients of the
+error and of the target: the transform's packed spectrum ``[L, M, BC]`` is summed over the orders by one HIP pass into
+float64 (``ops.degree_power`` / ``mk_degree_power``, ``mk_degree_power_bwd``), whose gradient the transform's backward
+takes in the same layout.  The degree sums add up over ``m`` shards and concatenate over ``l`` shards, so under spatial
+parallelism a rank transforms its own shard with ``DistributedRealSHT`` and the per-sample ``[B, 2]`` float64 sums are
+all-reduced over the ``"spatial"`` group: no loss gathers CUDA fields.  (CPU tensors are still gathered first, as the
+reference does; the transform has no CPU path.)
 """
 import math
 
@@ -163,26 +170,62 @@ class GeometricLpLoss(nn.Module):
 class GeometricH1Loss(nn.Module):
     """Weighted H1 loss on the sphere, losses.py:275-370: L2 and l (l + 1)-weighted norms of the spherical-harmonic
     coefficients of the error (``alpha`` balances the two), relative to the target's or absolute.  The transform is this
-    package's HIP ``RealSHT``; the degree sums are a handful of small torch reductions on its output.
+    package's HIP ``RealSHT``; its packed spectrum ``[L, M, BC]`` goes straight into one HIP pass that forms the per-degree
+    sums in float64 (``ops.degree_power``), and the two weighted sums over channels and degrees are taken on that small
+    ``[B, C, L]`` tensor.  The error ``prd - tar`` is formed in grid space: subtracting two spectra would cancel the
+    error's leading digits once the prediction is close to the target.
+
+    Under spatial parallelism (``comm.get_size("spatial") > 1``) the transform is a ``DistributedRealSHT``, ``forward``
+    takes the ranks' own shards ``[B, C, H_loc, W_loc]`` and the per-sample ``[B, 2]`` partial sums of the rank's degrees and
+    orders are all-reduced over the ``"spatial"`` group once per norm; the gradient of the all-reduce is the identity.
 
     As in the reference the third argument of ``forward`` is a per-(sample, channel) mask of the relative form --
     ``LossHandler`` passes its channel weights there (losses.py:168 with 364-368), which weights the relative norms."""
 
     def __init__(self, img_shape, p=2.0, size_average=False, reduction=True, absolute=False, squared=False, alpha=0.5):
         super().__init__()
-        from .sht import RealSHT
         self.reduction, self.size_average = reduction, size_average
         self.absolute, self.squared, self.alpha = absolute, squared, alpha
-        self.sht = RealSHT(*img_shape, grid="equiangular").float()
+        self.sharded = comm.get_size("spatial") > 1
+        if self.sharded:
+            from .distributed import DistributedRealSHT
+            self.sht = DistributedRealSHT(*img_shape, grid="equiangular").float()
+        else:
+            from .sht import RealSHT
+            self.sht = RealSHT(*img_shape, grid="equiangular").float()
         h1_weights = torch.arange(self.sht.lmax).float()
         self.register_buffer("h1_weights", h1_weights * (h1_weights + 1))
 
+    def norms_from_spectrum(self, c_packed, batch, l_off=0, m_off=0):
+        """``[batch, 2]`` float64 (L2 norm squared, H1 seminorm squared) of the packed spectrum ``[L_loc, M_loc, batch * C]``
+        of the degrees from ``l_off`` and the orders from ``m_off`` on: sums over channels, degrees and orders (m > 0
+        twice).  They add up over the shards of a spectrum."""
+        from . import ops
+        power = ops.degree_power(c_packed, l_off, m_off)                  # [batch * C, L_loc] float64
+        nl = power.shape[1]
+        power = power.reshape(batch, -1, nl)
+        wl = self.h1_weights[l_off:l_off + nl].to(torch.float64)         # l (l + 1) of the GLOBAL degree, exact in fp32
+        return torch.stack([power.sum(dim=(1, 2)), (power * wl).sum(dim=(1, 2))], dim=-1)
+
     def _norms(self, x):
         """(L2 norm squared, H1 seminorm squared) per sample: sums over channels, degrees and orders (m > 0 twice)."""
+        n = x.size()[0]
+        if x.is_cuda:
+            if x.dtype not in (torch.float32, torch.bfloat16):
+                x = x.float()
+            nlat, nlon = x.shape[-2:]
+            if self.sharded:
+                c = self.sht.forward_packed(x.reshape(n, -1, nlat, nlon).contiguous())
+                sums = self.norms_from_spectrum(c, n, self.sht.l_off, self.sht.m_off)
+                sums = reduce_from_parallel_region(sums, "spatial")
+            else:
+                if nlat != self.sht.nlat or nlon != self.sht.nlon:
+                    raise ValueError(f"expected [..., {self.sht.nlat}, {self.sht.nlon}], got {tuple(x.shape)}")
+                sums = self.norms_from_spectrum(self.sht.forward_packed(x.reshape(-1, nlat, nlon).contiguous()), n)
+            return sums[:, 0], sums[:, 1]
         c = torch.view_as_real(self.sht(x))
         c = c[..., 0] ** 2 + c[..., 1] ** 2
         norm2 = c[..., :, 0] + 2 * torch.sum(c[..., :, 1:], dim=-1)
-        n = x.size()[0]
         return norm2.reshape(n, -1).sum(dim=-1), (norm2 * self.h1_weights).reshape(n, -1).sum(dim=-1)
 
     def _combine(self, l2, h1):
@@ -207,13 +250,14 @@ class GeometricH1Loss(nn.Module):
         return retval
 
     def forward(self, prd, tar, mask=None):
-        return self.abs(prd, tar) if self.absolute else self.rel(prd, tar, mask)
+        out = self.abs(prd, tar) if self.absolute else self.rel(prd, tar, mask)
+        return out.float() if out.dtype == torch.float64 else out      # the degree sums are float64, the loss is fp32
 
 
 class LossHandler(nn.Module):
     """losses.py:33-172 for the Lp family: parses ``params.loss`` ("l2", "geometric l2", "absolute squared geometric l2",
     "weighted ...", "pole-masked ...", "l1" ...), builds channel / multistep weights and calls the loss object.  Under
-    spatial parallelism the Lp family all-reduces its per-shard sums and the H1 loss gathers the shards.  ``params`` is
+    spatial parallelism both families all-reduce their per-shard sums (CPU tensors of the H1 loss are gathered).  ``params`` is
     the trainer's parameter object (attribute access)."""
 
     def __init__(self, params):
@@ -295,6 +339,8 @@ class LossHandler(nn.Module):
             if isinstance(self.loss_obj, GeometricLpLoss) and self.loss_obj.has_sums(prd, tar):
                 sums = self.loss_obj.sums(prd, tar, self.shard_rows)
                 return self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
+            if isinstance(self.loss_obj, GeometricH1Loss) and prd.is_cuda and tar.is_cuda:
+                return self.loss_obj(prd, tar)      # transforms its own shard, all-reduces [B, 2] sums (no mask: see below)
             prd, tar = self._gather_input(prd), self._gather_input(tar)
         if isinstance(self.loss_obj, GeometricLpLoss):
             self.loss_obj.uniform_chw = self._uniform[bool(self.training)]

@@ -1337,6 +1337,73 @@ def geo_lp_sums(prd, tar, wrow, p):
 
 
 # ----------------------------------------------------------------------------
+# per-degree power of a packed spectrum (csrc/specnorm.hip)
+# ----------------------------------------------------------------------------
+def _degree_power_torch(c, l_off, m_off):
+    """The degree sums in torch float64 on the tensor's device, differentiable by ordinary autograd; the rows with
+    ``l_off + l < m_off + m`` are masked out before they are squared (they may hold anything, NaN included)."""
+    L, M, _ = c.shape
+    l = torch.arange(L, device=c.device).reshape(L, 1) + l_off
+    m = torch.arange(M, device=c.device).reshape(1, M) + m_off
+    w = torch.where(m == 0, 1.0, 2.0).to(torch.float64).expand(L, M)
+    w = torch.where(l >= m, w, torch.zeros_like(w)).unsqueeze(-1)
+    ri = torch.view_as_real(c).to(torch.float64)
+    ri = torch.where((w > 0).unsqueeze(-1), ri, torch.zeros_like(ri))
+    return (w * (ri[..., 0] ** 2 + ri[..., 1] ** 2)).sum(dim=1).t()
+
+
+class _DegreePower(torch.autograd.Function):
+    """[BC, L] float64 degree sums of a packed spectrum [L, M, BC]; one streaming pass each way (mk_degree_power,
+    mk_degree_power_bwd)."""
+
+    @staticmethod
+    def forward(ctx, c, l_off, m_off):
+        L, M, BC = c.shape
+        lib = _lib.load()
+        ws = torch.empty(lib.mk_degree_power_workspace(L, M, BC), dtype=torch.float64, device=c.device)
+        out = torch.empty(L, BC, dtype=torch.float64, device=c.device)
+        _lib.check(lib.mk_degree_power(c.data_ptr(), ws.data_ptr(), out.data_ptr(), L, M, BC, l_off, m_off, _stream()),
+                   "mk_degree_power")
+        ctx.save_for_backward(c)
+        ctx.offs = (l_off, m_off)
+        return out.t()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        c, = ctx.saved_tensors
+        L, M, BC = c.shape
+        gp = g.t().to(torch.float64).contiguous()        # [L, BC], as the kernel wrote P
+        gc = torch.empty_like(c)
+        _lib.check(_lib.load().mk_degree_power_bwd(c.data_ptr(), gp.data_ptr(), gc.data_ptr(), L, M, BC, *ctx.offs, _stream()),
+                   "mk_degree_power_bwd")
+        return gc, None, None
+
+
+def degree_power(c_packed, l_off=0, m_off=0):
+    """Per-degree power of a packed spectrum ``[L_loc, M_loc, BC]`` complex64 (``forward_packed`` of the transforms),
+    ``[BC, L_loc]`` float64: ``P[bc, l] = sum_m w(m_off + m) |c[l, m, bc]| ** 2`` with ``w(0) = 1`` and ``w(m > 0) = 2``
+    (a real field's orders ``-m`` counted with ``m``).  ``l_off`` / ``m_off`` are the shard's global offsets; the rows with
+    ``l_off + l < m_off + m``, which the Legendre kernels leave unwritten, are never read.  The sums add up over ``m`` shards
+    and concatenate over ``l`` shards.
+
+    CUDA tensors: one streaming HIP pass plus a fixed-order finalize (``mk_degree_power``; bitwise repeatable, capturable)
+    and one streaming pass for the gradient (``mk_degree_power_bwd``: ``2 w gP c``, exact zeros in the empty triangle,
+    handed to the transform's backward as it is).  CPU tensors: the same sums in torch float64, differentiated by ordinary
+    autograd."""
+    if c_packed.dim() != 3 or c_packed.dtype != torch.complex64:
+        raise ValueError(f"degree_power: expected a complex64 spectrum [L, M, BC], got {c_packed.dtype} {tuple(c_packed.shape)}")
+    if min(c_packed.shape) < 1:
+        raise ValueError(f"degree_power: empty spectrum {tuple(c_packed.shape)}")
+    l_off, m_off = int(l_off), int(m_off)
+    if l_off < 0 or m_off < 0:
+        raise ValueError(f"degree_power: offsets must not be negative, got l_off={l_off}, m_off={m_off}")
+    if not c_packed.is_cuda:
+        return _degree_power_torch(c_packed, l_off, m_off)
+    return _DegreePower.apply(c_packed.contiguous(), l_off, m_off)
+
+
+# ----------------------------------------------------------------------------
 # input assembly of the step wrappers (csrc/preproc.hip)
 # ----------------------------------------------------------------------------
 def _ptr(t):
