@@ -146,6 +146,13 @@ int mk_irfft_pm(const float* xf, void* x, int x_dtype, const float* twiddles, in
 int mk_irfft_sums(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon, int mmax,
                   float scale0, float scale_m, float scale_h, int xf_layout, int chans, int chans_per_peer, double* rowsums,
                   void* stream);
+/* mk_irfft_sums with statistics that are float64 throughout and independent of scheduling: every latitude's share goes to
+ * workspace[nlat][bc][2] (doubles, need not be zeroed) and a second launch adds the latitudes in a fixed order into
+ * rowsums (+=, zeroed by the caller).  mk_irfft_sums itself adds each latitude's share rounded to fp32 with one atomic
+ * (reproducible too, accurate to about 2^-24); the planar InverseRealFFT2.inverse_packed uses this entry. */
+int mk_irfft_sums_ws(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon, int mmax,
+                     float scale0, float scale_m, float scale_h, int xf_layout, int chans, int chans_per_peer, double* rowsums,
+                     double* workspace, void* stream);
 /* The same inverse transform with a companion field added in the store epilogue under a per-row affine map:
  *   x[r] = irfft(xf)[r] + affine[r][0] * z[r] + affine[r][1]     z, x: [bc][nlat][nlon] in x_dtype; affine fp32 [bc][2]
  * -- a skip connection synthesised from the (channel-mixed) spectrum plus the apply pass of the instance norm of z
@@ -153,6 +160,26 @@ int mk_irfft_sums(const float* xf, void* x, int x_dtype, const float* twiddles, 
 int mk_irfft_affine_add(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon,
                         int mmax, float scale0, float scale_m, float scale_h, int xf_layout, const void* z,
                         const float* affine, void* stream);
+
+/* ---- latitude DFT of the planar transform -------------------------------------------------------
+ * RealFFT2 / InverseRealFFT2 (layers.py:219-287, selected by spectral_transform="fft" at sfnonet.py:541-555):
+ * `rfft2(x, norm="ortho")` keeps mmax longitudinal modes and the first ceil(lmax / 2) and last floor(lmax / 2) latitude
+ * frequencies.  The longitudinal part is mk_rfft_ex / mk_irfft_ex with all three scales 1 / sqrt(nlon) and xf_layout = 1;
+ * the latitude part is a dense complex matrix, the same for every mode:
+ *   W[l][k] = exp(-2 pi i f_l k / nlat) / sqrt(nlat),   f_l = l for l < ceil(lmax / 2), else nlat - lmax + l.
+ * mk_latdft_table (host, float64 rounded once to fp32; the angle from f_l * k reduced modulo nlat in integers) writes
+ * mk_latdft_table_len(nlat, lmax) floats: cos [lmax][KP], sin [lmax][KP] (W = cos - i sin), then the transposes
+ * cos [nlat][LP], sin [nlat][LP] for the inverse; KP / LP = nlat / lmax rounded up to 4, zero padded.
+ * Needs nlat >= 2, 2 <= lmax <= nlat (the length query returns 0 otherwise). */
+long long mk_latdft_table_len(int nlat, int lmax);
+int mk_latdft_table(int nlat, int lmax, float* out);
+/* fwd: c[l][j]  = sum_k W[l][k] xf[k][j]            xf complex64 [nlat][ncols], c complex64 [lmax][ncols]
+ * inv: xf[k][j] = sum_l conj(W[l][k]) c[l][j]       ncols = mmax_loc * bc; only the kept frequencies are contracted
+ * (the zero padding between the high and the low modes of InverseRealFFT2.forward is implicit).  Each is the adjoint
+ * (backward) of the other.  bf16x3 engine (fp32-accurate), no atomics; `table` (device copy of mk_latdft_table's
+ * output) 16-byte aligned, 33 * 2 * ncols * 4 < 2^31. */
+int mk_latdft_fwd(const float* xf, const float* table, float* c, int nlat, int lmax, long long ncols, void* stream);
+int mk_latdft_inv(const float* c, const float* table, float* xf, int nlat, int lmax, long long ncols, void* stream);
 
 /* ---- spectral filter contraction (K5) ---------------------------------- */
 /* y[l][m][b][o] = sum_i x[l][m][b][i] * w[l][i][o]  (complex), for global m <= l.

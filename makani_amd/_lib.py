@@ -42,10 +42,16 @@ SIGNATURES = {
     "mk_irfft_pm": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int, _vp]),
     "mk_irfft_sums": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int,
                                _c_int, _vp, _vp]),
+    "mk_irfft_sums_ws": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_int, _c_int,
+                                  _c_int, _vp, _vp, _vp]),
     "mk_irfft_affine_add": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _c_float, _c_int,
                                      _vp, _vp, _vp]),
     "mk_legendre_fwd_x3_ex": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "mk_legendre_inv_x3_ex": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "mk_latdft_table_len": (ctypes.c_longlong, [_c_int, _c_int]),
+    "mk_latdft_table": (_c_int, [_c_int, _c_int, _vp]),
+    "mk_latdft_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
+    "mk_latdft_inv": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_dhconv_fwd": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),
     "mk_dhconv_dgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),
     "mk_dhconv_wgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),

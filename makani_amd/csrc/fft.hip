@@ -35,6 +35,7 @@ struct XfLayout {
 // What only the inverse transform takes besides its layout; at most one of the two is set.
 struct IrfftExtras {
     double* rowsums = nullptr;        // mk_irfft_sums: per-row (sum, sum of squares) accumulators of the output
+    double* sumws = nullptr;          // mk_irfft_sums_ws: [nlat][bc][2] per-latitude shares, added up in a fixed order afterwards
     const void* addz = nullptr;       // mk_irfft_affine_add: companion field and its per-row (a, b)
     const float* affine = nullptr;
 };
@@ -639,6 +640,41 @@ extern "C" int mk_irfft_sums(const float* xf, void* x, int x_dtype, const float*
         return e;
     return fft_synthesis(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl, {.rowsums = rowsums},
                          (hipStream_t)stream);
+}
+
+// The same with float64 statistics that do not depend on the order in which workgroups finish: every latitude's share of a
+// row's sums goes to workspace[k][r][2] (2 * bc * nlat doubles, need not be zeroed) and a second kernel adds the latitudes in
+// a fixed order into rowsums.  Sums of the stored values and of their exact squares, float64 from the first add.
+namespace {
+// one wave per accumulator: lane l adds the latitudes l, l + 64, ... in ascending order, then a fixed butterfly over the lanes
+// (a single thread walking all latitudes took 59 us at 240 latitudes: a chain of dependent loads)
+__global__ __launch_bounds__(64) void irfft_sums_reduce_kernel(const double* __restrict__ ws, double* __restrict__ rowsums, int n2,
+                                                               int K) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    double s = 0.0;
+    for (int k = lane; k < K; k += 64) s += ws[(size_t)k * n2 + i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) rowsums[i] += s;
+}
+}  // namespace
+
+extern "C" int mk_irfft_sums_ws(const float* xf, void* x, int x_dtype, const float* twiddles, int bc, int nlat, int nlon, int mmax,
+                                float scale0, float scale_m, float scale_h, int xf_layout, int chans, int chans_per_peer,
+                                double* rowsums, double* workspace, void* stream) {
+    MK_REQUIRE(rowsums != nullptr && workspace != nullptr, "null pointer");
+    MK_REQUIRE(fft_split_applies(nlon, mmax), "row statistics come from the split kernels only");
+    XfLayout xl;
+    if (int e = chans_per_peer > 0 ? xf_peer_major(bc, nlat, nlon, mmax, chans, chans_per_peer, xl)
+                                   : xf_plain(xf_layout, nlat, mmax, xl))
+        return e;
+    if (int e = fft_synthesis(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl,
+                              {.rowsums = rowsums, .sumws = workspace}, (hipStream_t)stream))
+        return e;
+    hipLaunchKernelGGL(irfft_sums_reduce_kernel, dim3((unsigned)(2 * bc)), dim3(64), 0, (hipStream_t)stream,
+                       (const double*)workspace, rowsums, 2 * bc, nlat);
+    MK_LAUNCH_CHECK();
+    return 0;
 }
 
 // Inverse transform whose store epilogue adds a companion field under a per-row affine map:

@@ -49,7 +49,7 @@ template <> __device__ __forceinline__ float as_stored<__hip_bfloat16>(float v) 
 // their sum and sum of squares, taken on the values as stored, go to red[2 sr], red[2 sr + 1] -- the row statistics of the
 // instance norm that reads the field next, for free while the row is in registers.
 template <bool SUMS = false, typename TOut = float>
-__device__ __forceinline__ void split_passes(float2* lds, int tid, int S, const float2 (&tw15)[15], float* red = nullptr) {
+__device__ __forceinline__ void split_passes(float2* lds, int tid, int S, const float2 (&tw15)[15], double* red = nullptr) {
     const int sr = tid >> 4, j = tid & 15;
     float2* base = lds + sub_base(sr, S);
     if (j < 15) {
@@ -70,12 +70,13 @@ __device__ __forceinline__ void split_passes(float2* lds, int tid, int S, const 
 #pragma unroll
     for (int r = 0; r < 15; ++r) base[j + 17 * r] = u[r];
     if constexpr (SUMS) {
-        float s1 = 0.f, s2 = 0.f;
+        // float64 from the first add: products of stored values are exact in it, so the statistics carry no fp32 rounding
+        double s1 = 0.0, s2 = 0.0;
 #pragma unroll
         for (int r = 0; r < 15; ++r) {
-            const float a = as_stored<TOut>(u[r].x), b = as_stored<TOut>(u[r].y);
+            const double a = (double)as_stored<TOut>(u[r].x), b = (double)as_stored<TOut>(u[r].y);
             s1 += a - b;
-            s2 = fmaf(a, a, fmaf(b, b, s2));
+            s2 = fma(a, a, fma(b, b, s2));
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) {      // the 16 lanes of the sub-row
@@ -302,10 +303,10 @@ __global__ __launch_bounds__(STHREADS, WIDE ? 3 : 5) void irfft_split_kernel(con
                                                                const float2* __restrict__ tw, int BC, int K, int M,
                                                                float scale0, float scale_m, float scale_h, XfLayout xl,
                                                                double* __restrict__ rowsums, const TOut* __restrict__ addz,
-                                                               const float* __restrict__ affine) {
+                                                               const float* __restrict__ affine, double* __restrict__ sumws) {
     constexpr int N = 480 * S, G = SNSUB / S, HH = N / 2;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
-    float* red = reinterpret_cast<float*>(lds + SLDS_F2);      // [24 sub-rows][sum, sum of squares] (rowsums only)
+    double* red = reinterpret_cast<double*>(lds + SLDS_F2);    // [24 sub-rows][sum, sum of squares] (rowsums only)
     const int tid = threadIdx.x;
     const int ntile = (BC + G - 1) / G;
     const int total = ntile * K;
@@ -434,10 +435,15 @@ __global__ __launch_bounds__(STHREADS, WIDE ? 3 : 5) void irfft_split_kernel(con
     if (SUMS && tl < 2 * G) {      // one fp64 atomic per (channel, statistic) and tile: the row's share of the field sums
         const int gch = tl >> 1, t = tl & 1;
         if (bc0 + gch < BC) {
-            float v = 0.f;
+            double v = 0.0;
 #pragma unroll
             for (int sq = 0; sq < S; ++sq) v += red[2 * (gch * S + sq) + t];
-            atomicAdd(&rowsums[2 * (size_t)(bc0 + gch) + t], (double)v);
+            // with a workspace (mk_irfft_sums_ws) the latitude's share is stored as it is and a second kernel adds the latitudes
+            // in a fixed order; without one it goes into the accumulator rounded to fp32: fp32 values add up without rounding in
+            // float64, whatever order the atomics arrive in, as long as the shares of a row (up to 721 latitudes) lie within about
+            // 19 binary orders of magnitude of each other -- arbitrary float64 values do not
+            if (sumws != nullptr) sumws[2 * ((size_t)k * BC + bc0 + gch) + t] = v;
+            else atomicAdd(&rowsums[2 * (size_t)(bc0 + gch) + t], (double)(float)v);
         }
     }
 
@@ -543,10 +549,10 @@ void launch_irfft_split(const float* xf, void* x, int x_dtype, const float* tw, 
                         float sm, float sh, const XfLayout& xl, const IrfftExtras& ex, bool wide, hipStream_t st) {
     constexpr int G = SNSUB / S;
     const dim3 grid(split_grid(mk::ceil_div(bc, G) * (long long)nlat));
-    const size_t lds = sizeof(float2) * SLDS_F2 + 2 * SNSUB * sizeof(float);
+    const size_t lds = sizeof(float2) * SLDS_F2 + 2 * SNSUB * sizeof(double);
 #define MK_IRFFT_LAUNCH(T, WIDE, SUMS, ADD)                                                                            \
     hipLaunchKernelGGL((irfft_split_kernel<S, T, WIDE, SUMS, ADD>), grid, dim3(STHREADS), lds, st, (const float2*)xf,  \
-                       (T*)x, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, xl, ex.rowsums, (const T*)ex.addz, ex.affine)
+                       (T*)x, (const float2*)tw, bc, nlat, mmax, s0, sm, sh, xl, ex.rowsums, (const T*)ex.addz, ex.affine, ex.sumws)
 #define MK_IRFFT_PICK(T)                                                                                               \
     if (ex.addz) MK_IRFFT_LAUNCH(T, false, false, true);                                                               \
     else if (ex.rowsums && wide) MK_IRFFT_LAUNCH(T, true, true, false);                                                \

@@ -216,6 +216,39 @@ struct RowStager {
     }
 };
 
+// Latitude-DFT table as the A operand: a 128-row tile carries 64 frequencies, per wave-row band the cosine rows of 32
+// frequencies (tile rows 64 wr + [0, 32): the accumulators a = 0) and the sine rows of the same 32 (64 wr + [32, 64): a = 1),
+// so both products a complex output needs end up in one lane (EPI 5 / 6).  Cosine row f of the tile at base[f * ld + k], its
+// sine row `part` floats behind; rows < rows (frequencies), k < kvalid (a multiple of 4, rows zero padded to it).
+struct DftStager {
+    const float* base;
+    long long ld, part;
+    int rows, kvalid;
+    typedef float4 Regs[4];
+    static __device__ __forceinline__ int row_off(int r) { return plain_off(r); }
+    __device__ __forceinline__ void gload(int kt, Regs& r, int tid) const {
+        const __amdgpu_buffer_rsrc_t rs = x3_rsrc(base);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int t = tid + q * XT, row = (t >> 6) * 16 + quad_row(t & 63), k = kt * XK + (t & 3) * 8;
+            const int f = ((row >> 6) << 5) + (row & 31), sine = (row >> 5) & 1;
+            const unsigned off = (unsigned)((sine * part + (long long)f * ld + k) * 4);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                r[2 * q + h] = x3_load16(rs, (f < rows && k + 4 * h < kvalid) ? off + 16 * h : X3_OOB);
+        }
+    }
+    __device__ __forceinline__ void sstore(const Regs& r, char* img, int tid) const {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int t = tid + q * XT, row = (t >> 6) * 16 + quad_row(t & 63);
+            const int f = ((row >> 6) << 5) + (row & 31);
+            const float v[8] = {r[2 * q].x, r[2 * q].y, r[2 * q].z, r[2 * q].w, r[2 * q + 1].x, r[2 * q + 1].y, r[2 * q + 1].z, r[2 * q + 1].w};
+            if (f < rows) split_store8(v, img + row * XPITCH + (t & 3) * 16);
+        }
+    }
+};
+
 // Complex k-major B operand: element (kk, o) = (base[(kk * ldk + o) * 2], base[... + 1]), kk < kk_hi,
 // o < ovalid.  Complex column o becomes the image rows n = 2o (real part of the product) and 2o + 1
 // (imaginary part); complex row kk the contraction indices k = 2kk, 2kk + 1:
@@ -379,7 +412,9 @@ __device__ __forceinline__ void x3_mfma_step(const char* As, const char* Bs, con
 // EPI: 0 = store (nontemporal), 1 = C += tile (read-modify-write by the one workgroup that owns the tile), 2 = atomic adds
 // (several workgroups contract disjoint k ranges into one tile), 3 = store act(tile + bias[row]) with `rowbias` pointing at the
 // tile's first row (null: no bias) and `act` != 0 the exact (erf) GELU: conv + bias + activation of layers.py:158-206 in one launch,
-// 4 = store complex rows: tile rows (2r, 2r + 1) are (re, im) of complex row r (the spectral channel mix)
+// 4 = store complex rows: tile rows (2r, 2r + 1) are (re, im) of complex row r (the spectral channel mix),
+// 5 / 6 = complex table times interleaved complex columns (DftStager; the latitude DFT and its adjoint): `rvalid` counts the
+// tile's FREQUENCIES (<= 64), output row f of band wr is  acc[0] -+ i acc[1]  combined over the column parities, see below
 template <int DB, class AS, class BS, int EPI = 0>
 __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int kt1, int rvalid, int cvalid, float* cbase,
                                         long long ldc, char* lds, int exp = 0, const float* rowbias = nullptr, int act = 0) {
@@ -412,7 +447,8 @@ __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int
     for (int a = 0; a < 2; ++a) {
         a_off[a] = AS::row_off(wr * 64 + a * 32 + fi) + kg * 16;
         b_off[a] = BS::row_off(wc * 64 + 2 * fi + a) + kg * 16;
-        live[a] = (wr * 64 + a * 32 < rvalid) && (wc * 64 < cvalid);
+        if constexpr (EPI == 5 || EPI == 6) live[a] = (wr * 32 < rvalid) && (wc * 64 < cvalid);   // cosine and sine band live together
+        else live[a] = (wr * 64 + a * 32 < rvalid) && (wc * 64 < cvalid);
     }
 
     typename AS::Regs ra;
@@ -450,6 +486,30 @@ __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int
     }
     // C/D map: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
     const int col = wc * 64 + 2 * fi;
+    if constexpr (EPI == 5 || EPI == 6) {
+        // acc[0][b] = C x_b, acc[1][b] = S x_b with C - i S the table entry, b = 0 / 1 the real / imaginary part of the column:
+        //   EPI 5  (C - i S)(x0 + i x1) = (C x0 + S x1) + i (C x1 - S x0)      EPI 6 (the conjugate)  (C x0 - S x1) + i (C x1 + S x0)
+        // one 8-byte store per complex output, 256 contiguous bytes per wave and row
+        if (col < cvalid) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
+                if (row < rvalid) {
+                    typedef float x3_c2 __attribute__((ext_vector_type(2)));
+                    x3_c2 v2;
+                    if constexpr (EPI == 5) {
+                        v2[0] = acc[0][0][r] + acc[1][1][r];
+                        v2[1] = acc[0][1][r] - acc[1][0][r];
+                    } else {
+                        v2[0] = acc[0][0][r] - acc[1][1][r];
+                        v2[1] = acc[0][1][r] + acc[1][0][r];
+                    }
+                    __builtin_nontemporal_store(v2, reinterpret_cast<x3_c2*>(cbase + (long long)row * ldc + col));
+                }
+            }
+        }
+        return;
+    }
     if constexpr (EPI == 4) {
         // tile rows 2r, 2r + 1 are the real and imaginary part of complex row r (SpecRowStager): registers (r, r + 1) of a lane
         // are (re, im) of one output, the two column parities two adjacent channels -> one 16-byte store per register pair,
@@ -1094,6 +1154,96 @@ extern "C" int mk_spec_mix_wgrad(const float* x, const float* gy, float* gw, int
     hipLaunchKernelGGL(spec_mix_wgrad_x3_kernel, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
     return 0;
+}
+
+
+// ---------------------------------------------------------------------------
+// Latitude DFT of the planar transform (RealFFT2 / InverseRealFFT2, layers.py:219-287), truncated to the kept frequencies:
+//   fwd  c[l][j]  = sum_k W[l][k] xf[k][j]            inv  xf[k][j] = sum_l conj(W[l][k]) c[l][j]
+// W = C - i S from mk_latdft_table (the same matrix for every longitudinal mode), j over the mmax_loc * BC complex64
+// columns of the latitude-major Fourier rows -- a plain GEMM on rows of 2 * ncols floats.  The two are adjoint to each other.
+// One work item per 128-float column tile, its row tiles back to back on one XCD (they share the streamed tile through
+// that XCD's L2, as the convolution kernels do).
+// ---------------------------------------------------------------------------
+namespace {
+struct LatDftParams {
+    const float* src;
+    const float* tab;     // cosine rows [R][ld]; the sine rows `part` floats behind
+    float* dst;
+    long long ld, part;
+    int K, R, N2;         // contraction length, output rows, floats per row
+    int tiles_m, tiles_n;
+};
+
+template <bool INV>
+__global__ __launch_bounds__(XT, 3) void latdft_x3_kernel(LatDftParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    // the "batch" slot of the decoder carries the COLUMN tile: column tiles spread over the XCDs, the row tiles of one column tile
+    // run back to back on one of them
+    const TileId t = decode_block(p.tiles_n, p.tiles_m, 1);
+    if (!t.valid) return;
+    const int r0 = t.tm * (XM / 2), n0 = t.batch * XN;
+    DftStager as;
+    as.base = p.tab + (long long)r0 * p.ld;
+    as.ld = p.ld;
+    as.part = p.part;
+    as.rows = p.R - r0;
+    as.kvalid = (p.K + 3) / 4 * 4;
+    TransStager bs;
+    bs.base = p.src + n0;
+    bs.ldk = p.N2;
+    bs.k_lo = 0;
+    bs.k_hi = p.K;
+    bs.cvalid = p.N2 - n0;
+    x3_tile<X3_DB, DftStager, TransStager, INV ? 6 : 5>(as, bs, 0, (p.K + XK - 1) / XK, p.R - r0, p.N2 - n0,
+                                                        p.dst + (long long)r0 * p.N2 + n0, p.N2, lds_x3);
+}
+}  // namespace
+
+static int latdft_launch(bool inv, const float* src, const float* table, float* dst, int nlat, int lmax, long long ncols,
+                         void* stream) {
+    MK_REQUIRE(src && table && dst, "null pointer");
+    MK_REQUIRE(nlat >= 2 && lmax >= 2 && lmax <= nlat && ncols >= 1, "need nlat >= 2, 2 <= lmax <= nlat and at least one column");
+    MK_REQUIRE(((uintptr_t)table & 15) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 7) == 0,
+               "the table must be 16-byte aligned, the complex operands 8-byte aligned");
+    const long long KP = ((long long)nlat + 3) / 4 * 4, LP = ((long long)lmax + 3) / 4 * 4;
+    MK_REQUIRE(mk_latdft_table_len(nlat, lmax) * 4 < (1LL << 31), "table over 2^31 bytes");
+    // TransStager: 32-bit byte offsets inside one 32-row k-step of the data operand
+    MK_REQUIRE(33LL * 2 * ncols * 4 < (1LL << 31), "operand too large: 33 * 2 * ncols * 4 bytes (one k-step of the data operand) over 2^31");
+    LatDftParams p;
+    p.src = src;
+    p.dst = dst;
+    p.N2 = (int)(2 * ncols);
+    if (!inv) {
+        p.tab = table;
+        p.ld = KP;
+        p.part = (long long)lmax * KP;
+        p.K = nlat;
+        p.R = lmax;
+    } else {
+        p.tab = table + 2 * (long long)lmax * KP;
+        p.ld = LP;
+        p.part = (long long)nlat * LP;
+        p.K = lmax;
+        p.R = nlat;
+    }
+    p.tiles_m = mk::ceil_div(p.R, XM / 2);
+    p.tiles_n = mk::ceil_div(p.N2, XN);
+    const long long nblk = grid_blocks(p.tiles_n, p.tiles_m, 1);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    const dim3 grid((unsigned)nblk), blk(XT);
+    if (inv) hipLaunchKernelGGL(latdft_x3_kernel<true>, grid, blk, X3_LDS, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(latdft_x3_kernel<false>, grid, blk, X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mk_latdft_fwd(const float* xf, const float* table, float* c, int nlat, int lmax, long long ncols, void* stream) {
+    return latdft_launch(false, xf, table, c, nlat, lmax, ncols, stream);
+}
+
+extern "C" int mk_latdft_inv(const float* c, const float* table, float* xf, int nlat, int lmax, long long ncols, void* stream) {
+    return latdft_launch(true, c, table, xf, nlat, lmax, ncols, stream);
 }
 
 

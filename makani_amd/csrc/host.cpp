@@ -162,3 +162,39 @@ extern "C" int mk_fft_twiddles(int nlon, float* out) {
     }
     return 0;
 }
+
+// ---- latitude DFT of the planar transform (RealFFT2 / InverseRealFFT2) ----
+// Kept frequencies of a transform truncated to lmax rows: the first ceil(lmax / 2) and the last floor(lmax / 2) rows of
+// the full DFT (layers.py:219-250: `cat(y[:lmax_high], y[-lmax_low:])`).
+static inline int latdft_freq(int nlat, int lmax, int l) { return l < (lmax + 1) / 2 ? l : nlat - lmax + l; }
+static inline long long latdft_pad4(int n) { return ((long long)n + 3) / 4 * 4; }
+
+extern "C" long long mk_latdft_table_len(int nlat, int lmax) {
+    if (nlat < 2 || lmax < 2 || lmax > nlat) return 0;
+    return 2 * (long long)lmax * latdft_pad4(nlat) + 2 * (long long)nlat * latdft_pad4(lmax);
+}
+
+extern "C" int mk_latdft_table(int nlat, int lmax, float* out) {
+    MK_REQUIRE(out != nullptr, "null pointer");
+    MK_REQUIRE(nlat >= 2 && lmax >= 2 && lmax <= nlat, "need nlat >= 2 and 2 <= lmax <= nlat");
+    const long long KP = latdft_pad4(nlat), LP = latdft_pad4(lmax);
+    std::memset(out, 0, sizeof(float) * (size_t)mk_latdft_table_len(nlat, lmax));
+    float* fc = out;                           // analysis: cos [lmax][KP], sin [lmax][KP]
+    float* fs = fc + (long long)lmax * KP;
+    float* ic = fs + (long long)lmax * KP;     // synthesis (the transposes): cos [nlat][LP], sin [nlat][LP]
+    float* is = ic + (long long)nlat * LP;
+    const double norm = 1.0 / std::sqrt((double)nlat);
+    for (int l = 0; l < lmax; ++l) {
+        const long long f = latdft_freq(nlat, lmax, l);
+        for (int k = 0; k < nlat; ++k) {
+            // the angle from f * k reduced modulo nlat in integers: no float64 cancellation at large f * k
+            const double a = 2.0 * M_PI * (double)((f * k) % nlat) / (double)nlat;
+            const float c = (float)(std::cos(a) * norm), s = (float)(std::sin(a) * norm);
+            fc[l * KP + k] = c;
+            fs[l * KP + k] = s;
+            ic[k * LP + l] = c;
+            is[k * LP + l] = s;
+        }
+    }
+    return 0;
+}

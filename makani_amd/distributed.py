@@ -295,24 +295,45 @@ class _DistFFT2Base(nn.Module):
         self.lon_shapes = compute_split_shapes(self.nlon, self.comm_size_w)
         self.l_shapes = compute_split_shapes(self.lmax, self.comm_size_h)
         self.m_shapes = compute_split_shapes(self.mmax, self.comm_size_w)
+        self._hip_sizes = nlon % 2 == 0 and nlon >= 2 and self.lmax >= 2 and nlat >= 2
+        if self._hip_sizes:      # non-persistent: no state_dict keys
+            self.register_buffer("twiddles", ops.fft_twiddles(nlon), persistent=False)
+            self.register_buffer("dft_table", ops.latdft_table(nlat, self.lmax), persistent=False)
+
+    def _hip(self, x):
+        """The local transforms run on the HIP kernels: a 4-D CUDA tensor next to CUDA buffers, not switched off (CPU ranks keep torch)."""
+        from .layers import planar_fft_hip
+        return self._hip_sizes and x.is_cuda and x.dim() == 4 and self.dft_table.is_cuda and planar_fft_hip()
 
 
 class DistributedRealFFT2(_DistFFT2Base):
     """``mpu/layers.py:38-100``: x [B, C, H/h, W/w] real -> [B, C, lmax/h, mmax/w] complex, ``rfft2(norm="ortho")`` with the
-    two axes made local one after the other by channel <-> axis transposes (one packed all-to-all each; the local FFTs are
-    torch.fft -- the planar transform is not on the SFNO hot path)."""
+    two axes made local one after the other by channel <-> axis transposes (one packed all-to-all each).  The two local
+    transforms run on the HIP real FFT and the MFMA latitude DFT for CUDA tensors (``_hip``), on torch.fft otherwise."""
 
     def forward(self, x):
         num_chans = x.shape[1]
+        hip = self._hip(x) and x.dtype in (torch.float32, torch.bfloat16)
         if self.comm_size_w > 1:                                              # w local, channels split
             x = distributed_transpose_azimuth.apply(x, (1, -1), self.lon_shapes)
-        x = torch.fft.rfft(x, n=self.nlon, dim=-1, norm="ortho")[..., :self.mmax].contiguous()
+        if hip:
+            B, Cw, K = x.shape[0], x.shape[1], x.shape[2]
+            xf = ops.rfft(x.reshape(B * Cw, K, self.nlon).contiguous(), self.twiddles, self.mmax, True,
+                          scale=1.0 / math.sqrt(self.nlon))                   # [K_loc, M, B C_w]
+            x = ops.spec_unpack(xf, self.mmax, 0).view(B, Cw, K, self.mmax)
+        else:
+            x = torch.fft.rfft(x, n=self.nlon, dim=-1, norm="ortho")[..., :self.mmax].contiguous()
         if self.comm_size_w > 1:                                              # m split, channels local
             x = distributed_transpose_azimuth.apply(x, (-1, 1), compute_split_shapes(num_chans, self.comm_size_w))
         if self.comm_size_h > 1:                                              # h local, channels split
             x = distributed_transpose_polar.apply(x, (1, -2), self.lat_shapes)
-        x = torch.fft.fft(x, n=self.nlat, dim=-2, norm="ortho")
-        x = torch.cat([x[..., :self.lmax_high, :], x[..., -self.lmax_low:, :]], dim=-2)
+        if hip:
+            B, Ch, Mloc = x.shape[0], x.shape[1], x.shape[3]
+            xf = ops.spec_pack(x.reshape(B * Ch, self.nlat, Mloc).contiguous(), Mloc, 0)      # [K, M_loc, B C_h]
+            x = ops.spec_unpack(ops.lat_dft(xf, self.dft_table, self.lmax), Mloc, 0).view(B, Ch, self.lmax, Mloc)
+        else:
+            x = torch.fft.fft(x, n=self.nlat, dim=-2, norm="ortho")
+            x = torch.cat([x[..., :self.lmax_high, :], x[..., -self.lmax_low:, :]], dim=-2)
         if self.comm_size_h > 1:                                              # l split, channels local
             x = distributed_transpose_polar.apply(x, (-2, 1), compute_split_shapes(num_chans, self.comm_size_h))
         return x
@@ -324,17 +345,29 @@ class DistributedInverseRealFFT2(_DistFFT2Base):
 
     def forward(self, x):
         num_chans = x.shape[1]
+        hip = self._hip(x) and x.dtype == torch.complex64
         if self.comm_size_h > 1:                                              # l local, channels split
             x = distributed_transpose_polar.apply(x, (1, -2), self.l_shapes)
-        if self.lmax < self.nlat:
-            xh, xl = x[..., :self.lmax_high, :], x[..., -self.lmax_low:, :]
-            x = torch.cat([torch.nn.functional.pad(xh, (0, 0, 0, self.nlat - self.lmax)), xl], dim=-2)
-        x = torch.fft.ifft(x, n=self.nlat, dim=-2, norm="ortho")
+        if hip:
+            B, Ch, Mloc = x.shape[0], x.shape[1], x.shape[3]
+            c = ops.spec_pack(x.reshape(B * Ch, self.lmax, Mloc).contiguous(), Mloc, 0)       # [L, M_loc, B C_h]
+            x = ops.spec_unpack(ops.lat_idft(c, self.dft_table, self.nlat), Mloc, 0).view(B, Ch, self.nlat, Mloc)
+        else:
+            if self.lmax < self.nlat:
+                xh, xl = x[..., :self.lmax_high, :], x[..., -self.lmax_low:, :]
+                x = torch.cat([torch.nn.functional.pad(xh, (0, 0, 0, self.nlat - self.lmax)), xl], dim=-2)
+            x = torch.fft.ifft(x, n=self.nlat, dim=-2, norm="ortho")
         if self.comm_size_h > 1:                                              # h split, channels local
             x = distributed_transpose_polar.apply(x, (-2, 1), compute_split_shapes(num_chans, self.comm_size_h))
         if self.comm_size_w > 1:                                              # m local, channels split
             x = distributed_transpose_azimuth.apply(x, (1, -1), self.m_shapes)
-        x = torch.fft.irfft(x, n=self.nlon, dim=-1, norm="ortho")
+        if hip:
+            B, Cw, K = x.shape[0], x.shape[1], x.shape[2]
+            xf = ops.spec_pack(x.reshape(B * Cw, K, self.mmax).contiguous(), self.mmax, 0)    # [K_loc, M, B C_w]
+            x = ops.irfft(xf, self.twiddles, self.nlon, torch.float32, True, scale=1.0 / math.sqrt(self.nlon))
+            x = x.view(B, Cw, K, self.nlon)
+        else:
+            x = torch.fft.irfft(x, n=self.nlon, dim=-1, norm="ortho")
         if self.comm_size_w > 1:                                              # w split, channels local
             x = distributed_transpose_azimuth.apply(x, (-1, 1), compute_split_shapes(num_chans, self.comm_size_w))
         return x

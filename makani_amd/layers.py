@@ -803,8 +803,26 @@ class MLP(nn.Module):
         return self._run(x, skip_last_bias, want_row_sums)
 
 
-class RealFFT2(nn.Module):
-    """layers.py:219-250 -- the duck-typed planar transform (torch.fft; not on the SFNO path)."""
+# The HIP path is opt-in: the rule for the default is "not slower than the torch formulation at both grids of
+# tools/fft2_bench.py", and at 384 x 240 x 480 `RealFFT2.forward` on fp32 rows is 11 % slower (every other row is faster, the
+# full grid 5.6-9.7x): DESIGN section 19.
+PLANAR_FFT_DEFAULT = "torch"
+
+
+def planar_fft_hip():
+    """The planar transforms run on this package's kernels: ``MK_PLANAR_FFT`` (``hip`` | ``torch``, read at call time), and
+    the bf16x3 engine selected -- ``MK_SPECTRAL_GEMM=f32`` has no fp32-MFMA variant of the latitude DFT."""
+    from . import ops
+    mode = os.environ.get("MK_PLANAR_FFT", PLANAR_FFT_DEFAULT)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"MK_PLANAR_FFT={mode!r} (hip | torch)")
+    return mode == "hip" and ops.SPECTRAL_GEMM == "bf16x3"
+
+
+class _PlanarFFT2Base(nn.Module):
+    """Sizes of layers.py:219-287 plus what the HIP path needs: the latitude DFT table and the FFT twiddles as non-persistent
+    buffers (no ``state_dict`` keys).  Sizes the kernels do not take (odd ``nlon``, ``lmax < 2``) get no buffers and stay on
+    the torch formulation."""
 
     def __init__(self, nlat, nlon, lmax=None, mmax=None):
         super().__init__()
@@ -814,27 +832,71 @@ class RealFFT2(nn.Module):
         self.truncate = not ((self.lmax == self.nlat) and (self.mmax == (self.nlon // 2 + 1)))
         self.lmax_high = math.ceil(self.lmax / 2)
         self.lmax_low = math.floor(self.lmax / 2)
+        self._hip_sizes = nlon % 2 == 0 and nlon >= 2 and self.lmax >= 2 and nlat >= 2
+        if self._hip_sizes:
+            from . import ops
+            self.register_buffer("twiddles", ops.fft_twiddles(nlon), persistent=False)
+            self.register_buffer("dft_table", ops.latdft_table(nlat, self.lmax), persistent=False)
 
-    def forward(self, x):
+    def hip_ready(self, x):
+        """The HIP path takes ``x``: a CUDA tensor next to CUDA buffers, sizes the kernels are built for, not switched off."""
+        return self._hip_sizes and x.is_cuda and self.dft_table.is_cuda and planar_fft_hip()
+
+    @staticmethod
+    def _flatten(x, inner):
+        lead = x.shape[:-2]
+        bc = 1
+        for s in lead:
+            bc *= s
+        return lead, x.reshape(bc, *inner)
+
+
+class RealFFT2(_PlanarFFT2Base):
+    """layers.py:219-250 -- the planar transform of ``spectral_transform="fft"``: real ``[..., nlat, nlon]`` -> complex
+    ``[..., lmax, mmax]`` = ``rfft2(norm="ortho")`` truncated to the first ``ceil(lmax / 2)`` / last ``floor(lmax / 2)``
+    latitude frequencies.  With ``MK_PLANAR_FFT=hip`` CUDA fp32 / bf16 inputs run on the HIP real FFT (``mk_rfft_ex``, scale ``1 / sqrt(nlon)``) and the
+    MFMA latitude DFT (``mk_latdft_fwd``); everything else on the torch formulation (``_forward_torch``)."""
+
+    def forward_packed(self, x3):
+        """x3 [BC, nlat, nlon] (fp32 or bf16, contiguous) -> private spectrum [lmax, mmax, BC] (every entry is data: no triangle)."""
+        from . import ops
+        xf = ops.rfft(x3, self.twiddles, self.mmax, True, scale=1.0 / math.sqrt(self.nlon))
+        return ops.lat_dft(xf, self.dft_table, self.lmax)
+
+    def _forward_torch(self, x):
         y = torch.fft.rfft2(x, s=(self.nlat, self.nlon), dim=(-2, -1), norm="ortho")
         if self.truncate:
             y = torch.cat((y[..., : self.lmax_high, : self.mmax], y[..., -self.lmax_low:, : self.mmax]), dim=-2)
         return y
 
-
-class InverseRealFFT2(nn.Module):
-    """layers.py:253-287."""
-
-    def __init__(self, nlat, nlon, lmax=None, mmax=None):
-        super().__init__()
-        self.nlat, self.nlon = nlat, nlon
-        self.lmax = min(lmax or self.nlat, self.nlat)
-        self.mmax = min(mmax or self.nlon // 2 + 1, self.nlon // 2 + 1)
-        self.truncate = not ((self.lmax == self.nlat) and (self.mmax == (self.nlon // 2 + 1)))
-        self.lmax_high = math.ceil(self.lmax / 2)
-        self.lmax_low = math.floor(self.lmax / 2)
-
     def forward(self, x):
+        if (x.dim() < 2 or x.dtype not in (torch.float32, torch.bfloat16) or tuple(x.shape[-2:]) != (self.nlat, self.nlon)
+                or x.numel() == 0 or not self.hip_ready(x)):
+            return self._forward_torch(x)
+        from . import ops
+        lead, x3 = self._flatten(x.contiguous(), (self.nlat, self.nlon))
+        c = ops.spec_unpack(self.forward_packed(x3), self.mmax, 0)       # degree offset mmax: dense, no triangle zeroed
+        return c.reshape(*lead, self.lmax, self.mmax)
+
+
+class InverseRealFFT2(_PlanarFFT2Base):
+    """layers.py:253-287: complex ``[..., lmax, mmax]`` -> real ``[..., nlat, nlon]``, the zero padding between the high and
+    the low latitude modes implicit in the kernel (``mk_latdft_inv``), then ``mk_irfft_ex`` with scale ``1 / sqrt(nlon)``."""
+
+    def inverse_packed(self, c, out_dtype=torch.float32, want_row_sums=False):
+        """private spectrum [lmax, mmax, BC] -> x [BC, nlat, nlon] (fp32, or bf16 rows straight from the FFT kernel); with
+        ``want_row_sums`` (and a length the split kernels serve) also the fp64 ``[BC, 2]`` sums / sums of squares of the rows of x,
+        else None in their place -- the conventions of ``InverseRealSHT.inverse_packed``."""
+        from . import ops
+        s = 1.0 / math.sqrt(self.nlon)
+        xf = ops.lat_idft(c, self.dft_table, self.nlat)
+        if want_row_sums:
+            if ops.irfft_sums_supported(self.nlon, self.mmax) and out_dtype in (torch.float32, torch.bfloat16):
+                return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, True, True, scale=s, exact_sums=True)
+            return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, True, scale=s), None
+        return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, True, scale=s)
+
+    def _forward_torch(self, x):
         xt = x[..., : self.mmax]
         if self.truncate:
             xth = xt[..., : self.lmax_high, :]
@@ -842,3 +904,12 @@ class InverseRealFFT2(nn.Module):
             xthp = F.pad(xth, (0, 0, 0, self.nlat - self.lmax))
             xt = torch.cat([xthp, xtl], dim=-2)
         return torch.fft.irfft2(xt, s=(self.nlat, self.nlon), dim=(-2, -1), norm="ortho")
+
+    def forward(self, x):
+        if (x.dim() < 2 or x.dtype != torch.complex64 or tuple(x.shape[-2:]) != (self.lmax, self.mmax) or x.numel() == 0
+                or not self.hip_ready(x)):
+            return self._forward_torch(x)
+        from . import ops
+        lead, c3 = self._flatten(x.contiguous(), (self.lmax, self.mmax))
+        y = self.inverse_packed(ops.spec_pack(c3, self.mmax, 0))
+        return y.reshape(*lead, self.nlat, self.nlon)

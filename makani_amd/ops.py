@@ -68,6 +68,18 @@ def fft_twiddles(nlon):
     return out
 
 
+def latdft_table(nlat, lmax):
+    """Cosine / sine tables of the truncated latitude DFT of the planar transform (``mk_latdft_table``: the analysis matrix
+    ``[2, lmax, pad4(nlat)]`` followed by its transpose ``[2, nlat, pad4(lmax)]``) as a flat fp32 CPU tensor."""
+    lib = _lib.load()
+    n = lib.mk_latdft_table_len(int(nlat), int(lmax))
+    if n <= 0:
+        raise ValueError(f"latdft_table: need nlat >= 2 and 2 <= lmax <= nlat, got nlat={nlat}, lmax={lmax}")
+    out = torch.empty(n, dtype=torch.float32)
+    _lib.check(lib.mk_latdft_table(int(nlat), int(lmax), out.data_ptr()), "mk_latdft_table")
+    return out
+
+
 # ----------------------------------------------------------------------------
 # raw (non-differentiable) launches
 # ----------------------------------------------------------------------------
@@ -108,16 +120,23 @@ def irfft_sums_supported(nlon, mmax):
     return _fft_split(nlon, mmax) and os.environ.get("MK_IRFFT_SUMS", "1") != "0"
 
 
-def irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor=False, chans=0, cpp=0):
-    """``irfft`` (scales 1, 1, 1) of plain (``[M, K, BC]`` / ``[K, M, BC]``) or peer-major (``cpp`` > 0:
+def irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor=False, chans=0, cpp=0, scale=1.0, exact=False):
+    """``irfft`` (scales 1, 1, 1, or ``scale`` three times) of plain (``[M, K, BC]`` / ``[K, M, BC]``) or peer-major (``cpp`` > 0:
     ``[chans / cpp, K, M, B * cpp]``) Fourier rows -> (x ``[BC, K, nlon]``, fp64 ``[BC, 2]`` sums and sums of squares of its rows)."""
     _need_cuda(xf, twiddles)
     m, k, bc = _xf_dims(xf, kmajor, chans, cpp)
     x = torch.empty(bc, k, nlon, dtype=out_dtype, device=xf.device)
     sums = torch.zeros(bc, 2, dtype=torch.float64, device=xf.device)
+    if exact:
+        # float64 sums of the stored rows, reproducible: per-latitude shares in a workspace, added in a fixed order by a second launch
+        ws = torch.empty(k, bc, 2, dtype=torch.float64, device=xf.device)
+        _lib.check(_lib.load().mk_irfft_sums_ws(xf.data_ptr(), x.data_ptr(), _pw_dtype(x), twiddles.data_ptr(), bc, k, nlon, m,
+                                                scale, scale, scale, int(bool(kmajor)), int(chans), int(cpp), sums.data_ptr(),
+                                                ws.data_ptr(), _stream()), "mk_irfft_sums_ws")
+        return x, sums
     _lib.check(_lib.load().mk_irfft_sums(xf.data_ptr(), x.data_ptr(), _pw_dtype(x), twiddles.data_ptr(), bc, k, nlon, m,
-                                         1.0, 1.0, 1.0, int(bool(kmajor)), int(chans), int(cpp), sums.data_ptr(), _stream()),
-               "mk_irfft_sums")
+                                         scale, scale, scale, int(bool(kmajor)), int(chans), int(cpp), sums.data_ptr(),
+                                         _stream()), "mk_irfft_sums")
     return x, sums
 
 
@@ -267,6 +286,33 @@ def legendre_inv_raw(c, table, nlat, m_off=0, mode=None, kmajor=False):
     else:
         _lib.check(_lib.load().mk_legendre_inv(c.data_ptr(), table.data_ptr(), xf.data_ptr(), bc, nlat, lmax, mloc,
                                                m_off, mg, _stream()), "mk_legendre_inv")
+    return xf
+
+
+def _latdft_check(a, table, nlat, lmax):
+    _need_cuda(a, table)
+    assert a.dim() == 3 and a.is_contiguous() and a.dtype == torch.complex64
+    assert table.dtype == torch.float32 and table.is_contiguous()
+    assert table.numel() == _lib.load().mk_latdft_table_len(int(nlat), int(lmax)), "latitude DFT table does not match the operand"
+
+
+def lat_dft_raw(xf, table, lmax):
+    """Latitude-major Fourier rows xf ``[nlat, M, BC]`` -> private spectrum ``[lmax, M, BC]`` of the planar transform."""
+    nlat, m, bc = xf.shape
+    _latdft_check(xf, table, nlat, lmax)
+    c = torch.empty(lmax, m, bc, dtype=torch.complex64, device=xf.device)
+    _lib.check(_lib.load().mk_latdft_fwd(xf.data_ptr(), table.data_ptr(), c.data_ptr(), nlat, lmax, m * bc, _stream()),
+               "mk_latdft_fwd")
+    return c
+
+
+def lat_idft_raw(c, table, nlat):
+    """Private spectrum ``[lmax, M, BC]`` -> latitude-major Fourier rows ``[nlat, M, BC]`` (the adjoint of ``lat_dft_raw``)."""
+    lmax, m, bc = c.shape
+    _latdft_check(c, table, nlat, lmax)
+    xf = torch.empty(nlat, m, bc, dtype=torch.complex64, device=c.device)
+    _lib.check(_lib.load().mk_latdft_inv(c.data_ptr(), table.data_ptr(), xf.data_ptr(), nlat, lmax, m * bc, _stream()),
+               "mk_latdft_inv")
     return xf
 
 
@@ -694,13 +740,14 @@ def pce_gemm(x3, wimg, m, bias=None, addend=None, aux_in=None, want_pre=False, g
 # ----------------------------------------------------------------------------
 class _RFFT(torch.autograd.Function):
     """x [BC, K, N] -> 2 pi rfft(x, norm="forward")[..., :mmax] (K1) as Fourier rows [mmax, K, BC], [K, mmax, BC] (``kmajor``) or,
-    with ``pm`` = (chans, cpp), peer-major; the adjoint is the inverse launch from the same layout."""
+    with ``pm`` = (chans, cpp), peer-major; the adjoint is the inverse launch from the same layout.  ``scale`` replaces the
+    factor 2 pi / N on every mode (the planar transform passes 1 / sqrt(N))."""
 
     @staticmethod
-    def forward(ctx, x, twiddles, mmax, kmajor=False, pm=None):
+    def forward(ctx, x, twiddles, mmax, kmajor=False, pm=None, scale=None):
         ctx.save_for_backward(twiddles)
-        ctx.cfg = (x.shape[-1], x.dtype, kmajor, pm)
-        s = 2.0 * math.pi / x.shape[-1]
+        ctx.cfg = (x.shape[-1], x.dtype, kmajor, pm, scale)
+        s = 2.0 * math.pi / x.shape[-1] if scale is None else float(scale)
         if pm:
             return rfft_pm_raw(x, twiddles, mmax, s, s, s, *pm)
         return rfft_raw(x, twiddles, mmax, s, s, s, kmajor)
@@ -708,42 +755,47 @@ class _RFFT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gxf):
         (tw,) = ctx.saved_tensors
-        n, dt, kmajor, pm = ctx.cfg
-        s = (2.0 * math.pi / n, math.pi / n, 2.0 * math.pi / n)
+        n, dt, kmajor, pm, scale = ctx.cfg
+        if scale is None:
+            s = (2.0 * math.pi / n, math.pi / n, 2.0 * math.pi / n)
+        else:           # the adjoint of mk_rfft(s, s, s) is mk_irfft(s, s / 2, s)
+            s = (float(scale), 0.5 * float(scale), float(scale))
         if pm:
             gx = irfft_pm_raw(gxf.contiguous(), tw, n, *s, *pm, dt)
         else:
             gx = irfft_raw(gxf.contiguous(), tw, n, *s, dt, kmajor)
-        return gx, None, None, None, None
+        return gx, None, None, None, None, None
 
 
 class _IRFFT(torch.autograd.Function):
-    """Fourier rows (layouts as for ``_RFFT``) -> x [BC, K, nlon] = irfft(xf, n=nlon, norm="forward") (K4)."""
+    """Fourier rows (layouts as for ``_RFFT``) -> x [BC, K, nlon] = irfft(xf, n=nlon, norm="forward") (K4), times ``scale``
+    where one is given (the planar transform passes 1 / sqrt(nlon))."""
 
     @staticmethod
-    def forward(ctx, xf, twiddles, nlon, out_dtype, kmajor=False, want_sums=False, pm=None):
+    def forward(ctx, xf, twiddles, nlon, out_dtype, kmajor=False, want_sums=False, pm=None, scale=None, exact_sums=False):
         ctx.save_for_backward(twiddles)
         chans, cpp = pm or (0, 0)
-        ctx.cfg = (_xf_dims(xf, kmajor, chans, cpp)[0], kmajor, pm)
+        s = 1.0 if scale is None else float(scale)
+        ctx.cfg = (_xf_dims(xf, kmajor, chans, cpp)[0], kmajor, pm, s)
         if want_sums:            # (x, row statistics): the sums are data for the norm's kernel, not a differentiable output
-            x, sums = irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor, chans, cpp)
+            x, sums = irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor, chans, cpp, scale=s, exact=bool(exact_sums))
             ctx.mark_non_differentiable(sums)
             return x, sums
         if pm:
-            return irfft_pm_raw(xf, twiddles, nlon, 1.0, 1.0, 1.0, chans, cpp, out_dtype)
-        return irfft_raw(xf, twiddles, nlon, 1.0, 1.0, 1.0, out_dtype, kmajor)
+            return irfft_pm_raw(xf, twiddles, nlon, s, s, s, chans, cpp, out_dtype)
+        return irfft_raw(xf, twiddles, nlon, s, s, s, out_dtype, kmajor)
 
     @staticmethod
     def backward(ctx, gx, *_):
         (tw,) = ctx.saved_tensors
-        mmax, kmajor, pm = ctx.cfg
+        mmax, kmajor, pm, s = ctx.cfg         # the adjoint of mk_irfft(s, s, s) is mk_rfft(s, 2 s, s)
         if gx.dtype not in (torch.float32, torch.bfloat16):
             gx = gx.float()
         if pm:
-            gxf = rfft_pm_raw(gx.contiguous(), tw, mmax, 1.0, 2.0, 1.0, *pm)
+            gxf = rfft_pm_raw(gx.contiguous(), tw, mmax, s, 2.0 * s, s, *pm)
         else:
-            gxf = rfft_raw(gx.contiguous(), tw, mmax, 1.0, 2.0, 1.0, kmajor)
-        return gxf, None, None, None, None, None, None
+            gxf = rfft_raw(gx.contiguous(), tw, mmax, s, 2.0 * s, s, kmajor)
+        return gxf, None, None, None, None, None, None, None, None
 
 
 class _LegendreFwd(torch.autograd.Function):
@@ -772,6 +824,32 @@ class _LegendreInv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gxf):
         return legendre_fwd_raw(gxf.contiguous(), ctx.table, ctx.lmax, ctx.m_off, kmajor=ctx.kmajor), None, None, None, None
+
+
+class _LatDft(torch.autograd.Function):
+    """xf [nlat, M, BC] -> c [lmax, M, BC]: the truncated latitude DFT of the planar transform; backward = ``mk_latdft_inv``."""
+
+    @staticmethod
+    def forward(ctx, xf, table, lmax):
+        ctx.table, ctx.nlat = table, xf.shape[0]
+        return lat_dft_raw(xf, table, lmax)
+
+    @staticmethod
+    def backward(ctx, gc):
+        return lat_idft_raw(gc.contiguous(), ctx.table, ctx.nlat), None, None
+
+
+class _LatIdft(torch.autograd.Function):
+    """c [lmax, M, BC] -> xf [nlat, M, BC]: the adjoint of ``_LatDft`` (the zero-padded inverse DFT); backward = ``mk_latdft_fwd``."""
+
+    @staticmethod
+    def forward(ctx, c, table, nlat):
+        ctx.table, ctx.lmax = table, c.shape[0]
+        return lat_idft_raw(c, table, nlat)
+
+    @staticmethod
+    def backward(ctx, gxf):
+        return lat_dft_raw(gxf.contiguous(), ctx.table, ctx.lmax), None, None
 
 
 class _SpecPack(torch.autograd.Function):
@@ -893,13 +971,24 @@ def spec_mix(x, w, batch, l_off=0, m_off=0):
     return _SpecMix.apply(x, w, batch, l_off, m_off)
 
 
-def rfft(x, twiddles, mmax, kmajor=False):
-    return _RFFT.apply(x, twiddles, mmax, kmajor)
+def rfft(x, twiddles, mmax, kmajor=False, scale=None):
+    """``scale``: the factor on every mode; None = the SHT's 2 pi / nlon."""
+    return _RFFT.apply(x, twiddles, mmax, kmajor, None, scale)
 
 
-def irfft(xf, twiddles, nlon, out_dtype=torch.float32, kmajor=False, want_sums=False):
-    """``want_sums``: returns (x, fp64 ``[BC, 2]`` row sums / sums of squares of x) -- see ``mk_irfft_sums``."""
-    return _IRFFT.apply(xf, twiddles, nlon, out_dtype, kmajor, want_sums)
+def irfft(xf, twiddles, nlon, out_dtype=torch.float32, kmajor=False, want_sums=False, scale=None, exact_sums=False):
+    """``want_sums``: returns (x, fp64 ``[BC, 2]`` row sums / sums of squares of x) -- see ``mk_irfft_sums``; ``exact_sums``: through
+    ``mk_irfft_sums_ws`` (float64 from the first add, fixed order; one more launch).
+    ``scale``: the factor on every mode; None = 1 (``norm="forward"``)."""
+    return _IRFFT.apply(xf, twiddles, nlon, out_dtype, kmajor, want_sums, None, scale, exact_sums)
+
+
+def lat_dft(xf, table, lmax):
+    return _LatDft.apply(xf, table, lmax)
+
+
+def lat_idft(c, table, nlat):
+    return _LatIdft.apply(c, table, nlat)
 
 
 def rfft_pm(x, twiddles, mmax, chans, cpp):

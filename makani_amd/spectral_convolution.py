@@ -7,8 +7,9 @@ arguments, ``weight`` shape / init / ``is_shared_mp`` / ``sharded_dims_mp`` anno
 When both transforms are this package's HIP transforms and ``operator_type="dhconv"``
 the layer runs fused on the private channels-last spectrum: FFT -> Legendre (MFMA)
 -> dhconv (MFMA) -> Legendre -> FFT, five to seven launches, no layout round trip and no
-``.contiguous()`` copies.  Any other duck-typed transform pair (e.g. ``RealFFT2``) takes
-the generic path through ``get_contract_fun``.
+``.contiguous()`` copies.  The planar pair (``RealFFT2`` / ``InverseRealFFT2`` on their HIP path) runs the
+same way: FFT -> latitude DFT (MFMA) -> dhconv (dense: no triangle) -> latitude DFT -> FFT.  Any other
+duck-typed transform pair takes the generic path through ``get_contract_fun``.
 
 The dhconv weight keeps the reference's logical shape ``[in, out, l]`` (state-dict
 parity) but is *stored* ``[l, in, out]`` (a permuted view), so each degree's
@@ -22,6 +23,7 @@ import torch.nn as nn
 from . import comm, ops
 from .contractions import get_contract_fun
 from .distributed import DistributedInverseRealFFT2, DistributedInverseRealSHT, DistributedRealSHT
+from .layers import InverseRealFFT2, RealFFT2
 from .sht import InverseRealSHT, RealSHT
 
 
@@ -102,6 +104,9 @@ class SpectralConv(nn.Module):
         self._contract = get_contract_fun(self.weight, implementation="factorized", separable=separable,
                                           complex=True, operator_type=operator_type)
         self._fused = _is_hip_pair(forward_transform, inverse_transform) and operator_type == "dhconv" and not separable
+        # the planar pair on the same fused path where its HIP transforms apply (decided per call: MK_PLANAR_FFT, the device)
+        self._planar = (isinstance(forward_transform, RealFFT2) and isinstance(inverse_transform, InverseRealFFT2)
+                        and operator_type == "dhconv" and not separable)
 
         if bias == "constant":
             self.bias = nn.Parameter(torch.zeros(1, self.out_channels, 1, 1))
@@ -133,6 +138,8 @@ class SpectralConv(nn.Module):
     def _forward_fused(self, x, dtype, want_row_sums=False, premix=None, spectrum_residual=False):
         B, C = x.shape[0], x.shape[1]
         ft, it = self.forward_transform, self.inverse_transform
+        # planar spectrum: every (l, m) entry is data -- a degree offset >= mmax switches the kernel's triangle off
+        l_off = self.modes_lon if self._planar else self.l_off
         xin = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
         xin = xin.contiguous()
         if isinstance(ft, DistributedRealSHT):
@@ -151,7 +158,7 @@ class SpectralConv(nn.Module):
         elif self.scale_residual:
             r = self.synthesise(c, B, odt)
             residual = r.view(B, C, r.shape[-2], r.shape[-1]).to(dtype)
-        y = ops.dhconv(c, self._weight_tensor(), B, self.l_off, self.m_off)
+        y = ops.dhconv(c, self._weight_tensor(), B, l_off, self.m_off)
         sums = None
         if want_row_sums:       # the inverse FFT hands over the row statistics of its output (mk_irfft_sums)
             out, sums = it.inverse_packed(y, B, odt, True) if self._distributed else it.inverse_packed(y, odt, True)
@@ -171,7 +178,12 @@ class SpectralConv(nn.Module):
         sums = None
         if premix is not None or spectrum_residual:
             assert self.takes_spectral_mix() and x.is_cuda and x.dim() == 4 and (premix is None or self.scale_residual)
-        if self._fused and x.is_cuda and x.dim() == 4:
+        ft = self.forward_transform
+        # (other dtypes take the generic path below, which casts to fp32 first, as the reference does)
+        fused = self._fused or (self._planar and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
+                                and tuple(x.shape[-2:]) == (ft.nlat, ft.nlon)
+                                and ft.hip_ready(x) and self.inverse_transform.hip_ready(x))
+        if fused and x.is_cuda and x.dim() == 4:
             with torch.autocast(device_type="cuda", enabled=False):
                 x, residual, sums = self._forward_fused(x, dtype, want_row_sums and not hasattr(self, "bias"), premix,
                                                         spectrum_residual)
@@ -251,6 +263,7 @@ class FactorizedSpectralConv(SpectralConv):
         self._contract = get_contract_fun(self.weight, implementation="reconstructed", separable=separable,
                                           complex=complex_weight, operator_type=operator_type)
         self._fused = self._fused and complex_weight
+        self._planar = self._planar and complex_weight
 
     def _weight_tensor(self):
         return self.weight.to_tensor()
