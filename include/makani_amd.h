@@ -221,6 +221,33 @@ int mk_spec_mix_dgrad(const float* gy, const float* w, float* gx, int lloc, int 
 int mk_spec_mix_wgrad(const float* x, const float* gy, float* gw, int lloc, int mloc, int batch,
                       int cin, int cout, int l_off, int m_off, void* stream);
 
+/* ---- complex channel MLP on the spectrum (the non-linear filter, SpectralAttention) -------------
+ * One layer of spectral_convolution.py:367-374 on the private spectrum [L][M][B][C] complex64, rows (m <= l, b) as in dhconv
+ * (entries with l < m are neither read nor written; l_off >= mmax: the dense planar spectrum), bf16x3 engine:
+ *   fwd:   y[l][m][b][o]  = act(sum_i x[l][m][b][i] * w[l * ws][i][o] + bias[o])
+ *   dgrad: gx[l][m][b][i] = (sum_o gy[l][m][b][o] * conj(w[l * ws][i][o])) * mask(a[l][m][b][i])
+ *   wgrad: gw[l][i][o]    = sum_{m<=l, b} conj(x[l][m][b][i]) * gy[l][m][b][o]      (per_degree; without: also summed over l)
+ *   bgrad: gb[o]          = sum_{l, m<=l, b} g[l][m][b][o]
+ * w: complex [cin][cout] panels, one per degree (per_degree = 1: the dhconv layout [L][cin][cout]) or one for all degrees
+ * (per_degree = 0).  bias: complex [cout] or NULL.  act: 0 none, 1 ReLU on the real part (the imaginary part passes), 2 ReLU on
+ * both parts; bias and activation are applied in fp32 on the accumulator.  a: the saved activation OUTPUT of the layer whose
+ * result this layer's input was ([L][M][B][cin], act its mode) or NULL for no mask; a component passes where the same
+ * component of a is > 0 (relu' with relu'(0) = 0), in mode 1 every imaginary component passes.
+ * The shared weight gradient contracts groups of consecutive degrees into partial panels in `workspace`
+ * (mk_spec_cmlp_wgrad_workspace bytes, 16-byte aligned; 0 bytes: not needed) and adds them in ascending order; the bias gradient
+ * sums rows, then degrees, in float64 in a fixed order (`workspace`: mk_spec_cmlp_bgrad_workspace bytes).  Neither uses
+ * atomics: the same bits on every run.  cin, cout even, operands 16-byte aligned, one degree of a field below 2^31 bytes. */
+int mk_spec_cmlp_fwd(const float* x, const float* w, const float* bias, float* y, int lloc, int mloc, int batch, int cin,
+                     int cout, int l_off, int m_off, int per_degree, int act, void* stream);
+int mk_spec_cmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int lloc, int mloc, int batch, int cin,
+                       int cout, int l_off, int m_off, int per_degree, int act, void* stream);
+long long mk_spec_cmlp_wgrad_workspace(int lloc, int cin, int cout, int per_degree);
+int mk_spec_cmlp_wgrad(const float* x, const float* gy, float* gw, void* workspace, int lloc, int mloc, int batch, int cin,
+                       int cout, int l_off, int m_off, int per_degree, void* stream);
+long long mk_spec_cmlp_bgrad_workspace(int lloc, int cout);
+int mk_spec_cmlp_bgrad(const float* g, float* gb, void* workspace, int lloc, int mloc, int batch, int cout, int l_off,
+                       int m_off, void* stream);
+
 /* ---- "diagonal" spectral filter: one complex weight per (l, m) ---------------------------
  * Public layout, P = L * M contiguous: x [B][I][P], w [I][O][P], y [B][O][P] complex64.
  *   y[b][o][p] = sum_i x[b][i][p] * w[i][o][p]

@@ -61,6 +61,12 @@ SIGNATURES = {
     "mk_spec_mix_fwd": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),
     "mk_spec_mix_dgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),
     "mk_spec_mix_wgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),
+    "mk_spec_cmlp_fwd": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 9 + [_vp]),
+    "mk_spec_cmlp_dgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 9 + [_vp]),
+    "mk_spec_cmlp_wgrad_workspace": (ctypes.c_longlong, [_c_int] * 4),
+    "mk_spec_cmlp_wgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 8 + [_vp]),
+    "mk_spec_cmlp_bgrad_workspace": (ctypes.c_longlong, [_c_int] * 2),
+    "mk_spec_cmlp_bgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 6 + [_vp]),
     "mk_affine_add": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_dgrad": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),

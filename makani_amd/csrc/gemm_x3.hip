@@ -414,10 +414,16 @@ __device__ __forceinline__ void x3_mfma_step(const char* As, const char* Bs, con
 // tile's first row (null: no bias) and `act` != 0 the exact (erf) GELU: conv + bias + activation of layers.py:158-206 in one launch,
 // 4 = store complex rows: tile rows (2r, 2r + 1) are (re, im) of complex row r (the spectral channel mix),
 // 5 / 6 = complex table times interleaved complex columns (DftStager; the latitude DFT and its adjoint): `rvalid` counts the
-// tile's FREQUENCIES (<= 64), output row f of band wr is  acc[0] -+ i acc[1]  combined over the column parities, see below
+// tile's FREQUENCIES (<= 64), output row f of band wr is  acc[0] -+ i acc[1]  combined over the column parities, see below,
+// 7 = complex channel MLP forward: the tile's columns (2o, 2o + 1) are (re, im) of output channel o; store
+// act(tile + bias[column]) with `rowbias` pointing at the tile's first COLUMN of the interleaved complex bias (null: none) and
+// act 1 = ReLU on the real parts, 2 = ReLU on both parts (ComplexReLU `real` / `cartesian`),
+// 8 = its masked data gradient: store tile * (aux > 0) with `aux` the saved activation output at the tile's origin (row pitch
+// ldc); act 1 masks the real parts only, act 2 both
 template <int DB, class AS, class BS, int EPI = 0>
 __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int kt1, int rvalid, int cvalid, float* cbase,
-                                        long long ldc, char* lds, int exp = 0, const float* rowbias = nullptr, int act = 0) {
+                                        long long ldc, char* lds, int exp = 0, const float* rowbias = nullptr, int act = 0,
+                                        const float* aux = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: liveness tests stay scalar
     const int wr = wave >> 1, wc = wave & 1;
@@ -528,6 +534,42 @@ __device__ __forceinline__ void x3_tile(const AS& as, const BS& bs, int kt0, int
                         v4[2] = acc[a][1][r];
                         v4[3] = acc[a][1][r + 1];
                         __builtin_nontemporal_store(v4, reinterpret_cast<x3_f4*>(cbase + (long long)(row >> 1) * ldc + 2 * col));
+                    }
+                }
+        }
+        return;
+    }
+    if constexpr (EPI == 7 || EPI == 8) {
+        // a lane owns (re, im) of one complex output per register: bias / mask in fp32 on the accumulator, one 8-byte store
+        if (col < cvalid) {
+            float b0 = 0.f, b1 = 0.f;
+            if constexpr (EPI == 7) {
+                if (rowbias) {
+                    b0 = rowbias[col];
+                    b1 = rowbias[col + 1];
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
+                    if (row < rvalid) {
+                        typedef float x3_c2 __attribute__((ext_vector_type(2)));
+                        x3_c2 v2;
+                        if constexpr (EPI == 7) {
+                            v2[0] = acc[a][0][r] + b0;
+                            v2[1] = acc[a][1][r] + b1;
+                            if (act >= 1) v2[0] = v2[0] > 0.f ? v2[0] : 0.f;
+                            if (act == 2) v2[1] = v2[1] > 0.f ? v2[1] : 0.f;
+                            // (plain store: the next product of the chain reads these rows back)
+                            *reinterpret_cast<x3_c2*>(cbase + (long long)row * ldc + col) = v2;
+                        } else {
+                            const float2 m = *reinterpret_cast<const float2*>(aux + (long long)row * ldc + col);
+                            v2[0] = m.x > 0.f ? acc[a][0][r] : 0.f;
+                            v2[1] = (act != 2 || m.y > 0.f) ? acc[a][1][r] : 0.f;
+                            *reinterpret_cast<x3_c2*>(cbase + (long long)row * ldc + col) = v2;
+                        }
                     }
                 }
         }
@@ -1152,6 +1194,298 @@ extern "C" int mk_spec_mix_wgrad(const float* x, const float* gy, float* gw, int
     const long long nblk = grid_blocks(p.ngroups, p.tiles_m, p.tiles_n);
     MK_REQUIRE(nblk < 2147483647LL, "grid too large");
     hipLaunchKernelGGL(spec_mix_wgrad_x3_kernel, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Complex channel MLP on the private spectrum (SpectralAttention, filter_type="non-linear"): per layer
+//   y[l][m][b][o] = act(sum_i x[l][m][b][i] w[l * ws][i][o] + bias[o])
+// with complex [I][O] weight panels -- one per degree (ws = I * O, "l-dependant": the dhconv layout) or one for all (ws = 0,
+// "diagonal") -- a complex per-channel bias and ComplexReLU `real` / `cartesian`, both applied in fp32 on the accumulator (EPI 7).
+// The data gradient multiplies by relu' read off the saved activation OUTPUT of the layer in front (EPI 8).  The per-degree weight
+// gradient is dhconv's; the shared one contracts G consecutive degrees per workgroup into a partial panel (plain stores) and a
+// second pass adds the partials in ascending group order: no atomics, the same bits on every run.  The bias gradient is two
+// fixed-order passes in float64.  Rows (m <= l, b) as in dhconv; entries with l < m are neither read nor written.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct CmlpParams {
+    const float* a;      // x (fwd, wgrad) or gy (dgrad)
+    const float* b;      // w (fwd, dgrad) or gy (wgrad)
+    float* dst;
+    const float* bias;   // fwd: interleaved complex [O] or null
+    const float* aux;    // dgrad: saved activation output [L][M][B][I] or null
+    long long ws;        // complex elements between the weight panels of consecutive degrees (0: one shared panel)
+    int Lloc, Mloc, B, I, O, l_off, m_off, tiles_m, tiles_n, act;
+    int G, ngroups;      // shared wgrad: degrees per workgroup, number of such groups
+};
+
+__global__ __launch_bounds__(XT, 3) void spec_cmlp_fwd_kernel(CmlpParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.Lloc, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int l = p.Lloc - 1 - t.batch;  // heaviest degrees first
+    const int R = mix_rows(p.Mloc, p.B, p.l_off, p.m_off, l);
+    const int r0 = t.tm * XM;
+    if (r0 >= R) return;
+    const int n0 = t.tn * XN;
+    const long long rowbase = (long long)l * p.Mloc * p.B + r0;
+    RowStager as;
+    as.base = p.a + rowbase * 2 * p.I;
+    as.ld = 2 * p.I;
+    as.rows = R - r0;
+    as.kvalid = 2 * p.I;
+    CplxStager<false> bs;
+    bs.base = p.b + ((long long)l * p.ws + n0 / 2) * 2;
+    bs.ldk = p.O;
+    bs.kk_hi = p.I;
+    bs.ovalid = p.O - n0 / 2;
+    x3_tile<X3_DB, RowStager, CplxStager<false>, 7>(as, bs, 0, (2 * p.I + XK - 1) / XK, R - r0, 2 * p.O - n0,
+                                                     p.dst + rowbase * 2 * p.O + n0, 2LL * p.O, lds_x3, 0,
+                                                     p.bias ? p.bias + n0 : nullptr, p.act);
+}
+
+template <bool MASK>
+__global__ __launch_bounds__(XT, 3) void spec_cmlp_dgrad_kernel(CmlpParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.Lloc, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int l = p.Lloc - 1 - t.batch;
+    const int R = mix_rows(p.Mloc, p.B, p.l_off, p.m_off, l);
+    const int r0 = t.tm * XM;
+    if (r0 >= R) return;
+    const int n0 = t.tn * XN;
+    const long long rowbase = (long long)l * p.Mloc * p.B + r0;
+    RowStager as;
+    as.base = p.a + rowbase * 2 * p.O;
+    as.ld = 2 * p.O;
+    as.rows = R - r0;
+    as.kvalid = 2 * p.O;
+    DgradStager bs;
+    bs.base = p.b + ((long long)l * p.ws + (long long)(n0 / 2) * p.O) * 2;
+    bs.O = p.O;
+    bs.ivalid = p.I - n0 / 2;
+    const long long off = rowbase * 2 * p.I + n0;
+    if constexpr (MASK)
+        x3_tile<X3_DB, RowStager, DgradStager, 8>(as, bs, 0, (2 * p.O + XK - 1) / XK, R - r0, 2 * p.I - n0, p.dst + off, 2LL * p.I,
+                                                  lds_x3, 0, nullptr, p.act, p.aux + off);
+    else
+        x3_tile<X3_DB>(as, bs, 0, (2 * p.O + XK - 1) / XK, R - r0, 2 * p.I - n0, p.dst + off, 2LL * p.I, lds_x3);
+}
+
+// MixKStager's walk over the valid rows of several degrees for the complex B operand of the weight gradient (gy): the image of
+// CplxStager<true> -- complex column o -> rows 2o: [re, im], 2o + 1: [im, -re]; the conjugate sits on the A side.
+struct CplxKStager {
+    const float* base;    // gy + first complex column of the tile
+    long long O;          // channels (complex row pitch)
+    long long lpitch;     // floats per degree
+    int l0, KPL, ovalid;
+    int Mloc, B, l_off, m_off;
+    typedef float2 Regs[4];
+    static __device__ __forceinline__ int row_off(int r) { return pair_off(r); }
+    __device__ __forceinline__ void gload(int kt, Regs& r, int tid) const {
+        const int w = __builtin_amdgcn_readfirstlane(tid >> 6), o = tid & 63;
+        const int li = kt / KPL, l = l0 + li;
+        const int kk0 = (kt - li * KPL) * (XK / 2) + w * 4;
+        const int R = mix_rows(Mloc, B, l_off, m_off, l);
+        const bool ook = o < ovalid;
+        const __amdgpu_buffer_rsrc_t rs = x3_rsrc(base + (long long)l * lpitch);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            r[i] = x3_load8(rs, (ook && kk0 + i < R) ? (unsigned)((((long long)(kk0 + i)) * O + o) * 8) : X3_OOB);
+    }
+    __device__ __forceinline__ void sstore(const Regs& r, char* img, int tid) const {
+        const int w = tid >> 6, t = tid & 63;
+        float a[8], b[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a[2 * i] = r[i].x;
+            a[2 * i + 1] = r[i].y;
+            b[2 * i] = r[i].y;
+            b[2 * i + 1] = -r[i].x;
+        }
+        split_store8(a, img + t * XPITCH + w * 16);
+        split_store8(b, img + (t + 64) * XPITCH + 128 + w * 16);
+    }
+};
+
+// part[g][i][o] = sum over the valid rows of the degrees of group g of conj(x[.][i]) gy[.][o]
+__global__ __launch_bounds__(XT, 3) void spec_cmlp_wgrad_shared_kernel(CmlpParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.ngroups, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int g = p.ngroups - 1 - t.batch;
+    const int l0 = g * p.G, l1 = l0 + p.G < p.Lloc ? l0 + p.G : p.Lloc;
+    // k-steps per degree: those of the group's last (longest) one; 0 = no valid row in the group, the tile stores zeros
+    const int KPL = (mix_rows(p.Mloc, p.B, p.l_off, p.m_off, l1 - 1) + XK / 2 - 1) / (XK / 2);
+    const int i0 = t.tm * XM, n0 = t.tn * XN;
+    if (i0 >= p.I) return;
+    MixKStager<false> as;
+    as.base = p.a + 2 * i0;
+    as.C = p.I;
+    as.lpitch = 2LL * p.Mloc * p.B * p.I;
+    as.cvalid = p.I - i0;
+    CplxKStager bs;
+    bs.base = p.b + n0;
+    bs.O = p.O;
+    bs.lpitch = 2LL * p.Mloc * p.B * p.O;
+    bs.ovalid = p.O - n0 / 2;
+    as.l0 = bs.l0 = l0;
+    as.KPL = bs.KPL = KPL > 0 ? KPL : 1;
+    as.Mloc = bs.Mloc = p.Mloc;
+    as.B = bs.B = p.B;
+    as.l_off = bs.l_off = p.l_off;
+    as.m_off = bs.m_off = p.m_off;
+    x3_tile<X3_DB>(as, bs, 0, (l1 - l0) * KPL, p.I - i0, 2 * p.O - n0,
+                   p.dst + ((long long)g * p.I + i0) * 2 * p.O + n0, 2LL * p.O, lds_x3);
+}
+
+// dst[e] = sum_g part[g][e] in ascending g; n4 float4 elements per panel.  Eight panels' loads are issued before their adds (a
+// small layer has one panel per degree and few elements: one load in flight per thread is a chain of memory latencies)
+__global__ void spec_cmlp_group_sum_kernel(const float4* __restrict__ part, float4* __restrict__ dst, long long n4, int ngroups) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n4) return;
+    float4 s = part[e];
+    int g = 1;
+    for (; g + 8 <= ngroups; g += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = part[(long long)(g + j) * n4 + e];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s.x += v[j].x;
+            s.y += v[j].y;
+            s.z += v[j].z;
+            s.w += v[j].w;
+        }
+    }
+    for (; g < ngroups; ++g) {
+        const float4 v = part[(long long)g * n4 + e];
+        s.x += v.x;
+        s.y += v.y;
+        s.z += v.z;
+        s.w += v.w;
+    }
+    dst[e] = s;
+}
+
+// part[l][c] = sum over the valid rows r of degree l of g[l][r][c], c over the 2 O floats of a row; float64, four interleaved
+// chains per thread added in a fixed order
+__global__ __launch_bounds__(256) void spec_cmlp_bgrad_rows_kernel(const float* __restrict__ g, double* __restrict__ part, int Mloc,
+                                                                   int B, int O2, int l_off, int m_off, int chunks) {
+    const int l = blockIdx.x / chunks, c = (blockIdx.x - l * chunks) * 256 + threadIdx.x;
+    if (c >= O2) return;
+    const int R = mix_rows(Mloc, B, l_off, m_off, l);
+    const float* p = g + (long long)l * Mloc * B * O2 + c;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    int r = 0;
+    for (; r + 4 <= R; r += 4)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] += (double)p[(long long)(r + j) * O2];
+    for (int j = 0; r < R; ++r, ++j) s[j] += (double)p[(long long)r * O2];
+    part[(long long)l * O2 + c] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+__global__ void spec_cmlp_bgrad_sum_kernel(const double* __restrict__ part, float* __restrict__ gb, int Lloc, int O2) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= O2) return;
+    double s = 0.0;
+    for (int l = 0; l < Lloc; ++l) s += part[(long long)l * O2 + c];
+    gb[c] = (float)s;
+}
+
+// degrees per workgroup of the shared weight gradient: about three workgroups per CU
+int cmlp_group_size(int lloc, int cin, int cout) {
+    const long long tiles = (long long)mk::ceil_div(cin, XM) * mk::ceil_div(2 * cout, XN);
+    const long long G = mk::ceil_div_ll((long long)lloc * tiles, 768LL);
+    return (int)(G < 1 ? 1 : G);
+}
+
+}  // namespace
+
+static int spec_cmlp_check(const void* a, const void* b, const void* c, int lloc, int mloc, int batch, int cin, int cout, int l_off,
+                           int m_off, int per_degree, int act) {
+    if (int e = spec_mix_check(a, b, c, lloc, mloc, batch, cin, cout, l_off, m_off)) return e;
+    MK_REQUIRE(per_degree == 0 || per_degree == 1, "per_degree must be 0 (one shared weight panel) or 1");
+    MK_REQUIRE((long long)cin * cout * 8 < (1LL << 31), "one weight panel must stay below 2^31 bytes");
+    MK_REQUIRE(act >= 0 && act <= 2, "unknown activation (0 none | 1 real | 2 cartesian)");
+    return 0;
+}
+
+extern "C" int mk_spec_cmlp_fwd(const float* x, const float* w, const float* bias, float* y, int lloc, int mloc, int batch, int cin,
+                                int cout, int l_off, int m_off, int per_degree, int act, void* stream) {
+    if (int e = spec_cmlp_check(x, w, y, lloc, mloc, batch, cin, cout, l_off, m_off, per_degree, act)) return e;
+    MK_REQUIRE(((uintptr_t)bias & 7) == 0, "the bias must be 8-byte aligned");
+    CmlpParams p{x, w, y, bias, nullptr, per_degree ? (long long)cin * cout : 0LL, lloc, mloc, batch, cin, cout, l_off, m_off,
+                 mk::ceil_div(mloc * batch, XM), mk::ceil_div(2 * cout, XN), act, 1, 0};
+    const long long nblk = grid_blocks(lloc, p.tiles_m, p.tiles_n);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    hipLaunchKernelGGL(spec_cmlp_fwd_kernel, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mk_spec_cmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int lloc, int mloc, int batch, int cin,
+                                  int cout, int l_off, int m_off, int per_degree, int act, void* stream) {
+    if (int e = spec_cmlp_check(gy, w, gx, lloc, mloc, batch, cin, cout, l_off, m_off, per_degree, act)) return e;
+    MK_REQUIRE(((uintptr_t)a & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(a == nullptr || act != 0, "a mask operand needs an activation mode (1 real | 2 cartesian)");
+    CmlpParams p{gy, w, gx, nullptr, a, per_degree ? (long long)cin * cout : 0LL, lloc, mloc, batch, cin, cout, l_off, m_off,
+                 mk::ceil_div(mloc * batch, XM), mk::ceil_div(2 * cin, XN), act, 1, 0};
+    const long long nblk = grid_blocks(lloc, p.tiles_m, p.tiles_n);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    if (a) hipLaunchKernelGGL(spec_cmlp_dgrad_kernel<true>, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(spec_cmlp_dgrad_kernel<false>, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" long long mk_spec_cmlp_wgrad_workspace(int lloc, int cin, int cout, int per_degree) {
+    if (per_degree || lloc <= 0 || cin <= 0 || cout <= 0) return 0;
+    const int ngroups = mk::ceil_div(lloc, cmlp_group_size(lloc, cin, cout));
+    return ngroups > 1 ? (long long)ngroups * cin * cout * 8 : 0;
+}
+
+extern "C" int mk_spec_cmlp_wgrad(const float* x, const float* gy, float* gw, void* workspace, int lloc, int mloc, int batch, int cin,
+                                  int cout, int l_off, int m_off, int per_degree, void* stream) {
+    if (int e = spec_cmlp_check(x, gy, gw, lloc, mloc, batch, cin, cout, l_off, m_off, per_degree, 0)) return e;
+    if (per_degree) return mk_dhconv_wgrad_x3(x, gy, gw, lloc, mloc, batch, cin, cout, l_off, m_off, stream);
+    CmlpParams p{x, gy, gw, nullptr, nullptr, 0LL, lloc, mloc, batch, cin, cout, l_off, m_off, mk::ceil_div(cin, XM),
+                 mk::ceil_div(2 * cout, XN), 0, 1, 0};
+    p.G = cmlp_group_size(lloc, cin, cout);
+    p.ngroups = mk::ceil_div(lloc, p.G);
+    if (p.ngroups > 1) {
+        MK_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "the shared weight gradient needs its 16-byte aligned workspace");
+        p.dst = static_cast<float*>(workspace);
+    }
+    const long long nblk = grid_blocks(p.ngroups, p.tiles_m, p.tiles_n);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    hipLaunchKernelGGL(spec_cmlp_wgrad_shared_kernel, dim3((unsigned)nblk), dim3(XT), X3_LDS, (hipStream_t)stream, p);
+    MK_LAUNCH_CHECK();
+    if (p.ngroups > 1) {
+        const long long n4 = (long long)cin * cout / 2;      // cin, cout even: a whole number of float4
+        hipLaunchKernelGGL(spec_cmlp_group_sum_kernel, dim3((unsigned)mk::ceil_div_ll(n4, 256LL)), dim3(256), 0, (hipStream_t)stream,
+                           static_cast<const float4*>(workspace), reinterpret_cast<float4*>(gw), n4, p.ngroups);
+        MK_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" long long mk_spec_cmlp_bgrad_workspace(int lloc, int cout) {
+    return lloc > 0 && cout > 0 ? (long long)lloc * cout * 2 * 8 : 0;
+}
+
+extern "C" int mk_spec_cmlp_bgrad(const float* g, float* gb, void* workspace, int lloc, int mloc, int batch, int cout, int l_off,
+                                  int m_off, void* stream) {
+    if (int e = spec_mix_check(g, gb, workspace, lloc, mloc, batch, cout, cout, l_off, m_off)) return e;
+    const int O2 = 2 * cout, chunks = mk::ceil_div(O2, 256);
+    MK_REQUIRE((long long)lloc * chunks < 2147483647LL, "grid too large");
+    hipLaunchKernelGGL(spec_cmlp_bgrad_rows_kernel, dim3((unsigned)(lloc * chunks)), dim3(256), 0, (hipStream_t)stream, g,
+                       static_cast<double*>(workspace), mloc, batch, O2, l_off, m_off, chunks);
+    MK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(spec_cmlp_bgrad_sum_kernel, dim3((unsigned)mk::ceil_div(O2, 256)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const double*>(workspace), gb, lloc, O2);
     MK_LAUNCH_CHECK();
     return 0;
 }

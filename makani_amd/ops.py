@@ -971,6 +971,148 @@ def spec_mix(x, w, batch, l_off=0, m_off=0):
     return _SpecMix.apply(x, w, batch, l_off, m_off)
 
 
+# ----------------------------------------------------------------------------
+# complex channel MLP on the private spectrum (the non-linear filter, mk_spec_cmlp_*)
+# ----------------------------------------------------------------------------
+# The fused path is the default by the rule of DESIGN section 19: no row of tools/specattn_bench.py is slower than the torch
+# formulation.
+SPEC_ATTN_DEFAULT = "hip"
+CMLP_ACT = {None: 0, "none": 0, "real": 1, "cartesian": 2}
+
+
+def spec_attn_hip():
+    """``MK_SPEC_ATTN=hip|torch`` (read at call time): the channel MLP of ``SpectralAttention`` on the ``mk_spec_cmlp_*`` kernels,
+    or the torch einsums on the public spectrum."""
+    mode = os.environ.get("MK_SPEC_ATTN", SPEC_ATTN_DEFAULT)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"unknown MK_SPEC_ATTN {mode!r} (hip | torch)")
+    return mode == "hip"
+
+
+def _cmlp_weight(w, lloc):
+    assert w.dtype == torch.complex64 and w.is_contiguous() and w.dim() in (2, 3), "complex64 [I, O] or [L, I, O] weight"
+    assert w.dim() == 2 or w.shape[0] == lloc, "a per-degree weight needs one panel per local degree"
+    return int(w.dim() == 3), w.shape[-2], w.shape[-1]
+
+
+def _cmlp_out(out, shape, like):
+    if out is None:
+        return torch.empty(shape, dtype=torch.complex64, device=like.device)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == torch.complex64 and out.is_contiguous() and out.device == like.device
+    return out
+
+
+def spec_cmlp_fwd_raw(x, w, bias, batch, act=0, l_off=0, m_off=0, out=None):
+    """y[l, m, b, o] = act(sum_i x[l, m, b, i] w[(l,) i, o] + bias[o]) on the private spectrum ``[L, M, B * I]``; ``w`` complex64
+    ``[I, O]`` (all degrees) or ``[L, I, O]`` (per degree), ``bias`` complex64 with O elements or None, ``act`` 0 | 1 | 2
+    (none | ``real`` | ``cartesian``).  ``out``: the result's buffer (its entries with l < m stay as they are)."""
+    lloc, mloc, cin = _spec_mix_args(x, batch)
+    _need_cuda(w)
+    per_degree, wi, cout = _cmlp_weight(w, lloc)
+    assert wi == cin, "channel MLP operand shapes do not match"
+    bp = 0
+    if bias is not None:
+        _need_cuda(bias)
+        assert bias.dtype == torch.complex64 and bias.is_contiguous() and bias.numel() == cout
+        bp = bias.data_ptr()
+    y = _cmlp_out(out, (lloc, mloc, batch * cout), x)
+    _lib.check(_lib.load().mk_spec_cmlp_fwd(x.data_ptr(), w.data_ptr(), bp, y.data_ptr(), lloc, mloc, batch, cin, cout, l_off, m_off,
+                                            per_degree, int(act), _stream()), "mk_spec_cmlp_fwd")
+    return y
+
+
+def spec_cmlp_dgrad_raw(gy, w, a, batch, act=0, l_off=0, m_off=0, out=None):
+    """gx = (gy conj(w)^T) * relu'(a): ``a`` the saved activation output ``[L, M, B * I]`` of the layer in front (mode ``act``), or
+    None for no mask."""
+    lloc, mloc, cout = _spec_mix_args(gy, batch)
+    _need_cuda(w)
+    per_degree, cin, wo = _cmlp_weight(w, lloc)
+    assert wo == cout, "channel MLP operand shapes do not match"
+    ap = 0
+    if a is not None:
+        assert _spec_mix_args(a, batch) == (lloc, mloc, cin)
+        ap = a.data_ptr()
+    gx = _cmlp_out(out, (lloc, mloc, batch * cin), gy)
+    _lib.check(_lib.load().mk_spec_cmlp_dgrad(gy.data_ptr(), w.data_ptr(), ap, gx.data_ptr(), lloc, mloc, batch, cin, cout, l_off,
+                                              m_off, per_degree, int(act) if a is not None else 0, _stream()), "mk_spec_cmlp_dgrad")
+    return gx
+
+
+def spec_cmlp_wgrad_raw(x, gy, batch, per_degree, l_off=0, m_off=0):
+    """gw[(l,) i, o] = sum over the valid (m, b) (and, without ``per_degree``, l) of conj(x[l, m, b, i]) gy[l, m, b, o]."""
+    lloc, mloc, cin = _spec_mix_args(x, batch)
+    l2, m2, cout = _spec_mix_args(gy, batch)
+    assert (l2, m2) == (lloc, mloc)
+    lib = _lib.load()
+    gw = torch.empty((lloc, cin, cout) if per_degree else (cin, cout), dtype=torch.complex64, device=x.device)
+    nbytes = lib.mk_spec_cmlp_wgrad_workspace(lloc, cin, cout, int(bool(per_degree)))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    _lib.check(lib.mk_spec_cmlp_wgrad(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), ws.data_ptr() if nbytes else 0, lloc, mloc, batch,
+                                      cin, cout, l_off, m_off, int(bool(per_degree)), _stream()), "mk_spec_cmlp_wgrad")
+    return gw
+
+
+def spec_cmlp_bgrad_raw(g, batch, l_off=0, m_off=0):
+    """gb[o] = sum over the valid (l, m, b) of g[l, m, b, o] -> complex64 ``[O]`` (float64 sums in a fixed order)."""
+    lloc, mloc, cout = _spec_mix_args(g, batch)
+    lib = _lib.load()
+    gb = torch.empty(cout, dtype=torch.complex64, device=g.device)
+    ws = torch.empty(lib.mk_spec_cmlp_bgrad_workspace(lloc, cout) // 8, dtype=torch.float64, device=g.device)
+    _lib.check(lib.mk_spec_cmlp_bgrad(g.data_ptr(), gb.data_ptr(), ws.data_ptr(), lloc, mloc, batch, cout, l_off, m_off, _stream()),
+               "mk_spec_cmlp_bgrad")
+    return gb
+
+
+class _SpecChannelMLP(torch.autograd.Function):
+    """The channel MLP of the non-linear filter on the private spectrum: ``n`` activated products, then ``wout``.  Saves the input
+    spectrum and every layer's activation output (the next product's input and, by its signs, relu' of its own layer)."""
+
+    @staticmethod
+    def forward(ctx, c, batch, act, per_degree, l_off, m_off, n, has_bias, *params):
+        weights, biases, wout = params[:n], params[n:2 * n] if has_bias else (None,) * n, params[-1]
+        fields = [c]
+        for w, b in zip(weights, biases):
+            fields.append(spec_cmlp_fwd_raw(fields[-1], w.detach(), None if b is None else b.detach().reshape(-1), batch, act,
+                                            l_off, m_off))
+        y = spec_cmlp_fwd_raw(fields[-1], wout.detach(), None, batch, 0, l_off, m_off)
+        ctx.save_for_backward(*fields, *weights, wout)
+        ctx.args = (batch, act, per_degree, l_off, m_off, n, has_bias, [None if b is None else b.shape for b in biases])
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        batch, act, per_degree, l_off, m_off, n, has_bias, bshapes = ctx.args
+        fields, ws = ctx.saved_tensors[:n + 1], ctx.saved_tensors[n + 1:]
+        need = ctx.needs_input_grad
+        g = gy.contiguous()
+        gws, gbs = [None] * (n + 1), [None] * n
+        for k in range(n, -1, -1):      # layer k reads fields[k]; k == n is wout
+            if need[8 + k if k < n else len(need) - 1]:
+                gws[k] = spec_cmlp_wgrad_raw(fields[k], g, batch, per_degree, l_off, m_off)
+            if k < n and has_bias and need[8 + n + k]:
+                gbs[k] = spec_cmlp_bgrad_raw(g, batch, l_off, m_off).view(bshapes[k])
+            if k > 0:
+                g = spec_cmlp_dgrad_raw(g, ws[k], fields[k] if act else None, batch, act, l_off, m_off)     # act 0: no mask
+            elif need[0]:
+                g = spec_cmlp_dgrad_raw(g, ws[0], None, batch, 0, l_off, m_off)
+            else:
+                g = None
+        return (g, None, None, None, None, None, None, None, *gws[:n], *(gbs if has_bias else ()), gws[n])
+
+
+def spec_channel_mlp(c, weights, biases, wout, batch, act, per_degree, l_off=0, m_off=0):
+    """``SpectralAttention.forward_mlp`` on the private spectrum ``c`` ``[L, M, B * C]``: for every layer
+    ``c = ComplexReLU(c w + b)``, then ``c wout``.  ``weights`` / ``wout``: complex64 ``[I, O]`` (``per_degree`` False) or
+    ``[L, I, O]``; ``biases``: one complex64 tensor of O elements per layer, or None; ``act``: ``"real"`` | ``"cartesian"`` (or
+    None: plain products, no mask in the backward).
+    Gradients come back in every parameter's own shape."""
+    weights = list(weights)
+    biases = list(biases) if biases is not None else []
+    assert not biases or len(biases) == len(weights)
+    return _SpecChannelMLP.apply(c, batch, CMLP_ACT[act], bool(per_degree), l_off, m_off, len(weights), bool(biases),
+                                 *weights, *biases, wout)
+
+
 def rfft(x, twiddles, mmax, kmajor=False, scale=None):
     """``scale``: the factor on every mode; None = the SHT's 2 pi / nlon."""
     return _RFFT.apply(x, twiddles, mmax, kmajor, None, scale)

@@ -13,7 +13,7 @@ pixel-column engine, the skip convolution with the norm output as its epilogue a
 Spatial model parallelism (``comm.get_size("spatial") > 1``) selects the distributed transforms and
 ``DistributedInstanceNorm2d`` where the reference does (sfnonet.py:375-377, 528-533).  Channel
 ("matmul") parallelism is outside the built hot path and raises; ``layer_norm`` runs on torch ops; the non-linear (attention)
-filter runs on the HIP transforms with a torch channel MLP in between (``spectral_convolution.SpectralAttention``).
+filter runs on the HIP transforms with the ``mk_spec_cmlp_*`` channel MLP in between (``spectral_convolution.SpectralAttention``).
 """
 import math
 import os
@@ -83,6 +83,8 @@ class SpectralFilterLayer(nn.Module):
             return out
         if want_row_sums and isinstance(self.filter, SpectralConv) and type(self.filter).forward is SpectralConv.forward:
             return self.filter(x, want_row_sums=True)
+        if want_row_sums and isinstance(self.filter, SpectralAttention) and type(self.filter).forward is SpectralAttention.forward:
+            return self.filter(x, want_row_sums=True)     # its fused path has the inverse FFT's statistics, the other None
         out = self.filter(x)
         return (out[0], out[1], None) if want_row_sums else out
 

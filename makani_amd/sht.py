@@ -80,15 +80,17 @@ class InverseRealSHT(_SHTBase):
         super().__init__(nlat, nlon, lmax, mmax, grid, norm, csphase)
         self.register_buffer("pct", ops.legendre_table(grid, nlat, self.lmax, self.mmax, False), persistent=False)
 
-    def inverse_packed(self, c, out_dtype=torch.float32, want_row_sums=False):
+    def inverse_packed(self, c, out_dtype=torch.float32, want_row_sums=False, exact_sums=False):
         """spectrum [lmax, mmax, BC] -> x [BC, nlat, nlon] (fp32, or bf16 rows straight from the FFT kernel); with
         ``want_row_sums`` (and a length the split kernels serve) also the fp64 ``[BC, 2]`` sums / sums of squares of the rows of x
-        -- the statistics of the instance norm that reads x next -- else None in their place."""
+        -- the statistics of the instance norm that reads x next -- else None in their place.  ``exact_sums``: the statistics
+        through ``mk_irfft_sums_ws`` (float64 from the first add, fixed order, one more launch: 1e-12 of the stored rows' sums
+        where ``mk_irfft_sums`` gives about 2^-24), as the planar ``InverseRealFFT2.inverse_packed`` always has them."""
         km = ops.SPECTRAL_GEMM == "bf16x3"
         xf = ops.legendre_inv(c, self.pct, self.nlat, 0, km)
         if want_row_sums:
             if ops.irfft_sums_supported(self.nlon, self.mmax) and out_dtype in (torch.float32, torch.bfloat16):
-                return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, km, True)
+                return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, km, True, exact_sums=exact_sums)
             return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, km), None
         return ops.irfft(xf, self.twiddles, self.nlon, out_dtype, km)
 

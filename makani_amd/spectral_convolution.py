@@ -327,9 +327,15 @@ class SpectralAttention(nn.Module):
 
     Deviation, documented: the reference's ``forward_mlp`` hands the ``view_as_real`` 5-D tensor to a 4-index einsum
     (spectral_convolution.py:367-374 with contractions.py:49-54) and cannot run; the arithmetic here is the evident intent
-    -- the same einsums on the complex tensor.  No reference fixture can exist: parity of this class is unpinned.  The
-    transforms are the HIP SHT of this package; the channel MLP itself is a handful of torch complex matmuls (it is not on
-    the path the benchmark config takes).
+    -- the same einsums on the complex tensor.  No reference fixture can exist: parity of this class is unpinned.
+
+    With this package's HIP transform pair (``RealSHT`` / ``InverseRealSHT``, their distributed pair, ``RealFFT2`` /
+    ``InverseRealFFT2`` on their HIP path), the ``real`` / ``cartesian`` activation, no active dropout and even channel counts
+    the layer runs fused on the private channels-last spectrum like ``SpectralConv``: analysis -> ``ops.spec_channel_mlp``
+    (one ``mk_spec_cmlp_fwd`` launch per product: bias and ``ComplexReLU`` in the GEMM's epilogue, the triangle only) ->
+    synthesis, with no ``spec_unpack`` / ``spec_pack`` and no vendor GEMM.  ``MK_SPEC_ATTN=torch`` (or any other case) takes
+    ``_forward_torch``: the public transforms around torch einsums.  Under a distributed pair the ``l-dependant`` weights hold
+    the local degrees only (``sharded_dims_mp = ["h", None, None]``); ``diagonal`` weights and the biases are replicated.
     """
 
     def __init__(self, forward_transform, inverse_transform, in_channels, out_channels, operator_type="diagonal",
@@ -337,18 +343,31 @@ class SpectralAttention(nn.Module):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.operator_type, self.spectral_layers = operator_type, spectral_layers
+        self.complex_activation = complex_activation
         self.modes_lat, self.modes_lon = forward_transform.lmax, forward_transform.mmax
         self.forward_transform, self.inverse_transform = forward_transform, inverse_transform
-        self.scale_residual = ((forward_transform.nlat != inverse_transform.nlat) or (forward_transform.nlon != inverse_transform.nlon)
-                               or (forward_transform.grid != inverse_transform.grid))
+        self.scale_residual = (forward_transform.nlat != inverse_transform.nlat) or (forward_transform.nlon != inverse_transform.nlon)
+        if hasattr(forward_transform, "grid"):
+            self.scale_residual = self.scale_residual or (forward_transform.grid != inverse_transform.grid)
         assert inverse_transform.lmax == self.modes_lat
         assert inverse_transform.mmax == self.modes_lon
+        self._distributed = isinstance(inverse_transform, (DistributedInverseRealSHT, DistributedInverseRealFFT2))
+        if self._distributed:
+            hr, wr = comm.get_rank("h"), comm.get_rank("w")
+            self.modes_lat_local = inverse_transform.l_shapes[hr]
+            self.modes_lon_local = inverse_transform.m_shapes[wr]
+            self.l_off = sum(inverse_transform.l_shapes[:hr])
+            self.m_off = sum(inverse_transform.m_shapes[:wr])
+        else:
+            self.modes_lat_local, self.modes_lon_local = self.modes_lat, self.modes_lon
+            self.l_off, self.m_off = 0, 0
         hidden = int(hidden_size_factor * in_channels)
+        self.hidden_channels = hidden
         if operator_type == "diagonal":
             lead = ()
             self._eq = "bixy,io->boxy"
         elif operator_type == "l-dependant":
-            lead = (self.modes_lat,)
+            lead = (self.modes_lat_local,)
             self._eq = "bixy,xio->boxy"
         else:
             raise ValueError("Unknown operator type")
@@ -361,9 +380,21 @@ class SpectralAttention(nn.Module):
             self.b = nn.ParameterList([nn.Parameter(scale * torch.randn(hidden, 1, 1, dtype=torch.complex64))
                                        for _ in range(spectral_layers)])
         self.wout = nn.Parameter(scale * torch.randn(*lead, hidden, out_channels, dtype=torch.complex64))
+        if self._distributed:
+            # every rank applies the MLP to its own (l, m) shard: a per-degree weight is a shard along l (and shared over the
+            # m shards), a degree-independent weight or a bias is the same on every spatial rank
+            for p in list(self.w) + [self.wout]:
+                if lead:
+                    p.is_shared_mp, p.sharded_dims_mp = ["matmul", "w"], ["h", None, None]
+                else:
+                    p.is_shared_mp, p.sharded_dims_mp = ["spatial"], [None, None]
+            for p in (self.b if bias else ()):
+                p.is_shared_mp, p.sharded_dims_mp = ["spatial"], [None, None, None]
         self.activations = nn.ModuleList([ComplexReLU(mode=complex_activation, bias_shape=(hidden, 1, 1), scale=scale)
                                           for _ in range(spectral_layers)])
         self.drop = nn.Dropout(drop_rate) if drop_rate > 0.0 else nn.Identity()
+        self._hip_pair = _is_hip_pair(forward_transform, inverse_transform)
+        self._planar = isinstance(forward_transform, RealFFT2) and isinstance(inverse_transform, InverseRealFFT2)
 
     def forward_mlp(self, x):
         for layer in range(self.spectral_layers):
@@ -375,7 +406,55 @@ class SpectralAttention(nn.Module):
                 x = torch.view_as_complex(self.drop(torch.view_as_real(x)))
         return torch.einsum(self._eq, x, self.wout)
 
-    def forward(self, x):
+    def _takes_fused(self, x):
+        """The fused path applies: the kernels' activations and channel counts, no active dropout, the bf16x3 engine, this
+        package's HIP transforms for this input, and ``MK_SPEC_ATTN`` not ``torch``."""
+        hip = ops.spec_attn_hip()       # validates the knob on every call
+        if not (hip and x.is_cuda and x.dim() == 4 and self.complex_activation in ("real", "cartesian")):
+            return False
+        if self.training and not isinstance(self.drop, nn.Identity):
+            return False
+        if self.in_channels % 2 or self.hidden_channels % 2 or self.out_channels % 2 or ops.SPECTRAL_GEMM != "bf16x3":
+            return False
+        if self._hip_pair:
+            return True
+        ft = self.forward_transform
+        return (self._planar and x.dtype in (torch.float32, torch.bfloat16) and tuple(x.shape[-2:]) == (ft.nlat, ft.nlon)
+                and ft.hip_ready(x) and self.inverse_transform.hip_ready(x))
+
+    def _forward_fused(self, x, dtype, want_row_sums=False):
+        B, C = x.shape[0], x.shape[1]
+        ft, it = self.forward_transform, self.inverse_transform
+        # planar spectrum: every (l, m) entry is data -- a degree offset >= mmax switches the kernels' triangle off
+        l_off = self.modes_lon if self._planar else self.l_off
+        xin = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
+        xin = xin.contiguous()
+        if isinstance(ft, DistributedRealSHT):
+            c = ft.forward_packed(xin)
+        else:
+            c = ft.forward_packed(xin.view(B * C, xin.shape[2], xin.shape[3]))
+        odt = dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32
+        residual = x
+        if self.scale_residual:
+            r = it.inverse_packed(c, B, odt) if self._distributed else it.inverse_packed(c, odt)
+            residual = r.view(B, C, r.shape[-2], r.shape[-1]).to(dtype)
+        y = ops.spec_channel_mlp(c, list(self.w), list(self.b) if hasattr(self, "b") else None, self.wout, B,
+                                 self.complex_activation, self.operator_type == "l-dependant", l_off, self.m_off)
+        sums = None
+        if want_row_sums and self._distributed:     # the local shares, mk_irfft_sums (the sharded norm all-reduces them)
+            out, sums = it.inverse_packed(y, B, odt, True)
+        elif want_row_sums and isinstance(it, InverseRealSHT):
+            # the inverse FFT hands over the row statistics of its output, float64 in a fixed order like the planar pair's
+            # (mk_irfft_sums_ws): they are those of the stored rows to 1e-12 whichever pair the layer was built on
+            out, sums = it.inverse_packed(y, odt, True, exact_sums=True)
+        elif want_row_sums:
+            out, sums = it.inverse_packed(y, odt, True)
+        else:
+            out = it.inverse_packed(y, B, odt) if self._distributed else it.inverse_packed(y, odt)
+        out = out.view(B, self.out_channels, out.shape[-2], out.shape[-1])
+        return out, residual, sums
+
+    def _forward_torch(self, x):
         dtype = x.dtype
         residual = x
         x = x.to(torch.float32)
@@ -387,3 +466,17 @@ class SpectralAttention(nn.Module):
         with torch.autocast(device_type=x.device.type, enabled=False):
             x = self.inverse_transform(x)
         return x.to(dtype), residual
+
+    def forward(self, x, want_row_sums=False):
+        """``want_row_sums`` (this package's blocks only): a third result, the fp64 ``[B*C, 2]`` sums / sums of squares of the rows
+        of the filtered field for the instance norm behind the filter, or None where the path cannot deliver them."""
+        if self._takes_fused(x):
+            dtype = x.dtype
+            with torch.autocast(device_type="cuda", enabled=False):
+                y, residual, sums = self._forward_fused(x, dtype, want_row_sums)
+            if sums is not None and y.dtype != dtype:
+                sums = None                         # a cast behind the kernel: the statistics are those of other values
+            y = y.to(dtype)
+        else:
+            (y, residual), sums = self._forward_torch(x), None
+        return (y, residual, sums) if want_row_sums else (y, residual)

@@ -1,0 +1,168 @@
+"""``SpectralAttention`` without a GPU: the constructor's parameters (names, shapes, order) for both operator types, the
+model-parallel annotations and local shapes under a faked ``h = 2`` communicator, the ``MK_SPEC_ATTN`` knob, and the CPU path
+being the torch formulation whatever the knob says."""
+import pytest
+import torch
+
+from makani_amd import comm, ops
+from makani_amd.sht import InverseRealSHT, RealSHT
+from makani_amd.spectral_convolution import SpectralAttention
+
+KW = dict(lmax=20, mmax=21, grid="equiangular")
+
+
+def _expected(operator_type, C, hidden, layers, bias, L):
+    lead = (L,) if operator_type == "l-dependant" else ()
+    want = {"w.0": lead + (C, hidden)}
+    for k in range(1, layers):
+        want[f"w.{k}"] = lead + (hidden, hidden)
+    if bias:
+        for k in range(layers):
+            want[f"b.{k}"] = (hidden, 1, 1)
+    want["wout"] = lead + (hidden, C)
+    return want
+
+
+@pytest.mark.parametrize("operator_type", ["diagonal", "l-dependant"])
+@pytest.mark.parametrize("activation,bias", [("real", False), ("cartesian", True), ("modulus", True)])
+def test_constructor_parity(operator_type, activation, bias):
+    """Keys and shapes of the reference's class (spectral_convolution.py:268-365): ``w.N`` ``[(L,) in, hidden]`` then
+    ``[(L,) hidden, hidden]``, ``b.N`` ``[hidden, 1, 1]``, ``wout`` ``[(L,) hidden, out]``, ``activations.N.bias`` ``[hidden, 1, 1]``
+    for the modes that learn one; complex64 weights and biases."""
+    C, layers = 6, 2
+    mod = SpectralAttention(RealSHT(33, 64, **KW), InverseRealSHT(33, 64, **KW), C, C, operator_type=operator_type,
+                            hidden_size_factor=2, complex_activation=activation, bias=bias, spectral_layers=layers)
+    want = _expected(operator_type, C, 12, layers, bias, 20)
+    if activation == "modulus":
+        want.update({f"activations.{k}.bias": (12, 1, 1) for k in range(layers)})
+    sd = mod.state_dict()
+    assert {k: tuple(v.shape) for k, v in sd.items()} == want
+    assert all(v.dtype == torch.complex64 for k, v in sd.items() if not k.startswith("activations"))
+    assert not any(hasattr(p, "is_shared_mp") or hasattr(p, "sharded_dims_mp") for p in mod.parameters())
+    assert (mod.l_off, mod.m_off, mod.modes_lat_local, mod.modes_lon_local) == (0, 0, 20, 21)
+    with pytest.raises(ValueError):
+        SpectralAttention(RealSHT(33, 64, **KW), InverseRealSHT(33, 64, **KW), C, C, operator_type="dhconv")
+
+
+def test_same_seed_same_initial_values():
+    """The initialisation draws in the order it always did: w.0 .. w.N, b.0 .. b.N, wout."""
+    import math
+    torch.manual_seed(3)
+    mod = SpectralAttention(RealSHT(33, 64, **KW), InverseRealSHT(33, 64, **KW), 4, 4, operator_type="l-dependant",
+                            hidden_size_factor=2, complex_activation="real", bias=True, spectral_layers=1, gain=2.0)
+    torch.manual_seed(3)
+    w0 = math.sqrt(2.0 / 4) * torch.randn(20, 4, 8, dtype=torch.complex64)
+    b0 = math.sqrt(2.0 / 4) * torch.randn(8, 1, 1, dtype=torch.complex64)
+    wout = math.sqrt(2.0 / 4) * torch.randn(20, 8, 4, dtype=torch.complex64)
+    assert torch.equal(mod.w[0], w0) and torch.equal(mod.b[0], b0) and torch.equal(mod.wout, wout)
+
+
+@pytest.mark.parametrize("rank", [0, 1])
+@pytest.mark.parametrize("operator_type", ["diagonal", "l-dependant"])
+def test_annotations_and_local_shapes_under_h2(monkeypatch, operator_type, rank):
+    """h = 2, lmax = 21: the degree shards are uneven (11 and 10).  A per-degree weight holds the local degrees and is a shard
+    along ``h`` (shared over ``matmul`` and the ``w`` ranks, which see the same degrees); a degree-independent weight and the
+    biases are replicated on every spatial rank, so their gradients are summed over ``spatial``."""
+    from makani_amd.distributed import DistributedInverseRealSHT, DistributedRealSHT
+    monkeypatch.setattr(comm, "get_size", lambda name: 2 if name in ("h", "spatial", "model") else 1)
+    monkeypatch.setattr(comm, "get_rank", lambda name: rank if name in ("h", "spatial", "model") else 0)
+    kw = dict(lmax=21, mmax=22, grid="equiangular")
+    mod = SpectralAttention(DistributedRealSHT(32, 64, **kw), DistributedInverseRealSHT(32, 64, **kw), 4, 4,
+                            operator_type=operator_type, hidden_size_factor=2, complex_activation="cartesian", bias=True,
+                            spectral_layers=2)
+    lloc = (11, 10)[rank]
+    assert (mod.modes_lat, mod.modes_lon, mod.modes_lat_local, mod.modes_lon_local) == (21, 22, lloc, 22)
+    assert (mod.l_off, mod.m_off) == ((0, 11)[rank], 0)
+    want = _expected(operator_type, 4, 8, 2, True, lloc)
+    assert {k: tuple(v.shape) for k, v in mod.state_dict().items()} == want
+    for p in list(mod.w) + [mod.wout]:
+        if operator_type == "l-dependant":
+            assert p.is_shared_mp == ["matmul", "w"] and p.sharded_dims_mp == ["h", None, None]
+        else:
+            assert p.is_shared_mp == ["spatial"] and p.sharded_dims_mp == [None, None]
+    for p in mod.b:
+        assert p.is_shared_mp == ["spatial"] and p.sharded_dims_mp == [None, None, None]
+
+
+def test_knob_validation(monkeypatch):
+    mod = SpectralAttention(RealSHT(33, 64, **KW), InverseRealSHT(33, 64, **KW), 4, 4)
+    for value, want in (("hip", True), ("torch", False)):
+        monkeypatch.setenv("MK_SPEC_ATTN", value)
+        assert ops.spec_attn_hip() is want
+    monkeypatch.delenv("MK_SPEC_ATTN")
+    assert ops.spec_attn_hip() is (ops.SPEC_ATTN_DEFAULT == "hip")
+    monkeypatch.setenv("MK_SPEC_ATTN", "triton")
+    with pytest.raises(ValueError, match="MK_SPEC_ATTN"):
+        ops.spec_attn_hip()
+    with pytest.raises(ValueError, match="MK_SPEC_ATTN"):      # read at call time, by the module too
+        mod(torch.zeros(1, 4, 33, 64))
+
+
+def test_raw_wrappers_have_no_cpu_fallback():
+    x = torch.zeros(4, 5, 4, dtype=torch.complex64)
+    w = torch.zeros(4, 6, dtype=torch.complex64)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.spec_cmlp_fwd_raw(x, w, None, 1)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.spec_channel_mlp(x, [w], None, w.t().contiguous(), 1, "real", False)
+
+
+def test_launchers_validate_before_launching():
+    """Code 1 and a message for what ``spec_mix_check`` refuses, plus the new arguments; nothing is launched (the pointers are
+    never dereferenced)."""
+    from makani_amd import _lib
+    lib = _lib.load()
+    P = 4096
+    ok = dict(lloc=4, mloc=5, batch=1, cin=4, cout=6, l_off=0, m_off=0, per_degree=0, act=1)
+
+    def fwd(x=P, w=P, bias=None, y=P, **kw):
+        a = dict(ok, **kw)
+        return lib.mk_spec_cmlp_fwd(x, w, bias, y, *(a[k] for k in ok), None)
+
+    def dgrad(gy=P, w=P, a=None, gx=P, **kw):
+        b = dict(ok, **kw)
+        return lib.mk_spec_cmlp_dgrad(gy, w, a, gx, *(b[k] for k in ok), None)
+
+    for bad in (dict(cin=5), dict(cout=7), dict(lloc=0), dict(l_off=-1), dict(act=3), dict(per_degree=2), dict(x=P + 8),
+                dict(y=None), dict(bias=P + 4), dict(mloc=1 << 15, batch=1 << 10, cout=1 << 10)):
+        assert fwd(**bad) == 1, bad
+        assert lib.mk_last_error()
+    # one weight panel of 2^31 bytes (the stagers' 32-bit byte offsets), a degree of the field far below it
+    assert fwd(mloc=1, cin=1 << 14, cout=1 << 14) == 1 and "weight panel" in lib.mk_last_error().decode()
+    assert dgrad(mloc=1, cin=1 << 14, cout=1 << 14) == 1 and "weight panel" in lib.mk_last_error().decode()
+    for bad in (dict(cin=3), dict(act=-1), dict(a=P + 8), dict(a=P, act=0), dict(gx=None)):
+        assert dgrad(**bad) == 1, bad
+    assert lib.mk_spec_cmlp_wgrad(P, P, P, None, 4, 5, 1, 3, 6, 0, 0, 0, None) == 1
+    assert lib.mk_spec_cmlp_bgrad(P, P, None, 4, 5, 1, 6, 0, 0, None) == 1
+    assert lib.mk_spec_cmlp_wgrad_workspace(240, 384, 768, 1) == 0
+    assert lib.mk_spec_cmlp_wgrad_workspace(240, 384, 768, 0) % (384 * 768 * 8) == 0
+    assert lib.mk_spec_cmlp_bgrad_workspace(240, 768) == 240 * 768 * 16
+
+
+@pytest.mark.parametrize("knob", ["hip", "torch"])
+def test_cpu_forward_is_the_torch_formulation(monkeypatch, knob):
+    monkeypatch.setenv("MK_SPEC_ATTN", knob)
+    torch.manual_seed(0)
+
+    class _Id(torch.nn.Module):          # a duck-typed transform pair on the CPU: the layer takes its torch path
+        nlat, nlon, lmax, mmax, grid = 8, 16, 8, 9, "equiangular"
+
+        def __init__(self, inverse):
+            super().__init__()
+            self.inverse = inverse
+
+        def forward(self, x):
+            return torch.fft.irfft(x, n=16, dim=-1) if self.inverse else torch.fft.rfft(x, dim=-1)
+
+    mod = SpectralAttention(_Id(False), _Id(True), 4, 4, operator_type="l-dependant", complex_activation="cartesian", bias=True,
+                            spectral_layers=2)
+    x = torch.randn(2, 4, 8, 16)
+    y, res = mod(x)
+    c = torch.fft.rfft(x, dim=-1)
+    for k in range(2):
+        c = torch.einsum("bixy,xio->boxy", c, mod.w[k]) + mod.b[k]
+        c = torch.complex(torch.relu(c.real), torch.relu(c.imag))
+    want = torch.fft.irfft(torch.einsum("bixy,xio->boxy", c, mod.wout), n=16, dim=-1)
+    assert res is x and torch.allclose(y, want, rtol=1e-6, atol=1e-6)
+    y3 = mod(x, want_row_sums=True)
+    assert len(y3) == 3 and y3[2] is None and torch.equal(y3[0], y)
