@@ -52,7 +52,7 @@ struct WgradParams {
 // LDS row pitch WPITCH = 2 TK + 16 bytes (an odd number of 16-byte units: conflict-free ds_read_b128)
 // Loads are raw buffer loads: a lane outside the tile (row past the operand, pixel past the slab) gets an offset past the
 // descriptor's range and reads zeros -- no exec-mask branch per vector, nothing that makes the compiler wait for a load
-// where it is issued (same finding as in gemm_x3.hip).  Offsets are bytes from the block's first row (< 2^31: at most
+// where it is issued (same finding as in x3_engine.h).  Offsets are bytes from the block's first row (< 2^31: at most
 // 256 rows of 2 P bytes).
 template <int NV, int WVPR>
 __device__ __forceinline__ void wg_load(const __hip_bfloat16* base, long long ld, int rows_valid, long long k0,
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(WT) void conv1x1_wgrad_kernel(WgradParams p) {
         for (int c = 0; c < 2; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][c][r] = 0.f;
-    // accumulators in the AccVGPR half of the register file (AGPR form of the MFMAs): see x3_tile in gemm_x3.hip
+    // accumulators in the AccVGPR half of the register file (AGPR form of the MFMAs): see x3_tile in x3_engine.h
 #pragma unroll
     for (int a = 0; a < MT; ++a)
 #pragma unroll
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(WT8) void conv1x1_wgrad_big_kernel(WgradParams p) {
 #pragma unroll
     for (int a = 0; a < RT; ++a)
 #pragma unroll
-        for (int c = 0; c < CT; ++c) asm volatile("" : "+a"(acc[a][c]));      // AGPR form of the MFMAs: see x3_tile in gemm_x3.hip
+        for (int c = 0; c < CT; ++c) asm volatile("" : "+a"(acc[a][c]));      // AGPR form of the MFMAs: see x3_tile in x3_engine.h
 
     uint4 ra[NVA], rb[NVB];
     const int nk = (int)((k_end - k_begin + 63) / 64);
