@@ -248,6 +248,31 @@ long long mk_spec_cmlp_bgrad_workspace(int lloc, int cout);
 int mk_spec_cmlp_bgrad(const float* g, float* gb, void* workspace, int lloc, int mloc, int batch, int cout, int l_off,
                        int m_off, void* stream);
 
+/* ---- block-diagonal complex MLP on the dense planar spectrum (AFNO2D, afnonet_v2.py:84-106) -----
+ * The spectrum of RealFFT2.forward_packed is dense (no triangle) and is taken as flat rows r < rows = L * M * B of nb * ib
+ * (nb * ob) complex64 channels, cut into nb blocks with one complex [ib][ob] panel each; bf16x3 engine:
+ *   fwd:   y[r][k*ob + o]  = act(sum_i x[r][k*ib + i] * w[k][i][o])
+ *   dgrad: gx[r][k*ib + i] = (sum_o gy[r][k*ob + o] * conj(w[k][i][o])) * mask(a[r][k*ib + i])
+ *   wgrad: gw[k][i][o]     = sum_r conj(x[r][k*ib + i]) * gy[r][k*ob + o]
+ *   mask:  out[e]          = s[e] != 0 ? gy[e] : 0          over n floats (components), out may alias gy
+ * w: complex [nb][ib][ob] (view_as_complex of the reference's [nb, ib, ob, 2] parameter).  act: 0 none, 2 ReLU on both
+ * components, 3 soft-shrink with threshold lambda >= 0 on both components (v > lambda: v - lambda, v < -lambda: v + lambda, else
+ * +0), applied in fp32 on the accumulator.  a: the saved activation OUTPUT of the layer in front ([rows][nb*ib], act = 2: a
+ * component passes where the same component of a is > 0) or NULL with act = 0.  There is no bias.
+ * softshrink' is read off the saved soft-shrink OUTPUT s by the pointwise `mask` pass (one read of gy and s, one write), whose
+ * result is the gy of both dgrad and wgrad of that layer.
+ * The weight gradient contracts groups of rows into partial panels in `workspace` (mk_spec_bdmlp_wgrad_workspace bytes, 16-byte
+ * aligned; 0 bytes: not needed) and adds them in ascending order: no atomics, the same bits on every run.
+ * ib, ob even (block offsets stay 16-byte aligned), operands 16-byte aligned, 129 rows of a field and one panel below 2^31 bytes. */
+int mk_spec_bdmlp_fwd(const float* x, const float* w, float* y, int rows, int nb, int ib, int ob, int act, float lambda,
+                      void* stream);
+int mk_spec_bdmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int rows, int nb, int ib, int ob, int act,
+                        void* stream);
+long long mk_spec_bdmlp_wgrad_workspace(int rows, int nb, int ib, int ob);
+int mk_spec_bdmlp_wgrad(const float* x, const float* gy, float* gw, void* workspace, int rows, int nb, int ib, int ob,
+                        void* stream);
+int mk_spec_bdmlp_mask(const float* gy, const float* s, float* out, long long n, void* stream);
+
 /* ---- "diagonal" spectral filter: one complex weight per (l, m) ---------------------------
  * Public layout, P = L * M contiguous: x [B][I][P], w [I][O][P], y [B][O][P] complex64.
  *   y[b][o][p] = sum_i x[b][i][p] * w[i][o][p]

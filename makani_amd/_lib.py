@@ -67,7 +67,12 @@ SIGNATURES = {
     "mk_spec_cmlp_wgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 8 + [_vp]),
     "mk_spec_cmlp_bgrad_workspace": (ctypes.c_longlong, [_c_int] * 2),
     "mk_spec_cmlp_bgrad": (_c_int, [_vp, _vp, _vp] + [_c_int] * 6 + [_vp]),
-    "mk_affine_add": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
+    "mk_spec_bdmlp_fwd": (_c_int, [_vp, _vp, _vp] + [_c_int] * 5 + [_c_float, _vp]),
+    "mk_spec_bdmlp_dgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
+    "mk_spec_bdmlp_wgrad_workspace": (ctypes.c_longlong, [_c_int] * 4),
+    "mk_spec_bdmlp_wgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 4 + [_vp]),
+    "mk_spec_bdmlp_mask": (_c_int, [_vp, _vp, _vp, ctypes.c_longlong, _vp]),
+    "mk_affine_add":(_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_dgrad": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_wgrad": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),

@@ -572,6 +572,154 @@ __global__ __launch_bounds__(XT, 3) void spec_mix_wgrad_x3_kernel(MixParams p) {
     x3_tile(as, bs, 0, (l1 - l0) * KPL, p.Ca - o0, p.Cd - i0, epi, lds_x3);
 }
 
+// ---------------------------------------------------------------------------
+// Block-diagonal complex MLP on the dense planar spectrum (AFNO2D): the channels are cut into nb blocks and block k has its
+// own [ib][ob] panel,   y[r][k ob + o] = act(sum_i x[r][k ib + i] w[k][i][o]).
+// The spectrum is dense (no triangle), so it is taken as flat rows r < rows = L * M * B of nb * ib complex channels, and the
+// block index is the grid's batch dimension: block k is a pointer offset of k * ib complex columns into rows of the full pitch,
+// with the stagers' valid counts set to the block's own extent (a k-step never runs into the next block's channels).
+// decode_block keeps the tiles of one block on one XCD, next to that block's panel in its L2.
+// The soft-shrink is an epilogue type of its own, compile-time like the other modes: the instantiations of the dense MLP and
+// dhconv kernels above are untouched.
+// ---------------------------------------------------------------------------
+struct BlockParams {
+    const float* a;      // x (fwd, wgrad) or gy (dgrad)
+    const float* b;      // w (fwd, dgrad) or gy (wgrad)
+    float* dst;
+    const float* aux;    // masked dgrad: saved activation output [rows][nb * ib]
+    int rows, nb, ib, ob, tiles_m, tiles_n;
+    float lambda;        // soft-shrink threshold
+    int rg, ngroups;     // wgrad: rows per group (a multiple of 16), number of groups
+};
+
+constexpr int BD_STORE = 0, BD_RELU = 2, BD_SHRINK = 3, BD_MASK = 4;
+
+// store f(tile) with f fixed at compile time: nothing, ReLU or soft-shrink on both components (fp32, on the accumulator), or the
+// mask (aux > 0) per component with `aux` the saved activation output at the tile's origin (row pitch ldc)
+template <int MODE>
+struct BlockEpi {
+    float* cbase;
+    long long ldc;
+    const float* aux;
+    float lambda;
+    static constexpr bool PAIRED_BANDS = false;
+    static __device__ __forceinline__ float shrink(float v, float l) { return v > l ? v - l : (v < -l ? v + l : 0.f); }
+    __device__ __forceinline__ void store(const f32x16 (&acc)[2][2], int wr, int wc, int fi, int kg, int rvalid, int cvalid) const {
+        const int col = wc * 64 + 2 * fi;
+        if (col < cvalid) {
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
+                    if (row < rvalid) {
+                        const long long off = (long long)row * ldc + col;
+                        x3_f2 v2;
+                        v2[0] = acc[a][0][r];
+                        v2[1] = acc[a][1][r];
+                        if constexpr (MODE == BD_RELU) {
+                            v2[0] = v2[0] > 0.f ? v2[0] : 0.f;
+                            v2[1] = v2[1] > 0.f ? v2[1] : 0.f;
+                        } else if constexpr (MODE == BD_SHRINK) {
+                            v2[0] = shrink(v2[0], lambda);
+                            v2[1] = shrink(v2[1], lambda);
+                        } else if constexpr (MODE == BD_MASK) {
+                            const float2 m = *reinterpret_cast<const float2*>(aux + off);
+                            v2[0] = m.x > 0.f ? v2[0] : 0.f;
+                            v2[1] = m.y > 0.f ? v2[1] : 0.f;
+                        }
+                        // (plain store: the next product of the chain, or the inverse transform, reads these rows back)
+                        *reinterpret_cast<x3_f2*>(cbase + off) = v2;
+                    }
+                }
+        }
+    }
+};
+
+// y[r][k ob + :] = f(x[r][k ib + :] * w[k])
+template <int MODE>
+__global__ __launch_bounds__(XT, 3) void spec_bdmlp_fwd_kernel(BlockParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.nb, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int k = t.batch, r0 = t.tm * XM, n0 = t.tn * XN;
+    const long long ci = (long long)p.nb * p.ib, co = (long long)p.nb * p.ob;
+    RowStager as;
+    as.base = p.a + ((long long)r0 * ci + (long long)k * p.ib) * 2;
+    as.ld = 2 * ci;
+    as.rows = p.rows - r0;
+    as.kvalid = 2 * p.ib;
+    CplxStager<false> bs;
+    bs.base = p.b + ((long long)k * p.ib * p.ob + n0 / 2) * 2;
+    bs.ldk = p.ob;
+    bs.kk_hi = p.ib;
+    bs.ovalid = p.ob - n0 / 2;
+    const BlockEpi<MODE> epi{p.dst + ((long long)r0 * co + (long long)k * p.ob) * 2 + n0, 2 * co, nullptr, p.lambda};
+    x3_tile(as, bs, 0, (2 * p.ib + XK - 1) / XK, p.rows - r0, 2 * p.ob - n0, epi, lds_x3);
+}
+
+// gx[r][k ib + :] = f(gy[r][k ob + :] * conj(w[k])^T)
+template <int MODE>
+__global__ __launch_bounds__(XT, 3) void spec_bdmlp_dgrad_kernel(BlockParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.nb, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int k = t.batch, r0 = t.tm * XM, n0 = t.tn * XN;
+    const long long ci = (long long)p.nb * p.ib, co = (long long)p.nb * p.ob;
+    RowStager as;
+    as.base = p.a + ((long long)r0 * co + (long long)k * p.ob) * 2;
+    as.ld = 2 * co;
+    as.rows = p.rows - r0;
+    as.kvalid = 2 * p.ob;
+    DgradStager bs;
+    bs.base = p.b + ((long long)k * p.ib * p.ob + (long long)(n0 / 2) * p.ob) * 2;
+    bs.O = p.ob;
+    bs.ivalid = p.ib - n0 / 2;
+    const long long off = ((long long)r0 * ci + (long long)k * p.ib) * 2 + n0;
+    const BlockEpi<MODE> epi{p.dst + off, 2 * ci, MODE == BD_MASK ? p.aux + off : nullptr, 0.f};
+    x3_tile(as, bs, 0, (2 * p.ob + XK - 1) / XK, p.rows - r0, 2 * p.ib - n0, epi, lds_x3);
+}
+
+// part[g][k][i][:] = sum over the rows r of group g of conj(x[r][k ib + i]) gy[r][k ob + :]   (batch index = g * nb + k)
+__global__ __launch_bounds__(XT, 3) void spec_bdmlp_wgrad_kernel(BlockParams p) {
+    extern __shared__ __attribute__((aligned(16))) char lds_x3[];
+    const TileId t = decode_block(p.nb * p.ngroups, p.tiles_m, p.tiles_n);
+    if (!t.valid) return;
+    const int g = t.batch / p.nb, k = t.batch - g * p.nb;
+    const int i0 = t.tm * XM, n0 = t.tn * XN;
+    const long long ci = (long long)p.nb * p.ib, co = (long long)p.nb * p.ob;
+    const long long rbeg = (long long)g * p.rg;
+    const int rcnt = p.rows - rbeg < p.rg ? (int)(p.rows - rbeg) : p.rg;
+    ChanKStager<false, false> as;
+    as.base = p.a + (rbeg * ci + (long long)k * p.ib + i0) * 2;
+    as.C = ci;
+    as.r_hi = rcnt;
+    as.cvalid = p.ib - i0;
+    CplxStager<true> bs;
+    bs.base = p.b + (rbeg * co + (long long)k * p.ob + n0 / 2) * 2;
+    bs.ldk = co;
+    bs.kk_hi = rcnt;
+    bs.ovalid = p.ob - n0 / 2;
+    const StoreEpi epi{p.dst + (((long long)g * p.nb + k) * p.ib + i0) * 2 * p.ob + n0, 2LL * p.ob};
+    x3_tile(as, bs, 0, (2 * rcnt + XK - 1) / XK, p.ib - i0, 2 * p.ob - n0, epi, lds_x3);
+}
+
+// out = gy where the same component of the saved soft-shrink output s is non-zero, else 0: softshrink' read off its output
+__global__ void spec_bdmlp_mask_kernel(const float4* __restrict__ gy, const float4* __restrict__ s, float4* __restrict__ out,
+                                       long long n4) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n4) return;
+    const float4 g = gy[e], m = s[e];
+    out[e] = make_float4(m.x != 0.f ? g.x : 0.f, m.y != 0.f ? g.y : 0.f, m.z != 0.f ? g.z : 0.f, m.w != 0.f ? g.w : 0.f);
+}
+
+// rows per group of the block weight gradient: about two workgroups per CU, whole k-steps (16 complex rows)
+int bdmlp_group_rows(int rows, int nb, int ib, int ob) {
+    const long long tiles = (long long)nb * mk::ceil_div(ib, XM) * mk::ceil_div(2 * ob, XN);
+    const long long want = tiles >= 512 ? 1 : 512 / tiles;
+    return (int)(mk::ceil_div_ll(mk::ceil_div_ll(rows, want), 16) * 16);
+}
+
 }  // namespace
 
 static int dh_x3_check(const void* a, const void* b, const void* c, int lloc, int mloc, int batch, int cin, int cout,
@@ -726,6 +874,88 @@ extern "C" int mk_spec_cmlp_bgrad(const float* g, float* gb, void* workspace, in
     MK_LAUNCH_CHECK();
     hipLaunchKernelGGL(spec_cmlp_bgrad_sum_kernel, dim3((unsigned)mk::ceil_div(O2, 256)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const double*>(workspace), gb, lloc, O2);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+static int spec_bdmlp_check(const void* a, const void* b, const void* c, int rows, int nb, int ib, int ob) {
+    MK_REQUIRE(a && b && c, "null pointer");
+    MK_REQUIRE(rows > 0 && nb > 0 && ib > 0 && ob > 0, "bad sizes");
+    MK_REQUIRE(ib % 2 == 0 && ob % 2 == 0, "the block MLP needs even block sizes (block offsets must stay 16-byte aligned)");
+    MK_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "operands must be 16-byte aligned");
+    const long long cmax = (long long)nb * (ib > ob ? ib : ob);
+    // the stagers' 32-bit byte offsets span one row tile of a field (129 rows) and one block's weight panel
+    MK_REQUIRE(129LL * cmax * 8 < (1LL << 31) && (long long)ib * ob * 8 < (1LL << 31),
+               "one row tile of the spectrum and one weight panel must stay below 2^31 bytes");
+    return 0;
+}
+
+static BlockParams bdmlp_params(const float* a, const float* b, float* dst, int rows, int nb, int ib, int ob, int rows_m, int cols) {
+    return BlockParams{a, b, dst, nullptr, rows, nb, ib, ob, mk::ceil_div(rows_m, XM), mk::ceil_div(2 * cols, XN), 0.f, 0, 1};
+}
+
+extern "C" int mk_spec_bdmlp_fwd(const float* x, const float* w, float* y, int rows, int nb, int ib, int ob, int act, float lambda,
+                                 void* stream) {
+    if (int e = spec_bdmlp_check(x, w, y, rows, nb, ib, ob)) return e;
+    MK_REQUIRE(act == 0 || act == 2 || act == 3, "unknown activation (0 none | 2 cartesian ReLU | 3 soft-shrink)");
+    MK_REQUIRE(act != 3 || lambda >= 0.f, "the soft-shrink threshold must not be negative");
+    BlockParams p = bdmlp_params(x, w, y, rows, nb, ib, ob, rows, ob);
+    p.lambda = lambda;
+    const long long nblk = grid_blocks(nb, p.tiles_m, p.tiles_n);
+    if (act == 2) return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_RELU>, nblk, stream, p);
+    if (act == 3) return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_SHRINK>, nblk, stream, p);
+    return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_STORE>, nblk, stream, p);
+}
+
+extern "C" int mk_spec_bdmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int rows, int nb, int ib, int ob,
+                                   int act, void* stream) {
+    if (int e = spec_bdmlp_check(gy, w, gx, rows, nb, ib, ob)) return e;
+    MK_REQUIRE(((uintptr_t)a & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(act == 0 || act == 2, "unknown mask mode (0 none | 2 cartesian ReLU)");
+    MK_REQUIRE((a != nullptr) == (act == 2), "the mask operand and the mask mode go together");
+    BlockParams p = bdmlp_params(gy, w, gx, rows, nb, ib, ob, rows, ib);
+    p.aux = a;
+    return x3_launch(__func__, a ? spec_bdmlp_dgrad_kernel<BD_MASK> : spec_bdmlp_dgrad_kernel<BD_STORE>,
+                     grid_blocks(nb, p.tiles_m, p.tiles_n), stream, p);
+}
+
+extern "C" long long mk_spec_bdmlp_wgrad_workspace(int rows, int nb, int ib, int ob) {
+    if (rows <= 0 || nb <= 0 || ib <= 0 || ob <= 0) return 0;
+    const int ngroups = mk::ceil_div(rows, bdmlp_group_rows(rows, nb, ib, ob));
+    return ngroups > 1 ? (long long)ngroups * nb * ib * ob * 8 : 0;
+}
+
+extern "C" int mk_spec_bdmlp_wgrad(const float* x, const float* gy, float* gw, void* workspace, int rows, int nb, int ib, int ob,
+                                   void* stream) {
+    if (int e = spec_bdmlp_check(x, gy, gw, rows, nb, ib, ob)) return e;
+    BlockParams p = bdmlp_params(x, gy, gw, rows, nb, ib, ob, ib, ob);
+    p.rg = bdmlp_group_rows(rows, nb, ib, ob);
+    p.ngroups = mk::ceil_div(rows, p.rg);
+    const long long cmax = (long long)nb * (ib > ob ? ib : ob);
+    MK_REQUIRE((p.rg + 16LL) * cmax * 8 < (1LL << 31), "one row group of the spectrum must stay below 2^31 bytes");
+    MK_REQUIRE((long long)nb * p.ngroups < 2147483647LL, "too many row groups");
+    if (p.ngroups > 1) {
+        MK_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "the block weight gradient needs its 16-byte aligned workspace");
+        p.dst = static_cast<float*>(workspace);
+    }
+    if (int e = x3_launch(__func__, spec_bdmlp_wgrad_kernel, grid_blocks(nb * p.ngroups, p.tiles_m, p.tiles_n), stream, p)) return e;
+    if (p.ngroups > 1) {
+        const long long n4 = (long long)nb * ib * ob / 2;      // ib, ob even: a whole number of float4
+        hipLaunchKernelGGL(spec_cmlp_group_sum_kernel, dim3((unsigned)mk::ceil_div_ll(n4, 256LL)), dim3(256), 0, (hipStream_t)stream,
+                           static_cast<const float4*>(workspace), reinterpret_cast<float4*>(gw), n4, p.ngroups);
+        MK_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int mk_spec_bdmlp_mask(const float* gy, const float* s, float* out, long long n, void* stream) {
+    MK_REQUIRE(gy && s && out, "null pointer");
+    MK_REQUIRE(n > 0 && n % 4 == 0, "the element count must be a positive multiple of 4 floats");
+    MK_REQUIRE((((uintptr_t)gy | (uintptr_t)s | (uintptr_t)out) & 15) == 0, "operands must be 16-byte aligned");
+    const long long nblk = mk::ceil_div_ll(n / 4, 256LL);
+    MK_REQUIRE(nblk < 2147483647LL, "grid too large");
+    hipLaunchKernelGGL(spec_bdmlp_mask_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(gy), reinterpret_cast<const float4*>(s), reinterpret_cast<float4*>(out), n / 4);
     MK_LAUNCH_CHECK();
     return 0;
 }

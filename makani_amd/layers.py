@@ -713,6 +713,26 @@ class DropPath(nn.Module):
         return drop_path(x, self.drop_prob, self.training)
 
 
+class PatchEmbed(nn.Module):
+    """layers.py:65-83: a strided convolution over non-overlapping patches, ``[B, C, H, W]`` -> ``[B, embed_dim, patches]``."""
+
+    def __init__(self, img_size=(224, 224), patch_size=(16, 16), in_chans=3, embed_dim=768):
+        super().__init__()
+        self.red_img_size = ((img_size[0] // patch_size[0]), (img_size[1] // patch_size[1]))
+        self.img_size = img_size
+        self.patch_size = patch_size
+        self.num_patches = self.red_img_size[0] * self.red_img_size[1]
+        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size, bias=True)
+        self.proj.weight.is_shared_mp = ["spatial"]
+        self.proj.bias.is_shared_mp = ["spatial"]
+
+    def forward(self, x):
+        H, W = x.shape[-2], x.shape[-1]
+        assert H == self.img_size[0] and W == self.img_size[1], \
+            f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        return self.proj(x).flatten(2)
+
+
 class EncoderDecoder(nn.Module):
     """layers.py:86-133."""
 

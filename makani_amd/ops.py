@@ -1113,6 +1113,162 @@ def spec_channel_mlp(c, weights, biases, wout, batch, act, per_degree, l_off=0, 
                                  *weights, *biases, wout)
 
 
+# ----------------------------------------------------------------------------
+# block-diagonal complex MLP on the dense planar spectrum (AFNO2D, mk_spec_bdmlp_*)
+# ----------------------------------------------------------------------------
+# The fused path is the default by the rule of DESIGN section 19: no row of tools/afno_bench.py is slower than the torch
+# formulation.  It still needs the HIP planar transforms (MK_PLANAR_FFT=hip).
+AFNO_DEFAULT = "hip"
+
+
+def afno_hip():
+    """``MK_AFNO=hip|torch`` (read at call time): ``AFNO2D`` on the HIP planar transforms with the ``mk_spec_bdmlp_*`` block MLP
+    in between, or the reference's formulation in torch ops."""
+    mode = os.environ.get("MK_AFNO", AFNO_DEFAULT)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"unknown MK_AFNO {mode!r} (hip | torch)")
+    return mode == "hip"
+
+
+def _bdmlp_args(x, w, cols):
+    """``x``: contiguous complex64 field whose last axis is a whole number of ``nb * cols`` channel groups; ``w``: complex64
+    ``[nb, ib, ob]``; ``cols``: which of the panel's axes the field's channels are (1: ib, 2: ob).  -> rows, nb, ib, ob."""
+    _need_cuda(x, w)
+    assert x.dtype == torch.complex64 and x.is_contiguous() and x.dim() >= 1, "contiguous complex64 field"
+    assert w.dtype == torch.complex64 and w.is_contiguous() and w.dim() == 3, "contiguous complex64 [nb, ib, ob] weight"
+    nb, ib, ob = w.shape
+    chans = nb * w.shape[cols]
+    assert x.shape[-1] % chans == 0, "block MLP operand shapes do not match"
+    return x.numel() // chans, nb, ib, ob
+
+
+def _bdmlp_out(out, x, chans_in, chans_out):
+    shape = tuple(x.shape[:-1]) + (x.shape[-1] // chans_in * chans_out,)
+    if out is None:
+        return torch.empty(shape, dtype=torch.complex64, device=x.device)
+    assert tuple(out.shape) == shape and out.dtype == torch.complex64 and out.is_contiguous() and out.device == x.device
+    return out
+
+
+def spec_bdmlp_mask_raw(gy, s, out=None):
+    """``gy`` where the same component (real / imaginary) of ``s`` is non-zero, else 0: the gradient through a soft-shrink whose
+    saved output is ``s``.  ``out`` may be ``gy`` itself."""
+    _need_cuda(gy, s)
+    assert gy.dtype == s.dtype == torch.complex64 and gy.is_contiguous() and s.is_contiguous() and gy.shape == s.shape
+    out = torch.empty_like(gy) if out is None else out
+    assert out.dtype == torch.complex64 and out.is_contiguous() and out.shape == gy.shape and out.device == gy.device
+    _lib.check(_lib.load().mk_spec_bdmlp_mask(gy.data_ptr(), s.data_ptr(), out.data_ptr(), 2 * gy.numel(), _stream()),
+               "mk_spec_bdmlp_mask")
+    return out
+
+
+def spec_bdmlp_fwd_raw(x, w, act=0, lam=0.0, out=None):
+    """y[r, k * ob + o] = act(sum_i x[r, k * ib + i] w[k, i, o]) on the rows of the dense spectrum ``[L, M, B * nb * ib]``; ``w``
+    complex64 ``[nb, ib, ob]``; ``act`` 0 | 2 | 3 (none | ReLU on both components | soft-shrink with threshold ``lam`` on both)."""
+    rows, nb, ib, ob = _bdmlp_args(x, w, 1)
+    y = _bdmlp_out(out, x, nb * ib, nb * ob)
+    _lib.check(_lib.load().mk_spec_bdmlp_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), rows, nb, ib, ob, int(act), float(lam),
+                                             _stream()), "mk_spec_bdmlp_fwd")
+    return y
+
+
+def spec_bdmlp_dgrad_raw(gy, w, a=None, s=None, out=None):
+    """gx = (gy' conj(w)^T) * relu'(a): ``a`` the saved ReLU output ``[L, M, B * nb * ib]`` of the layer in front or None; ``s``
+    the saved soft-shrink output of this layer or None -- with it gy' is ``spec_bdmlp_mask_raw(gy, s)`` (one more pass)."""
+    rows, nb, ib, ob = _bdmlp_args(gy, w, 2)
+    if s is not None:
+        gy = spec_bdmlp_mask_raw(gy, s)
+    ap = 0
+    if a is not None:
+        assert _bdmlp_args(a, w, 1) == (rows, nb, ib, ob)
+        ap = a.data_ptr()
+    gx = _bdmlp_out(out, gy, nb * ob, nb * ib)
+    _lib.check(_lib.load().mk_spec_bdmlp_dgrad(gy.data_ptr(), w.data_ptr(), ap, gx.data_ptr(), rows, nb, ib, ob, 2 if ap else 0,
+                                               _stream()), "mk_spec_bdmlp_dgrad")
+    return gx
+
+
+def spec_bdmlp_wgrad_raw(x, gy, batch, num_blocks, s=None):
+    """gw[k, i, o] = sum_r conj(x[r, k * ib + i]) gy'[r, k * ob + o] -> complex64 ``[nb, ib, ob]`` for fields ``[L, M, B * nb * ib]``
+    and ``[L, M, B * nb * ob]``; ``s`` as for the data gradient.  Partial panels are added in a fixed order: the same bits on
+    every run."""
+    _need_cuda(x, gy)
+    assert x.dtype == gy.dtype == torch.complex64 and x.is_contiguous() and gy.is_contiguous() and x.shape[:-1] == gy.shape[:-1]
+    nb, per = int(num_blocks), int(batch) * int(num_blocks)
+    assert x.shape[-1] % per == 0 and gy.shape[-1] % per == 0, "block MLP operand shapes do not match"
+    ib, ob = x.shape[-1] // per, gy.shape[-1] // per
+    rows = x.numel() // (nb * ib)
+    if s is not None:
+        gy = spec_bdmlp_mask_raw(gy, s)
+    lib = _lib.load()
+    gw = torch.empty((nb, ib, ob), dtype=torch.complex64, device=x.device)
+    nbytes = lib.mk_spec_bdmlp_wgrad_workspace(rows, nb, ib, ob)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+    _lib.check(lib.mk_spec_bdmlp_wgrad(x.data_ptr(), gy.data_ptr(), gw.data_ptr(), ws.data_ptr() if nbytes else 0, rows, nb, ib, ob,
+                                       _stream()), "mk_spec_bdmlp_wgrad")
+    return gw
+
+
+def _block_weight(w):
+    """The reference's real ``[nb, ib, ob, 2]`` parameter as the kernels' complex64 ``[nb, ib, ob]``, taken as it is."""
+    assert w.dim() == 4 and w.shape[-1] == 2 and w.dtype == torch.float32, "fp32 [nb, ib, ob, 2] block weight"
+    return torch.view_as_complex(w.detach().contiguous())
+
+
+class _SpecBlockMLP(torch.autograd.Function):
+    """``softshrink(relu_c(c w1) w2)`` per channel block on the dense spectrum.  Saves the input spectrum, the hidden activation
+    (the second product's input and, by its signs, relu') and the output (by its zeros, softshrink')."""
+
+    @staticmethod
+    def forward(ctx, c, w1, w2, batch, nb, lam):
+        h = spec_bdmlp_fwd_raw(c, _block_weight(w1), 2)
+        y = spec_bdmlp_fwd_raw(h, _block_weight(w2), 3, lam)
+        ctx.save_for_backward(c, h, y, w1, w2)
+        ctx.args = (batch, nb)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        batch, nb = ctx.args
+        c, h, y, w1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = spec_bdmlp_mask_raw(gy.contiguous(), y)         # one masked copy serves both gradients of the second layer
+        gw2 = torch.view_as_real(spec_bdmlp_wgrad_raw(h, g, batch, nb)) if need[2] else None
+        gc = gw1 = None
+        if need[0] or need[1]:
+            gh = spec_bdmlp_dgrad_raw(g, _block_weight(w2), a=h)
+            if need[1]:
+                gw1 = torch.view_as_real(spec_bdmlp_wgrad_raw(c, gh, batch, nb))
+            if need[0]:
+                gc = spec_bdmlp_dgrad_raw(gh, _block_weight(w1))
+        return gc, gw1, gw2, None, None, None
+
+
+def _spec_block_mlp_torch(c, w1, w2, batch, nb, lam):
+    """The same function in torch ops (CPU tensors)."""
+    L, M = c.shape[0], c.shape[1]
+    x = c.reshape(L, M, batch, nb, -1)
+    h = torch.einsum("lmbki,kio->lmbko", x, torch.view_as_complex(w1.contiguous()))
+    h = torch.complex(torch.relu(h.real), torch.relu(h.imag))
+    y = torch.einsum("lmbki,kio->lmbko", h, torch.view_as_complex(w2.contiguous()))
+    y = torch.view_as_complex(torch.nn.functional.softshrink(torch.view_as_real(y), lambd=lam))
+    return y.reshape(L, M, -1)
+
+
+def spec_block_mlp(c, w1, w2, batch, num_blocks, lam):
+    """AFNO's filter arithmetic on the dense private spectrum ``c`` ``[L, M, B * C]`` (complex64): per channel block k of
+    ``C / num_blocks`` channels ``softshrink(relu_c(c_k w1[k]) w2[k], lam)``, ReLU and soft-shrink on both components.  ``w1``
+    ``[nb, bs, hb, 2]``, ``w2`` ``[nb, hb, bs, 2]``: the reference's real fp32 parameters; their gradients come back in that shape.
+    CUDA tensors run on the ``mk_spec_bdmlp_*`` kernels (even ``bs`` and ``hb``), CPU tensors on torch ops."""
+    nb = int(num_blocks)
+    assert c.dim() == 3 and c.shape[2] % (batch * nb) == 0 and w1.dim() == 4 and w2.dim() == 4
+    bs = c.shape[2] // (batch * nb)
+    assert w1.shape[0] == w2.shape[0] == nb and w1.shape[1] == w2.shape[2] == bs and w1.shape[2] == w2.shape[1], "block weight shapes"
+    if not c.is_cuda:
+        return _spec_block_mlp_torch(c, w1, w2, batch, nb, lam)
+    return _SpecBlockMLP.apply(c.contiguous(), w1, w2, int(batch), nb, float(lam))
+
+
 def rfft(x, twiddles, mmax, kmajor=False, scale=None):
     """``scale``: the factor on every mode; None = the SHT's 2 pi / nlon."""
     return _RFFT.apply(x, twiddles, mmax, kmajor, None, scale)
