@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_checks import bf16_ulp as _bf16_ulp
 from test_afno_cpu import NET_KW, build, check_against_fixture, ref, rel as trel  # noqa: F401  (ref: the fixture)
 
 pytestmark = pytest.mark.gpu
@@ -255,8 +256,6 @@ def test_afno2d_fused_against_float64_chain(dev, monkeypatch, B, C, nb, H, W, fr
     assert errs[worst] < GRAD_TOL, (worst, errs[worst])
 
 
-def _bf16_ulp(v):
-    return torch.exp2(torch.floor(torch.log2(v)) - 7)
 
 
 def test_afno2d_bf16_input(dev, monkeypatch):

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as kc
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
@@ -103,6 +105,146 @@ def test_fft_adjoint_pairs(dev, bc, nlat, nlon, mmax):
     zr = torch.fft.irfft(cc.permute(2, 1, 0), n=nlon, dim=-1, norm="forward")
     (gcref,) = torch.autograd.grad(zr, cc, gy.cpu().double())
     assert rel(gc.cpu().numpy(), gcref.numpy()) < TOL
+
+
+# the dispatch table against numpy, through the C ABI with guarded outputs and poisoned inputs (tests/kernel_checks.py)
+FFT_SCALES = (1.0, 0.5, 0.25)          # scale0, scale_m, scale_h: distinct, so a kernel that swaps them fails
+
+
+def _mode_scales(nlon, mmax):
+    s = np.full(mmax, FFT_SCALES[1])
+    s[0] = FFT_SCALES[0]
+    if mmax == nlon // 2 + 1:
+        s[-1] = FFT_SCALES[2]
+    return s
+
+
+def fft_mmax_values(nlon):
+    """1, an odd value near the middle and all modes including Nyquist (nlon = 2 has only the two ends; nlon = 6 gives 1, 3, 4)."""
+    h = nlon // 2
+    return sorted({1, min(h + 1, ((h + 1) // 2) | 1), h + 1})
+
+
+def fft_plan_errors(dev, nlon, mmaxes, bcs=(5, 19), nlat=3):
+    """Runs ``mk_rfft_ex`` (fp32 and bf16 rows) and ``mk_irfft_ex`` for one length over ``bcs`` x ``mmaxes`` x both Fourier-row
+    layouts with guarded outputs and poisoned inputs, three distinct scales, and compares with ``numpy.fft`` in float64.
+    Returns (worst per-row relative L2 error of the analysis, of the synthesis); guard bands and finiteness are asserted here."""
+    from makani_amd import _lib, ops
+    lib = _lib.load()
+    s0, sm, sh = FFT_SCALES
+    h = nlon // 2
+    tw = kc.poisoned(ops.fft_twiddles(nlon), dev)
+    rng = np.random.default_rng(1000 + nlon)
+    worst_a = worst_s = 0.0
+    for bc in bcs:
+        # a mean away from zero keeps the zero mode of every row (all there is at mmax = 1) away from a cancelling sum
+        x32 = torch.from_numpy((rng.standard_normal((bc, nlat, nlon)) + 1.5).astype(np.float32))
+        spec = (rng.standard_normal((bc, nlat, h + 1)) + 1j * rng.standard_normal((bc, nlat, h + 1))).astype(np.complex64)
+        for dtype in (torch.float32, torch.bfloat16):
+            xh = x32.to(dtype)
+            xd = kc.poisoned(xh, dev)
+            full = np.fft.rfft(xh.double().numpy(), axis=-1)
+            for mmax in mmaxes:
+                want = full[..., :mmax] * _mode_scales(nlon, mmax)
+                for layout in (0, 1):
+                    shape = (nlat, mmax, bc) if layout else (mmax, nlat, bc)
+                    xf, check = kc.guarded(shape, torch.complex64, dev)
+                    what = f"rfft nlon={nlon} bc={bc} mmax={mmax} layout={layout} {dtype}"
+                    _lib.check(lib.mk_rfft_ex(xd.data_ptr(), int(dtype == torch.bfloat16), xf.data_ptr(), tw.data_ptr(), bc, nlat,
+                                              nlon, mmax, s0, sm, sh, layout, ops._stream()), what)
+                    torch.cuda.synchronize()
+                    check(what)
+                    got = xf.cpu().numpy().transpose(2, 0, 1) if layout else xf.cpu().numpy().transpose(2, 1, 0)
+                    worst_a = max(worst_a, float(kc.row_rel(got, want).max()))
+        for mmax in mmaxes:
+            # non-zero imaginary parts at mode 0 and at Nyquist: the transform must ignore them
+            xs = np.zeros((bc, nlat, h + 1), dtype=np.complex128)
+            xs[..., :mmax] = spec[..., :mmax].astype(np.complex128) * _mode_scales(nlon, mmax)
+            xs[..., 0] = xs[..., 0].real
+            xs[..., h] = xs[..., h].real
+            want = np.fft.irfft(xs, n=nlon, axis=-1, norm="forward")
+            for layout in (0, 1):
+                src = spec[..., :mmax].transpose(1, 2, 0) if layout else spec[..., :mmax].transpose(2, 1, 0)
+                xfd = kc.poisoned(torch.from_numpy(np.ascontiguousarray(src)), dev)
+                x, check = kc.guarded((bc, nlat, nlon), torch.float32, dev)
+                what = f"irfft nlon={nlon} bc={bc} mmax={mmax} layout={layout}"
+                _lib.check(lib.mk_irfft_ex(xfd.data_ptr(), x.data_ptr(), 0, tw.data_ptr(), bc, nlat, nlon, mmax, s0, sm, sh,
+                                           layout, ops._stream()), what)
+                torch.cuda.synchronize()
+                check(what)
+                worst_s = max(worst_s, float(kc.row_rel(x.cpu().numpy(), want).max()))
+    return worst_a, worst_s
+
+
+# Every length the dispatch table plans (MK_FFT_SIZES; half-length 240 and, below 242 modes, 720 only behind MK_FFT_LEGACY=1: the
+# child-process test below) and four that take the generic DFT.  Per length: bc 5 and 19 at nlat 3 (row groups of 16 ragged, and
+# full plus ragged), mmax 1 / an odd middle value / all modes with Nyquist, both Fourier-row layouts, fp32 and bf16 input rows.
+FFT_PLANNED = [16, 32, 64, 90, 96, 128, 180, 240, 256, 360, 512, 720]
+FFT_GENERIC = [2, 6, 36, 100]
+FFT_TABLE = [(n, None) for n in FFT_PLANNED + FFT_GENERIC] + [(1440, (300, 451, 721))]     # above 241 modes: the 720 plan
+
+
+@pytest.mark.parametrize("nlon,mmaxes", FFT_TABLE, ids=[str(n) for n, _ in FFT_TABLE])
+def test_fft_dispatch_table_vs_numpy(dev, nlon, mmaxes):
+    """mk_rfft_ex / mk_irfft_ex against numpy.fft in float64, relative L2 per (bc, k) row, with three DISTINCT scales (a kernel
+    that swaps scale0 / scale_m / scale_h fails), outputs between sentinel bands, inputs and twiddles between NaN bands, and
+    non-zero imaginary parts in the zero and Nyquist modes of the synthesis input (``fft_plan_errors`` above)."""
+    ea, es = fft_plan_errors(dev, nlon, mmaxes or fft_mmax_values(nlon))
+    print(f"[fft table] nlon={nlon}: worst row, analysis {ea:.2e}, synthesis {es:.2e}")
+    assert ea < TOL and es < TOL
+
+
+FFT_LEGACY_CASES = [(480, (1, 121, 241)), (1440, (241,))]      # the 240 plan (the only user of Dft<15>); the 720 plan at 241 modes
+
+
+def _fft_legacy_worker(q):
+    """In a fresh process: the switch is read once per process, so it is set before makani_amd is imported."""
+    import os
+    os.environ["MK_FFT_LEGACY"] = "1"
+    try:
+        from makani_amd import _lib, ops
+        lib = _lib.load()
+        d = torch.device("cuda:0")
+        # the switch is on in this process: bf16 output rows exist in the split kernels only, so the entry point refuses them
+        buf = torch.zeros(2 * 480, dtype=torch.float32, device=d)
+        tw = ops.fft_twiddles(480).to(d)
+        rc = lib.mk_irfft_ex(buf.data_ptr(), buf.data_ptr(), 1, tw.data_ptr(), 1, 1, 480, 241, 1.0, 1.0, 1.0, 0, ops._stream())
+        assert rc != 0 and b"production lengths" in lib.mk_last_error(), "MK_FFT_LEGACY=1 did not switch the split kernels off"
+        q.put(("ok", [fft_plan_errors(d, nlon, mmaxes) for nlon, mmaxes in FFT_LEGACY_CASES]))
+    except BaseException as e:       # report, never hang the parent
+        import traceback
+        q.put(("error", "".join(traceback.format_exception(type(e), e, e.__traceback__))))
+
+
+def test_fft_legacy_plans_vs_numpy(dev):
+    """The same comparison for the plans production lengths reach only with MK_FFT_LEGACY=1, in one fresh child process."""
+    import multiprocessing as mp
+    import queue
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_fft_legacy_worker, args=(q,))
+    p.start()
+    import time
+    deadline = time.monotonic() + 120         # import, library load and ~100 small launches take a few seconds
+    answer = None
+    while answer is None:
+        try:
+            answer = q.get(timeout=1)
+        except queue.Empty:
+            if not p.is_alive() and q.empty():
+                break                          # died without an answer: the exit status below says how
+            if time.monotonic() > deadline:
+                p.kill()
+                p.join()
+                pytest.fail("the child process did not answer in time")
+    p.join(timeout=60)
+    assert answer is not None, f"the child process ended without an answer, exit status {p.exitcode}"
+    status, res = answer
+    assert p.exitcode == 0, f"child exit status {p.exitcode}"
+    assert status == "ok", res
+    for (nlon, mmaxes), (ea, es) in zip(FFT_LEGACY_CASES, res):
+        print(f"[fft table] legacy nlon={nlon} mmax={mmaxes}: worst row, analysis {ea:.2e}, synthesis {es:.2e}")
+        assert ea < TOL and es < TOL
 
 
 # --------------------------------------------------------------------------- Legendre

@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from kernel_checks import bf16_ulp as _bf16_ulp
 from test_kernels_gpu import DH_CASES, rel, tril_mask
 
 pytestmark = pytest.mark.gpu
@@ -265,9 +266,6 @@ def test_fused_equals_fallback_fp32(dev, monkeypatch):
     assert max(e) < 1e-5
 
 
-def _bf16_ulp(v):
-    """Spacing of bf16 (8 significant bits) at the magnitude of ``v``."""
-    return torch.exp2(torch.floor(torch.log2(v)) - 7)
 
 
 def test_fused_equals_fallback_bf16_autocast_and_row_sums(dev, monkeypatch):
