@@ -13,6 +13,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import kernel_checks as kc
 from kernel_checks import bf16_ulp as _bf16_ulp
 from test_kernels_gpu import DH_CASES, rel, tril_mask
 
@@ -123,7 +124,9 @@ def test_kernels_alone(dev, L, M, B, I, O, l_off, m_off, per_degree):
 def test_shared_weight_gradient_over_several_degree_groups(dev):
     """Enough degrees and tiles that a workgroup of the shared weight gradient contracts several degrees (of different row
     counts) and the fixed-order pass adds many partial panels: L = 200 with 136 x 130 channels is 2 x 3 tiles,
-    ceil(1200 / 768) = 2 degrees per group, 100 partial panels; the workspace query must say so."""
+    ceil(1200 / 768) = 2 degrees per group, 100 partial panels; the workspace query must say so.  Held to the whole-tensor
+    norm and, element by element, to ``kernel_checks.x3_elementwise`` (tests/test_x3_guard_gpu.py runs the same shape through
+    the C ABI between guard bands)."""
     from makani_amd import _lib, ops
     L, M, B, I, O = 200, 20, 1, 136, 130
     assert _lib.load().mk_spec_cmlp_wgrad_workspace(L, I, O, 0) == 100 * I * O * 8
@@ -136,6 +139,11 @@ def test_shared_weight_gradient_over_several_degree_groups(dev):
     want = np.einsum("lmbi,lmbo->io", np.conj(np.where(mask, x, 0).astype(np.complex128)), np.where(mask, gy, 0).astype(np.complex128))
     assert rel(gw.cpu().numpy(), want) < TOL
     assert torch.equal(gw, ops.spec_cmlp_wgrad_raw(xd, gyd, B, False))
+    # every element, under the engine's fp32-result criterion; the fixed-order sum of the 100 panels is the slack
+    xm, gm = torch.from_numpy(np.where(mask, x, 0)), torch.from_numpy(np.where(mask, gy, 0))
+    mag = kc.absdot("lmbi,lmbo->io", xm, gm)
+    worst = kc.x3_elementwise(gw.cpu(), torch.from_numpy(want), mag, slack64=kc.x3_slack_sum(100, mag), what="shared wgrad, 100 panels")
+    print(f"[specattn] shared wgrad over 100 panels: worst |err| / (2^-23 mag) {worst:.2f} of {kc.X3_C}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
