@@ -35,6 +35,8 @@
 
 #pragma clang fp contract(off)   // file scope: what is fused is written as fmaf, nothing else is
 
+#include "gelu.h"   // below the pragma: its products and sums stay unfused here, as everything else in this file
+
 namespace {
 
 constexpr int kT = 512;                    // threads per workgroup (8 waves)
@@ -46,10 +48,12 @@ constexpr int kFwdGrid = 1 << 20;          // forward: one tile per workgroup up
 constexpr int kMinTP = 32;                 // the smaller of the two tile widths (fp32 input)
 
 using bf16 = __hip_bfloat16;
+using mk::gelu::Act;
 
 template <int BYTES> struct alignas(BYTES > 16 ? 16 : BYTES) Raw { unsigned int w[BYTES / 4]; };
 
-// N elements of T at p (aligned to min(16, N sizeof(T)) bytes) <-> N floats
+// N elements of T at p (aligned to min(16, N sizeof(T)) bytes) <-> N floats.  Kept apart from IO<T> of stream_io.h: with either
+// spelling of the store for both, kernels here or there came out with other instructions
 template <typename T, int N> __device__ __forceinline__ void load_n(const T* p, float (&v)[N]) {
     const Raw<N * (int)sizeof(T)> r = *reinterpret_cast<const Raw<N * (int)sizeof(T)>*>(p);
     if constexpr (sizeof(T) == 4) {
@@ -84,41 +88,6 @@ __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(bf16* p, float v) { *p = __float2bfloat16(v); }
 __device__ __forceinline__ void zero1(float* p) { *p = 0.f; }
 __device__ __forceinline__ void zero1(bf16* p) { *reinterpret_cast<unsigned short*>(p) = 0; }
-
-// GELU (exact erf form) and its derivative, as in pointwise.hip: erff() where the result is kept in fp32; where it is
-// rounded to bf16, the normal CDF in the Abramowitz-Stegun 7.1.26 form (|error| < 1.5e-7 absolute on erf, three orders below
-// the 2^-9 rounding of the stored value) at a third of the instructions.
-struct PhiPair {
-    float Phi, phi;   // standard normal CDF and PDF
-};
-__device__ __forceinline__ PhiPair normal_cdf_pdf_fast(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float q = fmaf(1.061405429f, t, -1.453152027f);
-    q = fmaf(q, t, 1.421413741f);
-    q = fmaf(q, t, -0.284496736f);
-    q = fmaf(q, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);   // exp(-x^2 / 2)
-    const float half_erfc = 0.5f * q * t * e;                               // Phi(-|x|)
-    PhiPair r;
-    r.Phi = x < 0.f ? half_erfc : 1.0f - half_erfc;
-    r.phi = 0.3989422804014327f * e;
-    return r;
-}
-template <typename T> struct Act;
-template <> struct Act<float> {
-    static __device__ __forceinline__ float gelu(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752440f)); }
-    static __device__ __forceinline__ float gelu_grad(float z) {
-        return 0.5f * (1.f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * __expf(-0.5f * z * z);
-    }
-};
-template <> struct Act<bf16> {
-    static __device__ __forceinline__ float gelu(float z) { return z * normal_cdf_pdf_fast(z).Phi; }
-    static __device__ __forceinline__ float gelu_grad(float z) {
-        const PhiPair c = normal_cdf_pdf_fast(z);
-        return fmaf(z, c.phi, c.Phi);
-    }
-};
 
 // One stream of a tile: rows of TP pixels, served from LDS (row c at lds + c * TP) or, when the tile does not fit, from
 // global memory (row c at glob + c * P, pixels past `np` read as zero).  V = pixels per lane.

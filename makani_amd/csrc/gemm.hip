@@ -20,6 +20,7 @@
 // are dealt to the same XCD (blockIdx % 8) back to back, so the operand panels they
 // share stay in that XCD's L2.
 #include "common.h"
+#include "tile_map.h"
 #include "../../include/makani_amd.h"
 
 #include <cstdlib>
@@ -353,22 +354,8 @@ __device__ __forceinline__ void gemm_tile(const ALoad& al, const BLoad& bl, int 
 // ---------------------------------------------------------------------------
 // block -> (batch, tile_m, tile_n), XCD aware
 // ---------------------------------------------------------------------------
-struct TileId {
-    int batch, tm, tn;
-    bool valid;
-};
-__device__ __forceinline__ TileId decode_block(int nbatch, int tiles_m, int tiles_n) {
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, q = bid >> 3;
-    const int T = tiles_m * tiles_n;
-    TileId t;
-    t.batch = (q / T) * 8 + xcd;
-    const int r = q % T;
-    t.tm = r / tiles_n;
-    t.tn = r - t.tm * tiles_n;
-    t.valid = t.batch < nbatch;
-    return t;
-}
+using mk::decode_block;
+using mk::TileId;
 static inline unsigned grid_blocks(int nbatch, int tiles_m, int tiles_n) {
     return (unsigned)(mk::ceil_div(nbatch, 8) * 8 * tiles_m * tiles_n);
 }

@@ -19,6 +19,7 @@
 // Any W: a row is walked as a scalar head up to the 16-byte boundary of the prediction, an 8-wide vector body
 // (16-byte accesses) and a scalar tail; when the streams of a row disagree on their alignment the row runs scalar.
 #include "common.h"
+#include "stream_io.h"
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
@@ -28,43 +29,14 @@
 namespace {
 
 constexpr int kT = 256;          // threads per workgroup (4 waves)
-constexpr int kE = 8;            // points per lane per step
+constexpr int kE = mk::sio::kVec;  // points per lane per step (the width of IO<T>)
 constexpr int kRows = 16;        // latitude rows per forward workgroup
 constexpr int kK = 2;            // sums per (sample, channel)
 constexpr int kBwdGrid = 8192;   // backward: at most this many workgroups, waves stride over the rows
 
-template <typename T> struct IO;
-template <> struct IO<float> {
-    static __device__ __forceinline__ void load(const float* p, float (&v)[kE]) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[kE]) {
-        reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    }
-    static __device__ __forceinline__ float ld1(const float* p) { return *p; }
-    static __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
-};
-template <> struct IO<__hip_bfloat16> {
-    static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[kE]) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        const unsigned int w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&v)[kE]) {
-        __hip_bfloat16 h[kE];
-#pragma unroll
-        for (int i = 0; i < kE; ++i) h[i] = __float2bfloat16(v[i]);  // round to nearest even, NaN safe
-        *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(h);
-    }
-    static __device__ __forceinline__ float ld1(const __hip_bfloat16* p) { return __bfloat162float(*p); }
-    static __device__ __forceinline__ void st1(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
-};
+using mk::sio::al16;
+using mk::sio::head_points;
+using mk::sio::IO;
 
 template <int P>
 __device__ __forceinline__ void accum(float (&s)[kK], float p, float t) {
@@ -84,15 +56,6 @@ __device__ __forceinline__ float dnorm(float k, float p, float t) {
     const float d = p - t;
     if (P == 2) return k * d;
     return d > 0.f ? k : (d < 0.f ? -k : 0.f);
-}
-
-__device__ __forceinline__ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// scalar points before the 16-byte boundary of a row that starts at p (at most W)
-template <typename T>
-__device__ __forceinline__ int head_points(const T* p, int W) {
-    const int head = (int)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / sizeof(T));
-    return head > W ? W : head;
 }
 
 // partials [nslab][B][C][2]: slab s = blockIdx.x, channel c = blockIdx.y
@@ -156,7 +119,8 @@ __global__ __launch_bounds__(kT) void geo_lp_sums_kernel(const T* __restrict__ p
 #pragma unroll
                 for (int k = 0; k < kK; ++k) acc[b][k] = fma((double)r[b][k], w, acc[b][k]);
         }
-        // fixed-order reduction: lanes by shuffle, then the four waves in order
+        // fixed-order reduction: lanes by shuffle, then the four waves in order; the fold is spelled out in each kernel,
+        // as a shared function it changed the generated code (stream_io.h)
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -176,20 +140,6 @@ __global__ __launch_bounds__(kT) void geo_lp_sums_kernel(const T* __restrict__ p
         }
         __syncthreads();
     }
-}
-
-// sums[i] = sum over slabs of part[slab][i], i over [B][C][2], one wave per i in a fixed order: lane q adds slabs q, q + 64,
-// ... in order, then the lanes fold by the same shuffle tree every time (46 dependent loads per thread otherwise)
-__global__ __launch_bounds__(kT) void geo_lp_finalize(const double* __restrict__ part, double* __restrict__ sums, int nslab,
-                                                      long long n) {
-    const long long i = (long long)blockIdx.x * (kT / 64) + (threadIdx.x >> 6);
-    if (i >= n) return;                                          // wave-uniform
-    const int lane = threadIdx.x & 63;
-    double v = 0.0;
-    for (int q = lane; q < nslab; q += 64) v += part[(long long)q * n + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) sums[i] = v;
 }
 
 // rows = B * C * H rows of W points; wave (blockIdx.x, wave) takes rows blockIdx.x * 4 + wave, + 4 gridDim.x, ...
@@ -280,7 +230,7 @@ extern "C" int mk_geo_lp_sums(const void* pred, int dtype, const float* tar, con
         launch_nb<__hip_bfloat16>((const __hip_bfloat16*)pred, tar, wrow, workspace, p, B, C, H, W, st);
     MK_LAUNCH_CHECK();
     const long long n = (long long)B * C * kK;
-    hipLaunchKernelGGL(geo_lp_finalize, dim3((unsigned)mk::ceil_div_ll(n, kT / 64)), dim3(kT), 0, st, workspace, sums,
+    hipLaunchKernelGGL(slab_finalize_kernel<kT>, dim3((unsigned)mk::ceil_div_ll(n, kT / 64)), dim3(kT), 0, st, workspace, sums,
                        mk::ceil_div(H, kRows), n);
     MK_LAUNCH_CHECK();
     return 0;

@@ -15,6 +15,7 @@
 // Any W: a row is walked as a scalar head up to the 16-byte boundary of the prediction, an 8-wide vector body
 // (16-byte loads) and a scalar tail; when the streams of a row disagree on their alignment the row runs scalar.
 #include "common.h"
+#include "stream_io.h"
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
@@ -24,30 +25,13 @@
 namespace {
 
 constexpr int kT = 256;          // threads per workgroup (4 waves)
-constexpr int kE = 8;            // points per lane per step
+constexpr int kE = mk::sio::kVec;  // points per lane per step (the width of IO<T>)
 constexpr int kRows = 16;        // latitude rows per workgroup
 constexpr int kK = 5;            // sums per (sample, channel)
 
-template <typename T> struct Ld;
-template <> struct Ld<float> {
-    static __device__ __forceinline__ void load(const float* p, float (&v)[kE]) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-    static __device__ __forceinline__ float ld1(const float* p) { return *p; }
-};
-template <> struct Ld<__hip_bfloat16> {
-    static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[kE]) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        const unsigned int w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ float ld1(const __hip_bfloat16* p) { return __bfloat162float(*p); }
-};
+using mk::sio::al16;
+using mk::sio::head_points;
+using mk::sio::IO;
 
 __device__ __forceinline__ void accum(float (&s)[kK], float p, float t, float c) {
     const float d = p - t, pa = p - c, ta = t - c;
@@ -57,8 +41,6 @@ __device__ __forceinline__ void accum(float (&s)[kK], float p, float t, float c)
     s[3] = fmaf(pa, pa, s[3]);
     s[4] = fmaf(ta, ta, s[4]);
 }
-
-__device__ __forceinline__ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // partials [nslab][B][C][5]: slab s = blockIdx.x, channel c = blockIdx.y
 template <typename T, int NB, bool CLIM>
@@ -88,8 +70,7 @@ __global__ __launch_bounds__(kT) void geo_sums_kernel(const T* __restrict__ pred
                 for (int k = 0; k < kK; ++k) r[b][k] = 0.f;
             // head: scalar points up to the prediction's 16-byte boundary; the row is vectorised when every stream of
             // every sample of the pass is 16-byte aligned there (wave-uniform), else walked scalar
-            int head = (int)(((16 - (reinterpret_cast<uintptr_t>(pr) & 15)) & 15) / sizeof(T));
-            if (head > W) head = W;
+            const int head = head_points(pr, W);
             bool vec = !CLIM || al16(cr + head);
 #pragma unroll
             for (int b = 0; b < NB; ++b)
@@ -99,13 +80,13 @@ __global__ __launch_bounds__(kT) void geo_sums_kernel(const T* __restrict__ pred
             for (int j = lane; j < nv; j += 64) {
                 const int i = head + j * kE;
                 float cv[kE];
-                if (CLIM) Ld<float>::load(cr + i, cv);
+                if (CLIM) IO<float>::load(cr + i, cv);
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
                     if (b < nb) {
                         float pv[kE], tv[kE];
-                        Ld<T>::load(pr + b * CHW + i, pv);
-                        Ld<float>::load(tr + b * CHW + i, tv);
+                        IO<T>::load(pr + b * CHW + i, pv);
+                        IO<float>::load(tr + b * CHW + i, tv);
 #pragma unroll
                         for (int e = 0; e < kE; ++e) accum(r[b], pv[e], tv[e], CLIM ? cv[e] : 0.f);
                     }
@@ -119,7 +100,7 @@ __global__ __launch_bounds__(kT) void geo_sums_kernel(const T* __restrict__ pred
                 const float cs = CLIM ? cr[i] : 0.f;
 #pragma unroll
                 for (int b = 0; b < NB; ++b)
-                    if (b < nb) accum(r[b], Ld<T>::ld1(pr + b * CHW + i), tr[b * CHW + i], cs);
+                    if (b < nb) accum(r[b], IO<T>::ld1(pr + b * CHW + i), tr[b * CHW + i], cs);
             }
             const double w = (double)wrow[h];
 #pragma unroll
@@ -127,7 +108,8 @@ __global__ __launch_bounds__(kT) void geo_sums_kernel(const T* __restrict__ pred
 #pragma unroll
                 for (int k = 0; k < kK; ++k) acc[b][k] = fma((double)r[b][k], w, acc[b][k]);
         }
-        // fixed-order reduction: lanes by shuffle, then the four waves in order
+        // fixed-order reduction: lanes by shuffle, then the four waves in order; the fold is spelled out in each kernel,
+        // as a shared function it changed the generated code (stream_io.h)
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll

@@ -3,6 +3,8 @@
 // with hand-counted waits (the compiler drains vmcnt(0) in front of every LDS access it can see while an LDS-DMA is
 // in flight), raw barriers.
 #pragma once
+#include "gelu.h"
+
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
@@ -14,32 +16,11 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// ---- GELU (exact erf form, makani uses nn.GELU()) on the VALU budget of an epilogue --------------------------
-// Phi(x) through erfc(|x|/sqrt2) with the Abramowitz-Stegun 7.1.26 rational-exponential form (|error| < 1.5e-7
-// absolute on erf): 2 transcendentals + ~12 FMAs instead of ~30 instructions of erff().  The results are rounded
-// to bf16 (2^-9 relative) right after.
-struct PhiPair {
-    float Phi, phi;   // standard normal CDF and PDF at x
-};
-__device__ __forceinline__ PhiPair normal_cdf_pdf(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float q = fmaf(1.061405429f, t, -1.453152027f);
-    q = fmaf(q, t, 1.421413741f);
-    q = fmaf(q, t, -0.284496736f);
-    q = fmaf(q, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);   // exp(-x^2/2)
-    const float half_erfc = 0.5f * q * t * e;                               // 0.5 erfc(|x|/sqrt2) = Phi(-|x|)
-    PhiPair r;
-    r.Phi = x < 0.f ? half_erfc : 1.0f - half_erfc;
-    r.phi = 0.3989422804014327f * e;
-    return r;
-}
-__device__ __forceinline__ float gelu_f(float x) { return x * normal_cdf_pdf(x).Phi; }
-__device__ __forceinline__ float gelu_grad_f(float x) {
-    const PhiPair c = normal_cdf_pdf(x);
-    return fmaf(x, c.phi, c.Phi);
-}
+// ---- GELU on the VALU budget of an epilogue: the erfc form of gelu.h; the results are rounded to bf16 right after ----
+using mk::gelu::normal_cdf_pdf;
+using mk::gelu::PhiPair;
+__device__ __forceinline__ float gelu_f(float x) { return mk::gelu::Act<__hip_bfloat16>::gelu(x); }
+__device__ __forceinline__ float gelu_grad_f(float x) { return mk::gelu::Act<__hip_bfloat16>::gelu_grad(x); }
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __uint_as_float((uint32_t)b << 16); }
 __device__ __forceinline__ unsigned short f32_to_bf16_bits(float v) {

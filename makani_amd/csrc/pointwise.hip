@@ -6,6 +6,8 @@
 // Replaces in the reference block: `nn.Conv2d` bias add + `nn.GELU` (layers.py:95-99,158-206),
 // `nn.InstanceNorm2d(eps=1e-6, affine=True)` + `act_layer0` (sfnonet.py:239-253, 375-380).
 #include "common.h"
+#include "gelu.h"
+#include "stream_io.h"
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
@@ -13,79 +15,12 @@
 namespace {
 
 constexpr int kT = 256;          // threads per workgroup
-constexpr int kE = 8;            // elements per thread per step
+constexpr int kE = mk::sio::kVec;  // elements per thread per step (the width of IO<T>)
 constexpr int kSteps = 4;        // steps per workgroup -> 8192 elements per workgroup
 constexpr int kChunk = kT * kE * kSteps;
 
-template <typename T> struct IO;
-template <> struct IO<float> {
-    static __device__ __forceinline__ void load(const float* p, float (&v)[kE]) {
-        const float4 a = reinterpret_cast<const float4*>(p)[0], b = reinterpret_cast<const float4*>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-    static __device__ __forceinline__ void store(float* p, const float (&v)[kE]) {
-        reinterpret_cast<float4*>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4*>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    }
-    static __device__ __forceinline__ float ld1(const float* p) { return *p; }
-    static __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
-};
-template <> struct IO<__hip_bfloat16> {
-    static __device__ __forceinline__ void load(const __hip_bfloat16* p, float (&v)[kE]) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        const unsigned int w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-        }
-    }
-    static __device__ __forceinline__ void store(__hip_bfloat16* p, const float (&v)[kE]) {
-        __hip_bfloat16 h[kE];
-#pragma unroll
-        for (int i = 0; i < kE; ++i) h[i] = __float2bfloat16(v[i]);  // round to nearest even, NaN safe
-        *reinterpret_cast<uint4*>(p) = *reinterpret_cast<const uint4*>(h);
-    }
-    static __device__ __forceinline__ float ld1(const __hip_bfloat16* p) { return __bfloat162float(*p); }
-    static __device__ __forceinline__ void st1(__hip_bfloat16* p, float v) { *p = __float2bfloat16(v); }
-};
-
-// GELU (exact erf form, nn.GELU()) and its derivative.  fp32 fields: erff().  bf16 fields: the normal CDF through
-// erfc(|z|/sqrt2) in the Abramowitz-Stegun 7.1.26 rational-exponential form (|error| < 1.5e-7 absolute on erf, three orders
-// below the 2^-9 rounding of the stored value): 2 transcendentals + ~12 FMAs instead of erff()'s ~35 instructions plus a
-// separate exp for the derivative -- with erff() the norm+GELU passes were VALU-bound (the backward sums pass ran at
-// 3.3 TB/s against 5.4 TB/s for the same pass without the activation).
-struct PhiPair {
-    float Phi, phi;   // standard normal CDF and PDF
-};
-__device__ __forceinline__ PhiPair normal_cdf_pdf_fast(float x) {
-    const float z = fabsf(x) * 0.70710678118654752f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-    float q = fmaf(1.061405429f, t, -1.453152027f);
-    q = fmaf(q, t, 1.421413741f);
-    q = fmaf(q, t, -0.284496736f);
-    q = fmaf(q, t, 0.254829592f);
-    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);   // exp(-x^2 / 2)
-    const float half_erfc = 0.5f * q * t * e;                               // Phi(-|x|)
-    PhiPair r;
-    r.Phi = x < 0.f ? half_erfc : 1.0f - half_erfc;
-    r.phi = 0.3989422804014327f * e;
-    return r;
-}
-template <typename T> struct Act;
-template <> struct Act<float> {
-    static __device__ __forceinline__ float gelu(float z) { return 0.5f * z * (1.f + erff(z * 0.70710678118654752440f)); }
-    static __device__ __forceinline__ float gelu_grad(float z) {
-        return 0.5f * (1.f + erff(z * 0.70710678118654752440f)) + z * 0.39894228040143267794f * __expf(-0.5f * z * z);
-    }
-};
-template <> struct Act<__hip_bfloat16> {
-    static __device__ __forceinline__ float gelu(float z) { return z * normal_cdf_pdf_fast(z).Phi; }
-    static __device__ __forceinline__ float gelu_grad(float z) {
-        const PhiPair c = normal_cdf_pdf_fast(z);
-        return fmaf(z, c.phi, c.Phi);
-    }
-};
+using mk::gelu::Act;
+using mk::sio::IO;
 
 // visit the elements [p0, p1) of one row in vectors of kE (plus a scalar tail); F(offset, float(&)[kE], n)
 template <typename T, class F>
@@ -101,6 +36,7 @@ __device__ __forceinline__ void for_chunk(long long P, F&& f) {
     }
 }
 
+// the lane fold is spelled out here: as a shared function it changed the generated code (stream_io.h)
 __device__ __forceinline__ float block_sum(float v, float* red) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

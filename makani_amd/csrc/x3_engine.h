@@ -34,6 +34,7 @@
 // (the Legendre tables) are laid out once, tile by tile, so staging them is a straight walk over 16 KB.
 #pragma once
 #include "common.h"
+#include "tile_map.h"
 #include "../../include/makani_amd.h"
 
 #include <cstdint>
@@ -379,23 +380,9 @@ struct AtomicEpi {
     }
 };
 
-// block -> (batch, tile_m, tile_n): all tiles of one batch index on one XCD (blockIdx % 8), back to back
-struct TileId {
-    int batch, tm, tn;
-    bool valid;
-};
-__device__ __forceinline__ TileId decode_block(int nbatch, int tiles_m, int tiles_n) {
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, q = bid >> 3;
-    const int T = tiles_m * tiles_n;
-    TileId t;
-    t.batch = (q / T) * 8 + xcd;
-    const int r = q % T;
-    t.tm = r / tiles_n;
-    t.tn = r - t.tm * tiles_n;
-    t.valid = t.batch < nbatch;
-    return t;
-}
+// block -> (batch, tile_m, tile_n) by tile_map.h, and the grid it expects
+using mk::decode_block;
+using mk::TileId;
 [[maybe_unused]] inline long long grid_blocks(int nbatch, int tiles_m, int tiles_n) {
     return (long long)mk::ceil_div(nbatch, 8) * 8 * tiles_m * tiles_n;
 }

@@ -19,6 +19,7 @@
 // several steps.  Any W, any element-aligned output.  Items are strided over a grid capped as in preproc.hip.  No
 // atomics, no allocation, nothing that waits on the host.
 #include "common.h"
+#include "stream_io.h"
 #include "../../include/makani_amd.h"
 
 #include <cstdint>
@@ -35,16 +36,13 @@ constexpr int kRowsMax = 32;     // rows per item: from here halved down to kRow
 constexpr int kRowsMin = 8;
 constexpr int kWant = 1024;      // workgroups that fill the 256 CUs four times
 
+using mk::sio::head_points;
+
 // the one arithmetic expression of a point, used by head, body and tail alike: a rounded product, then a rounded sum
 // (contraction is off, see above)
 __device__ __forceinline__ float point(float a, float b, float c) {
     const float bc = b * c;
     return a + bc;
-}
-
-__device__ __forceinline__ int head_points(const float* p, int W) {
-    const int head = (int)(((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / sizeof(float));
-    return head > W ? W : head;
 }
 
 // items = n * nchunk * ntile, item = (time * nchunk + chunk) * ntile + tile

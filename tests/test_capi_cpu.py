@@ -30,6 +30,27 @@ def test_library_exports_every_declared_symbol():
     assert lib.mk_version() >= 100
 
 
+def test_build_header_list_is_what_the_sources_include():
+    """build.HEADERS feeds the source digest behind stale(): a header that a source includes and the list lacks would let an
+    edit of it pass unseen and an old library run, a listed header that nothing includes is dead weight.  The list must be
+    the set of quoted includes of build.SOURCES, followed through the headers themselves."""
+    from makani_amd import build
+
+    def norm(path):
+        return os.path.normpath(os.path.relpath(path, build.CSRC))
+
+    seen, todo = set(), [os.path.join(build.CSRC, s) for s in build.SOURCES]
+    while todo:
+        path = todo.pop()
+        for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(path).read(), flags=re.M):
+            target = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+            if norm(target) not in seen:
+                seen.add(norm(target))
+                todo.append(target)
+    assert seen == {norm(os.path.join(build.CSRC, h)) for h in build.HEADERS}
+    assert len(build.HEADERS) == len(set(build.HEADERS))
+
+
 @pytest.mark.parametrize("grid", ["equiangular", "legendre-gauss"])
 @pytest.mark.parametrize("nlat", [2, 3, 33, 240, 721])
 def test_quadrature_matches_oracle(grid, nlat):
