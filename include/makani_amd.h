@@ -571,6 +571,32 @@ long long mk_degree_power_workspace(int L, int M, int BC);
 int mk_degree_power(const float* c, double* workspace, double* P, int L, int M, int BC, int l_off, int m_off, void* stream);
 int mk_degree_power_bwd(const float* c, const double* gP, float* gc, int L, int M, int BC, int l_off, int m_off, void* stream);
 
+/* ---- scaled-dot-product attention (csrc/attn.hip): F.scaled_dot_product_attention of the ViT attention module
+ * (makani/models/networks/vit.py:44-55), non-causal, no mask, no dropout.  bf16 operands, fp32 scores, softmax and accumulators:
+ *   o[b,h,i,:] = sum_j P[i,j] v[b,h,j,:],   P = softmax_j(scale q[b,h,i,:] . k[b,h,j,:]),   lse[b,h,i] = ln sum_j exp(scale s_ij).
+ * Every bf16 tensor is a base pointer (16-byte aligned) and three element strides (batch, head, token), each a non-negative
+ * multiple of 8, the token stride at least D; the D axis is contiguous.  `strides` holds them in the order of the pointer
+ * arguments, three per tensor, and is read on the host during the call.  q, k, v may so be the three views of one
+ * [B][N][3][H][D] projection output, o a [B][N][H D] buffer, and dq, dk, dv the views of one [B][N][3][H][D] gradient.
+ * D a multiple of 16 in 16 ... 128 (zero-padded on chip to 64 or 128; a padded element is never read or written); any
+ * Nq, Nk >= 1, independent.  lse, delta [B][H][Nq] fp32 contiguous; mk_attn_fwd takes lse == NULL (nothing stored).
+ * P (fwd, dkv) and dS = P o (dO V^T - delta) (dkv, dq) are rounded to bf16 (nearest even) before their second products;
+ * delta = rowsum(dO o O) is formed from the stored bf16 o.  dq = scale dS K, dk = scale dS^T Q, dv = P^T dO.
+ * One workgroup per (batch, head, tile of 128 queries) in fwd and dq, per (batch, head, tile of 128 keys) in dkv; nothing is
+ * summed across workgroups: no atomics, no waiting on another workgroup, the same inputs give the same bits.  Each call is
+ * one launch on `stream`, allocates nothing, does not synchronise and can be captured.  Unsupported D, strides or alignment
+ * return code 1 before any launch.
+ * mk_attn_info: tiles[6] = (query tile, key tile) of fwd, of dkv and of dq for head size D. */
+int mk_attn_info(int D, int* tiles);
+int mk_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int D,
+                const long long* strides, float scale, void* stream);
+int mk_attn_bwd_delta(const void* o, const void* dO, float* delta, int B, int H, int Nq, int D, const long long* strides,
+                      void* stream);
+int mk_attn_bwd_dkv(const void* q, const void* k, const void* v, const void* dO, const float* lse, const float* delta, void* dk,
+                    void* dv, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream);
+int mk_attn_bwd_dq(const void* q, const void* k, const void* v, const void* dO, const float* lse, const float* delta, void* dq,
+                   int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ Mirrors the reference's interfaces for the hot path only:
 * ``makani_amd.spectral_convolution`` SpectralConv / FactorizedSpectralConv
 * ``makani_amd.sfnonet``              FourierNeuralOperatorBlock / SphericalFourierNeuralOperatorNet
 * ``makani_amd.afnonet``              AFNO2D / Block / AdaptiveFourierNeuralOperatorNet (block-diagonal spectral MLP kernels)
+* ``makani_amd.vit``                  Attention / Block / VisionTransformer (scaled-dot-product attention on HIP MFMA kernels)
 * ``makani_amd.comm``                 h / w / data process groups over torch.distributed (RCCL)
 * ``makani_amd.preprocessor``         Preprocessor2D / get_preprocessor (one-pass HIP input assembly: ``assemble``)
 * ``makani_amd.stepper``              SingleStepWrapper / MultiStepWrapper (the model wrappers of trainer and inferencer)

@@ -137,6 +137,11 @@ SIGNATURES = {
     "mk_degree_power_workspace": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "mk_degree_power": (_c_int, [_vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
     "mk_degree_power_bwd": (_c_int, [_vp, _vp, _vp] + [_c_int] * 5 + [_vp]),
+    "mk_attn_info": (_c_int, [_c_int, _vp]),
+    "mk_attn_fwd": (_c_int, [_vp] * 5 + [_c_int] * 5 + [_vp, _c_float, _vp]),
+    "mk_attn_bwd_delta": (_c_int, [_vp] * 3 + [_c_int] * 4 + [_vp, _vp]),
+    "mk_attn_bwd_dkv": (_c_int, [_vp] * 8 + [_c_int] * 5 + [_vp, _c_float, _vp]),
+    "mk_attn_bwd_dq": (_c_int, [_vp] * 7 + [_c_int] * 5 + [_vp, _c_float, _vp]),
 }
 
 

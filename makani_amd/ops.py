@@ -1938,3 +1938,195 @@ def cos_zenith(eph, sin_lat, cos_lat, lon_rad, out=None):
     _lib.check(_lib.load().mk_cos_zenith(eph.data_ptr(), sin_lat.data_ptr(), cos_lat.data_ptr(), lon_rad.data_ptr(),
                                          out.data_ptr(), n, H, W, _stream()), "mk_cos_zenith")
     return out
+
+
+# ----------------------------------------------------------------------------
+# scaled-dot-product attention (csrc/attn.hip): the attention of the ViT blocks
+# ----------------------------------------------------------------------------
+# The kernels are the default by the rule of DESIGN section 19: no row of tools/attn_bench.py is slower than the torch path
+# (DESIGN section 24).
+ATTN_DEFAULT = "hip"
+
+
+def attn_hip():
+    """``MK_ATTN=hip|torch`` (read at call time): bf16 attention on the ``mk_attn_*`` kernels, or ``F.scaled_dot_product_attention``."""
+    mode = os.environ.get("MK_ATTN", ATTN_DEFAULT)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"unknown MK_ATTN {mode!r} (hip | torch)")
+    return mode == "hip"
+
+
+def attn_info(head_dim):
+    """(query tile, key tile) of the forward, the dK / dV and the dQ kernel at this head size: three pairs."""
+    t = (ctypes.c_int * 6)()
+    _lib.check(_lib.load().mk_attn_info(int(head_dim), ctypes.addressof(t)), "mk_attn_info")
+    return (t[0], t[1]), (t[2], t[3]), (t[4], t[5])
+
+
+def _attn_strides(t):
+    """(batch, head, token) element strides of a ``[B, H, N, D]`` view; an axis of size 1 has no stride of its own."""
+    sb, sh, sn = t.stride(0), t.stride(1), t.stride(2)
+    return (sb if t.shape[0] > 1 else 0, sh if t.shape[1] > 1 else 0, sn if t.shape[2] > 1 else t.shape[3])
+
+
+def _attn_operand_ok(t):
+    if t.dim() != 4 or not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(3) != 1 or t.data_ptr() % 16:
+        return False
+    sb, sh, sn = _attn_strides(t)
+    return min(sb, sh) >= 0 and sb % 8 == 0 and sh % 8 == 0 and sn % 8 == 0 and sn >= t.shape[3]
+
+
+def attention_supported(q, k, v):
+    """True when the kernels take these ``[B, H, N, D]`` views as they are: bf16 on the device, D a multiple of 16 in 16 ... 128 and
+    contiguous, 16-byte aligned, batch / head / token strides multiples of 8 elements."""
+    if not (q.dim() == k.dim() == v.dim() == 4 and k.shape == v.shape and q.shape[:2] == k.shape[:2] and q.shape[3] == k.shape[3]):
+        return False
+    D = q.shape[3]
+    if D % 16 or not 16 <= D <= 128 or min(q.shape[2], k.shape[2], q.shape[0], q.shape[1]) < 1:
+        return False
+    return all(_attn_operand_ok(t) for t in (q, k, v))
+
+
+def _attn_stride_array(*tensors):
+    flat = [s for t in tensors for s in _attn_strides(t)]
+    return (ctypes.c_longlong * len(flat))(*flat)
+
+
+def attn_fwd_raw(q, k, v, o, lse, scale):
+    """``o`` (a ``[B, H, Nq, D]`` view, written in place) and, unless None, ``lse`` ``[B, H, Nq]`` fp32 from ``[B, H, N, D]`` views."""
+    B, H, Nq, D = q.shape
+    st = _attn_stride_array(q, k, v, o)
+    _lib.check(_lib.load().mk_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _ptr(lse), B, H, Nq, k.shape[2], D,
+                                       ctypes.addressof(st), float(scale), _stream()), "mk_attn_fwd")
+
+
+def attn_bwd_raw(q, k, v, o, go, lse, dq, dk, dv, scale):
+    """The three gradients, written in place into the ``[B, H, N, D]`` views ``dq``, ``dk``, ``dv``: delta, then dK / dV, then dQ."""
+    B, H, Nq, D = q.shape
+    Nk = k.shape[2]
+    lib = _lib.load()
+    delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    st = _attn_stride_array(o, go)
+    _lib.check(lib.mk_attn_bwd_delta(o.data_ptr(), go.data_ptr(), delta.data_ptr(), B, H, Nq, D, ctypes.addressof(st), _stream()),
+               "mk_attn_bwd_delta")
+    st = _attn_stride_array(q, k, v, go, dk, dv)
+    _lib.check(lib.mk_attn_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                   dk.data_ptr(), dv.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()),
+               "mk_attn_bwd_dkv")
+    st = _attn_stride_array(q, k, v, go, dq)
+    _lib.check(lib.mk_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                  dq.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()), "mk_attn_bwd_dq")
+
+
+def _attn_grad_out(go):
+    """The upstream gradient as a view the kernels take (a token-major ``[B, N, H D]`` gradient already is one)."""
+    return go if _attn_operand_ok(go) else go.contiguous()
+
+
+class _Attention(torch.autograd.Function):
+    """``softmax(scale q k^T) v`` on ``[B, H, N, D]`` views.  The output and the gradients are token-major buffers ``[B, N, H, D]``
+    seen through a permutation, so the ``transpose(1, 2).reshape(B, N, C)`` behind the op is a view."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        B, H, Nq, D = q.shape
+        o = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        need = any(ctx.needs_input_grad[:3])
+        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if need else None
+        attn_fwd_raw(q, k, v, o, lse, scale)
+        if need:
+            ctx.save_for_backward(q, k, v, o, lse)
+            ctx.scale = scale
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        q, k, v, o, lse = ctx.saved_tensors
+        B, H, Nq, D = q.shape
+        Nk = k.shape[2]
+        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        attn_bwd_raw(q, k, v, o, _attn_grad_out(go), lse, dq, dk, dv, ctx.scale)
+        return dq, dk, dv, None
+
+
+def _qkv_views(qkv, B, N, H, D):
+    return tuple(t.permute(0, 2, 1, 3) for t in qkv.view(B, N, 3, H, D).unbind(2))
+
+
+class _AttentionPacked(torch.autograd.Function):
+    """The same on the projection output ``qkv`` ``[B, N, 3 H D]`` as it stands: q, k, v are three strided views of it, the output
+    is ``[B, N, H D]`` and the gradient one ``[B, N, 3 H D]`` buffer the kernels write in place.  No permuted copy, no cat."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, scale):
+        B, N, C3 = qkv.shape
+        D = C3 // (3 * H)
+        q, k, v = _qkv_views(qkv, B, N, H, D)
+        o = torch.empty(B, N, H * D, dtype=qkv.dtype, device=qkv.device)
+        need = ctx.needs_input_grad[0]
+        lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device) if need else None
+        attn_fwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), lse, scale)
+        if need:
+            ctx.save_for_backward(qkv, o, lse)
+            ctx.args = (H, scale)
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        qkv, o, lse = ctx.saved_tensors
+        H, scale = ctx.args
+        B, N, C3 = qkv.shape
+        D = C3 // (3 * H)
+        q, k, v = _qkv_views(qkv, B, N, H, D)
+        dqkv = torch.empty(B, N, C3, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = _qkv_views(dqkv, B, N, H, D)
+        go = _attn_grad_out(go.reshape(B, N, H, D).permute(0, 2, 1, 3))
+        attn_bwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), go, lse, dq, dk, dv, scale)
+        return dqkv, None, None
+
+
+def _attn_scale(scale, D):
+    return float(scale) if scale is not None else 1.0 / math.sqrt(D)
+
+
+def _attn_autocast(*tensors):
+    """Under device autocast ``F.scaled_dot_product_attention`` takes its operands in the autocast dtype; so do these ops (the
+    fp32 output of a ``qk_norm`` LayerNorm reaches the product as bf16 either way)."""
+    if tensors[0].is_cuda and torch.is_autocast_enabled():
+        dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+        return tuple(t.to(dt) for t in tensors)
+    return tensors
+
+
+def attention(q, k, v, scale=None, dropout_p=0.0):
+    """``F.scaled_dot_product_attention(q, k, v)`` (no mask, not causal) for ``[B, H, N, D]`` views; returns ``[B, H, Nq, D]``.
+    bf16 device tensors that ``attention_supported`` accepts run on the ``mk_attn_*`` kernels under ``MK_ATTN=hip``; fp32 / fp16
+    inputs, CPU tensors, other head sizes or strides, ``dropout_p > 0`` and ``MK_ATTN=torch`` take the torch formulation."""
+    hip = attn_hip()
+    q, k, v = _attn_autocast(q, k, v)
+    if hip and dropout_p == 0.0 and attention_supported(q, k, v):
+        return _Attention.apply(q, k, v, _attn_scale(scale, q.shape[-1]))
+    return torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
+
+
+def attention_packed(qkv, num_heads, scale=None, dropout_p=0.0):
+    """Self-attention on a fused projection output: ``qkv`` ``[B, N, 3 H D]`` laid out as ``[B, N, 3, H, D]`` -> ``[B, N, H D]``.
+    Same dispatch as ``attention``; the HIP path reads q, k, v in place and returns the gradient as one tensor."""
+    if qkv.dim() != 3 or qkv.shape[2] % (3 * int(num_heads)):
+        raise ValueError(f"attention_packed: qkv {tuple(qkv.shape)} must be [B, N, 3 * {num_heads} * D]")
+    B, N, C3 = qkv.shape
+    H = int(num_heads)
+    D = C3 // (3 * H)
+    hip = attn_hip()
+    (qkv,) = _attn_autocast(qkv)
+    if hip and dropout_p == 0.0 and qkv.is_cuda and qkv.dtype == torch.bfloat16:
+        x = qkv if (qkv.stride(2) == 1 and qkv.data_ptr() % 16 == 0) else qkv.contiguous()
+        if attention_supported(*_qkv_views(x.detach(), B, N, H, D)):
+            return _AttentionPacked.apply(x, H, _attn_scale(scale, D))
+    q, k, v = (t.permute(0, 2, 1, 3) for t in qkv.reshape(B, N, 3, H, D).unbind(2))
+    o = torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
+    return o.transpose(1, 2).reshape(B, N, H * D)
