@@ -597,6 +597,39 @@ int mk_attn_bwd_dkv(const void* q, const void* k, const void* v, const void* dO,
 int mk_attn_bwd_dq(const void* q, const void* k, const void* v, const void* dO, const float* lse, const float* delta, void* dq,
                    int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream);
 
+/* ---- layer norm over the TRAILING axis with the residual add fused in (csrc/toknorm.hip): nn.LayerNorm of the ViT blocks
+ * (makani/models/networks/vit.py:86-118) and nn.LayerNorm((h, w)) of AFNO (afnonet.py:249-250).  `rows` rows of L >= 1
+ * contiguous elements; every tensor has its own dtype (0 = fp32, 1 = bf16) and element row stride ld >= L.  Per row
+ *   s = x + r (added in fp32; r NULL: s = x),  mean = sum s / L,  var = sum (s - mean)^2 / L (biased, two passes over the
+ *   on-chip row),  rstd = 1 / sqrt(var + eps),  v = weight (s - mean) rstd + bias   in fp32,
+ * weight, bias fp32 [L], each may be NULL (1 / 0).  Outputs, each may be NULL but not both y and y2: y = v rounded once to
+ * y_dtype; y2 = the same fp32 v rounded once to bf16 (the operand of the next linear under autocast); s_out = s in s_dtype;
+ * stats [rows][2] = (mean, rstd) fp32.
+ * Backward: s is recomputed from x and r (the forward need not have stored it); gy (its dtype), gy2 (bf16) and gs (the
+ * gradient of s_out, its dtype) may each be NULL.  With g = gy + gy2 in fp32, xh = (s - mean) rstd, s1 = sum weight g,
+ * s2 = sum weight g xh over the row:
+ *   gx = rstd (weight g - s1 / L - xh s2 / L) + gs   in x's dtype and ld;  gr (NULL: not written) the same values in r's;
+ *   gwb [2][L] fp32 (NULL: not formed):  row 0 = sum_rows g xh,  row 1 = sum_rows g.
+ * gwb uses no atomics: per-workgroup fp32 partials in `workspace` (mk_token_layernorm_workspace(rows, L) floats, no need to
+ * clear it), added in a fixed order in fp64 by a finishing launch.
+ * Any rows, L >= 1 and any element-aligned pointers and strides: 16-byte vectors when L is a multiple of 8 and every pointer
+ * and row stride is a multiple of 16 bytes, single elements otherwise.  Rows of up to 2048 elements are held in the
+ * registers of one wavefront; longer ones by a workgroup in LDS while they fit (40 944 elements forward, 20 472
+ * backward), and are read again (L2) beyond that.  x and r are read once and every output is written once from / to HBM.
+ * The sums of a row are formed in an order that depends on L only -- not on the alignment or on the row's place -- so a
+ * launch on a subset of the rows gives the bits of that subset (y, gx, stats), and the same inputs give the same bits.
+ * Columns L ... ld - 1 of an output are never written.  No allocation, synchronisation or host copy; can be captured; the
+ * launch configuration depends on the shape, the dtypes and the alignment only. */
+long long mk_token_layernorm_workspace(long long rows, long long L);
+int mk_token_layernorm_fwd(const void* x, int x_dtype, long long x_ld, const void* r, int r_dtype, long long r_ld,
+                           const float* weight, const float* bias, void* y, int y_dtype, long long y_ld, void* y2, long long y2_ld,
+                           void* s_out, int s_dtype, long long s_ld, float* stats, long long rows, long long L, float eps,
+                           void* stream);
+int mk_token_layernorm_bwd(const void* x, int x_dtype, long long x_ld, const void* r, int r_dtype, long long r_ld, const void* gy,
+                           int gy_dtype, long long gy_ld, const void* gy2, long long gy2_ld, const void* gs, int gs_dtype,
+                           long long gs_ld, const float* stats, const float* weight, void* gx, void* gr, float* workspace,
+                           float* gwb, long long rows, long long L, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

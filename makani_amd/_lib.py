@@ -142,6 +142,12 @@ SIGNATURES = {
     "mk_attn_bwd_delta": (_c_int, [_vp] * 3 + [_c_int] * 4 + [_vp, _vp]),
     "mk_attn_bwd_dkv": (_c_int, [_vp] * 8 + [_c_int] * 5 + [_vp, _c_float, _vp]),
     "mk_attn_bwd_dq": (_c_int, [_vp] * 7 + [_c_int] * 5 + [_vp, _c_float, _vp]),
+    "mk_token_layernorm_workspace": (ctypes.c_longlong, [ctypes.c_longlong] * 2),
+    "mk_token_layernorm_fwd": (_c_int, [_vp, _c_int, ctypes.c_longlong] * 2 + [_vp, _vp] + [_vp, _c_int, ctypes.c_longlong]
+                               + [_vp, ctypes.c_longlong] + [_vp, _c_int, ctypes.c_longlong] + [_vp, ctypes.c_longlong,
+                                                                                             ctypes.c_longlong, _c_float, _vp]),
+    "mk_token_layernorm_bwd": (_c_int, [_vp, _c_int, ctypes.c_longlong] * 3 + [_vp, ctypes.c_longlong]
+                               + [_vp, _c_int, ctypes.c_longlong] + [_vp] * 6 + [ctypes.c_longlong] * 2 + [_vp]),
 }
 
 

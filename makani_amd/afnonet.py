@@ -29,7 +29,7 @@ except ImportError:     # loaded by file path (the reference's registry: ``netty
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from makani_amd import comm, ops
-from makani_amd.layers import MLP, Conv1x1, DropPath, InstanceNorm2d, InverseRealFFT2, PatchEmbed, RealFFT2
+from makani_amd.layers import MLP, Conv1x1, DropPath, InstanceNorm2d, InverseRealFFT2, LayerNorm, PatchEmbed, RealFFT2
 from makani_amd.spectral_convolution import ComplexReLU
 
 
@@ -222,7 +222,8 @@ class AdaptiveFourierNeuralOperatorNet(nn.Module):
     """afnonet_v2.py:190-314: patch embedding, position embedding, ``num_layers`` blocks, a 1x1 head and the rearrangement of
     its ``out_chans * p0 * p1`` channels back onto the full grid.  All keywords and defaults of the reference; further
     keywords are tolerated like there.  ``instance_norm`` is this package's ``layers.InstanceNorm2d`` (HIP passes),
-    ``layer_norm`` the reference's ``nn.LayerNorm((h, w))`` in torch."""
+    ``layer_norm`` is ``layers.LayerNorm((h, w))``: the reference's ``nn.LayerNorm`` over the rows of ``h w`` grid points of each
+    (sample, channel), on the ``mk_token_layernorm_*`` kernels under ``MK_TOKEN_NORM=hip``."""
 
     def __init__(self, inp_shape=(720, 1440), patch_size=(16, 16), inp_chans=2, out_chans=2, embed_dim=768, num_layers=12,
                  mlp_ratio=4.0, drop_rate=0.0, drop_path_rate=0.0, num_blocks=16, sparsity_threshold=0.01,
@@ -247,7 +248,7 @@ class AdaptiveFourierNeuralOperatorNet(nn.Module):
         self.h = self.img_size[0] // self.patch_size[0]
         self.w = self.img_size[1] // self.patch_size[1]
         if normalization_layer == "layer_norm":
-            norm_layer = partial(nn.LayerNorm, normalized_shape=(self.h, self.w), eps=1e-6)
+            norm_layer = partial(LayerNorm, normalized_shape=(self.h, self.w), eps=1e-6)
         elif normalization_layer == "instance_norm":
             norm_layer = partial(InstanceNorm2d, num_features=embed_dim, eps=1e-6, affine=True, track_running_stats=False)
         else:

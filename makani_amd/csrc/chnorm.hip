@@ -30,7 +30,6 @@
 
 #include <hip/hip_bf16.h>
 
-#include <atomic>
 #include <cstdint>
 
 #pragma clang fp contract(off)   // file scope: what is fused is written as fmaf, nothing else is
@@ -369,22 +368,6 @@ __global__ __launch_bounds__(256) void chan_layernorm_finish(const float* __rest
     if (lane == 0) gwb[i] = (float)v;
 }
 
-// Dynamic LDS above 64 KB has to be allowed per kernel AND per device: once for each (instantiation, device) pair, checked.
-template <auto Kernel> int raise_lds_limit() {
-    static std::atomic<unsigned long long> done{0};      // one bit per device ordinal (< 64)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
-    const unsigned long long bit = 1ULL << dev;
-    if (done.load(std::memory_order_acquire) & bit) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax) !=
-        hipSuccess) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    done.fetch_or(bit, std::memory_order_release);
-    return 0;
-}
-
 bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 long long bwd_grid(long long ntiles) { return ntiles < kBwdGrid ? ntiles : kBwdGrid; }
@@ -393,7 +376,7 @@ template <typename TI, typename TO, bool GELU>
 int launch_fwd(const void* x, const float* w, const float* b, void* y, float* stats, int B, int C, long long P, float eps,
                hipStream_t st) {
     constexpr int TP = tile_px<TI>();
-    MK_REQUIRE((raise_lds_limit<chan_layernorm_fwd_kernel<TI, TO, GELU>>() == 0), "cannot raise the dynamic LDS limit on this device");
+    MK_REQUIRE((mk::raise_lds_limit<chan_layernorm_fwd_kernel<TI, TO, GELU>>(kLdsMax) == 0), "cannot raise the dynamic LDS limit on this device");
     const long long tps = mk::ceil_div_ll(P, TP), ntiles = tps * B;
     const long long grid = ntiles < kFwdGrid ? ntiles : kFwdGrid;
     const long long want = fwd_lds_fixed<TI>() + (long long)C * TP * (long long)sizeof(TI);
@@ -410,7 +393,7 @@ template <typename TX, typename TG, bool GELU>
 int launch_bwd(const void* x, const void* gy, const float* stats, const float* w, const float* b, void* gx, float* ws,
                float* gwb, int B, int C, long long P, hipStream_t st) {
     constexpr int V = bwd_v<TX, TG>(), TP = kLanes * V;
-    MK_REQUIRE((raise_lds_limit<chan_layernorm_bwd_kernel<TX, TG, GELU>>() == 0), "cannot raise the dynamic LDS limit on this device");
+    MK_REQUIRE((mk::raise_lds_limit<chan_layernorm_bwd_kernel<TX, TG, GELU>>(kLdsMax) == 0), "cannot raise the dynamic LDS limit on this device");
     const long long tps = mk::ceil_div_ll(P, TP), ntiles = tps * B;
     const long long fixed = bwd_lds_fixed(TP);
     const long long want = fixed + 4LL * acc_floats(C) + (long long)C * TP * (long long)(sizeof(TX) + sizeof(TG));

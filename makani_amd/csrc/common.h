@@ -1,6 +1,7 @@
 // Shared helpers for the libmakani_amd.so translation units (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdio>
 #include <string>
 
@@ -30,5 +31,22 @@ void set_error(const std::string& msg);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
+
+// Dynamic LDS above 64 KB has to be allowed per kernel AND per device: once for each (instantiation, device) pair, checked.
+// `bytes` is applied by the first call for a pair and not looked at again: a kernel's callers pass one constant, the most
+// its launches may ever ask for.
+template <auto Kernel> int raise_lds_limit(int bytes) {
+    static std::atomic<unsigned long long> done{0};      // one bit per device ordinal (< 64)
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1;
+    const unsigned long long bit = 1ULL << dev;
+    if (done.load(std::memory_order_acquire) & bit) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return 1;
+    }
+    done.fetch_or(bit, std::memory_order_release);
+    return 0;
+}
 
 }  // namespace mk

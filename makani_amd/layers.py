@@ -694,6 +694,36 @@ class InstanceNorm2d(nn.InstanceNorm2d):
         return ops.instance_norm(x, self.weight, self.bias, self.eps, fuse_gelu, row_sums=row_sums)
 
 
+class LayerNorm(nn.LayerNorm):
+    """``nn.LayerNorm`` (same constructor, parameters and ``state_dict`` entries) over one or more trailing axes on the
+    ``mk_token_layernorm_*`` kernels under ``MK_TOKEN_NORM=hip`` (read and validated on every call).  On the CPU, on inputs that
+    ``ops.token_layer_norm_supported`` declines and with ``MK_TOKEN_NORM=torch`` it is exactly ``nn.LayerNorm.forward``."""
+
+    def hip_ready(self, x):
+        from . import ops
+        return ops.token_norm_hip() and ops.token_layer_norm_supported(x, self.normalized_shape, self.weight, self.bias)
+
+    def forward(self, x):
+        if not self.hip_ready(x):
+            return super().forward(x)
+        from . import ops
+        return ops.token_layer_norm(x, self.weight, self.bias, self.eps, normalized_shape=self.normalized_shape)
+
+    def forward_add(self, x, residual=None, lowp=False, want_sum=False, out_dtype=None):
+        """The norm of ``x + residual`` for callers that fuse: a tuple of ``y`` (``out_dtype``: as ``ops.token_layer_norm``), then
+        its bf16 copy if ``lowp``, then the sum if ``want_sum``.  One launch on the HIP path; the torch formulation elsewhere."""
+        from . import ops
+        if self.hip_ready(x) and (residual is None or (residual.shape == x.shape
+                                                       and ops.token_layer_norm_supported(residual, self.normalized_shape))):
+            out = ops.token_layer_norm(x, self.weight, self.bias, self.eps, residual, out_dtype, lowp, want_sum, self.normalized_shape)
+            return out if isinstance(out, tuple) else (out,)
+        s = x if residual is None else x + residual
+        y = super().forward(s)
+        if out_dtype is not None:
+            y = y.to(out_dtype)
+        return (y,) + ((y.to(torch.bfloat16),) if lowp else ()) + ((s,) if want_sum else ())
+
+
 def drop_path(x, drop_prob=0.0, training=False):
     if drop_prob == 0.0 or not training:
         return x

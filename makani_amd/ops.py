@@ -2130,3 +2130,167 @@ def attention_packed(qkv, num_heads, scale=None, dropout_p=0.0):
     q, k, v = (t.permute(0, 2, 1, 3) for t in qkv.reshape(B, N, 3, H, D).unbind(2))
     o = torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
     return o.transpose(1, 2).reshape(B, N, H * D)
+
+
+# ----------------------------------------------------------------------------
+# layer norm over the trailing axes with the residual add fused in (csrc/toknorm.hip): the norms of ViT and AFNO
+# ----------------------------------------------------------------------------
+# Opt-in by the rule of DESIGN section 19: 8 of the 22 rows of tools/toknorm_bench.py are slower than the torch path (the
+# single-kernel rows at (8100, 768), which are bound by the host, and four of the AFNO rows).
+TOKEN_NORM_DEFAULT = "torch"
+
+
+def token_norm_hip():
+    """``MK_TOKEN_NORM=hip|torch`` (read at call time): trailing-axis layer norms on the ``mk_token_layernorm_*`` kernels, or
+    ``F.layer_norm``."""
+    mode = os.environ.get("MK_TOKEN_NORM", TOKEN_NORM_DEFAULT)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"unknown MK_TOKEN_NORM {mode!r} (hip | torch)")
+    return mode == "hip"
+
+
+def _trailing(normalized_shape):
+    shape = (normalized_shape,) if isinstance(normalized_shape, int) else tuple(normalized_shape)
+    return shape, math.prod(shape)
+
+
+def _rows_contiguous(t, k):
+    """The last ``k`` axes of ``t`` are contiguous among themselves (from the strides: no view is made, this runs on every call)."""
+    want = 1
+    for size, stride in zip(reversed(t.shape[t.dim() - k:]), reversed(t.stride()[t.dim() - k:])):
+        if size != 1 and stride != want:
+            return False
+        want *= size
+    return True
+
+
+def token_layer_norm_supported(x, normalized_shape, weight=None, bias=None):
+    """True for device fp32 / bf16 tensors whose trailing axes are ``normalized_shape``, contiguous among themselves, next to
+    fp32 parameters (or none).  Everything else is the caller's torch path."""
+    shape, L = _trailing(normalized_shape)
+    k = len(shape)
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and k >= 1 and x.dim() >= k):
+        return False
+    if tuple(x.shape[x.dim() - k:]) != shape or x.numel() == 0:
+        return False
+    if any(p is not None and (p.dtype != torch.float32 or not p.is_cuda or tuple(p.shape) != shape) for p in (weight, bias)):
+        return False
+    return _rows_contiguous(x, k)
+
+
+def _token_rows(t, k, L):
+    """``t`` as rows the kernels take, and their element stride: itself where its memory already is ``rows`` rows of ``L``
+    contiguous elements at one stride, a contiguous copy otherwise."""
+    if t.is_contiguous():
+        return t, L
+    if t.dim() == k + 1 and _rows_contiguous(t, k) and (t.shape[0] == 1 or t.stride(0) >= L):
+        return t, (L if t.shape[0] == 1 else t.stride(0))
+    return t.contiguous(), L
+
+
+def _tok3(t, ld=0):
+    """(pointer, dtype code, row stride) of an optional tensor."""
+    return (None, 0, 0) if t is None else (t.data_ptr(), _pw_dtype(t), ld)
+
+
+def token_layernorm_fwd_raw(x, x_ld, r, r_ld, weight, bias, y, y2, s_out, stats, rows, L, eps):
+    """One launch of ``mk_token_layernorm_fwd``; ``y``, ``y2``, ``s_out`` contiguous ``[rows, L]`` outputs or None."""
+    _lib.check(_lib.load().mk_token_layernorm_fwd(*_tok3(x, x_ld), *_tok3(r, r_ld), _ptr(weight), _ptr(bias), *_tok3(y, L), _ptr(y2), L,
+                                                  *_tok3(s_out, L), _ptr(stats), rows, L, float(eps), _stream()),
+               "mk_token_layernorm_fwd")
+
+
+def token_layernorm_bwd_raw(x, x_ld, r, r_ld, gy, gy_ld, gy2, gy2_ld, gs, gs_ld, stats, weight, gx, gr, gwb, rows, L):
+    """``mk_token_layernorm_bwd``: one launch, plus the finishing launch when ``gwb`` ``[2, L]`` is asked for.  ``gx`` / ``gr`` have
+    the layout of ``x`` / ``r``."""
+    lib = _lib.load()
+    ws = None
+    if gwb is not None:
+        ws = torch.empty(lib.mk_token_layernorm_workspace(rows, L), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mk_token_layernorm_bwd(*_tok3(x, x_ld), *_tok3(r, r_ld), *_tok3(gy, gy_ld), _ptr(gy2), gy2_ld, *_tok3(gs, gs_ld),
+                                          stats.data_ptr(), _ptr(weight), gx.data_ptr(), _ptr(gr), _ptr(ws), _ptr(gwb), rows, L,
+                                          _stream()), "mk_token_layernorm_bwd")
+
+
+class _TokenLayerNorm(torch.autograd.Function):
+    """``s = x + residual``, ``y = layer_norm(s)`` over the last ``k`` axes, with up to three results from one launch: ``y``, its
+    bf16 copy ``y2`` (rounded from the same fp32 value) and ``s``.  Saves ``x``, ``residual`` and the per-row (mean, rstd): the
+    backward recomputes ``s``, takes the gradients of all results in one launch and returns those of ``x``, ``residual``, the
+    weight and the bias."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, eps, k, y_dtype, s_dtype, lowp, want_sum):
+        _need_cuda(x)
+        L = math.prod(x.shape[x.dim() - k:])
+        rows = x.numel() // L
+        x, x_ld = _token_rows(x, k, L)
+        r, r_ld = (None, 0) if residual is None else _token_rows(residual, k, L)
+        wf = None if weight is None else weight.contiguous()
+        bf = None if bias is None else bias.contiguous()
+        y = torch.empty(x.shape, dtype=y_dtype, device=x.device)
+        y2 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if lowp else None
+        s = torch.empty(x.shape, dtype=s_dtype, device=x.device) if want_sum else None
+        need = any(ctx.needs_input_grad[:4])
+        stats = torch.empty(rows, 2, dtype=torch.float32, device=x.device) if need else None
+        token_layernorm_fwd_raw(x, x_ld, r, r_ld, wf, bf, y, y2, s, stats, rows, L, eps)
+        if need:
+            ctx.save_for_backward(x, r, stats, wf)
+            ctx.cfg = (k, L, rows, x_ld, r_ld, r is not None, weight is not None, bias is not None, bool(lowp), bool(want_sum))
+            ctx.set_materialize_grads(False)
+        return tuple(t for t in (y, y2, s) if t is not None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, r, stats, wf = ctx.saved_tensors
+        k, L, rows, x_ld, r_ld, has_r, has_w, has_b, lowp, want_sum = ctx.cfg
+        grads = list(grads)
+        gy = grads.pop(0)
+        gy2 = grads.pop(0) if lowp else None
+        gs = grads.pop(0) if want_sum else None
+
+        def rows_of(g, dtypes):
+            if g is None:
+                return None, 0
+            return _token_rows(g if g.dtype in dtypes else g.to(dtypes[0]), k, L)
+
+        gy, gy_ld = rows_of(gy, (torch.float32, torch.bfloat16))
+        gy2, gy2_ld = rows_of(gy2, (torch.bfloat16,))
+        gs, gs_ld = rows_of(gs, (torch.float32, torch.bfloat16))
+        gx = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
+        gr = torch.empty_strided(r.shape, r.stride(), dtype=r.dtype, device=x.device) if has_r and ctx.needs_input_grad[1] else None
+        want = (has_w and ctx.needs_input_grad[2]) or (has_b and ctx.needs_input_grad[3])
+        gwb = torch.empty(2, L, dtype=torch.float32, device=x.device) if want else None
+        token_layernorm_bwd_raw(x, x_ld, r, r_ld, gy, gy_ld, gy2, gy2_ld, gs, gs_ld, stats, wf, gx, gr, gwb, rows, L)
+        gw = gb = None
+        if want:
+            gw, gb = gwb.view(2, *x.shape[x.dim() - k:]).unbind(0)
+            gw = gw if (has_w and ctx.needs_input_grad[2]) else None
+            gb = gb if (has_b and ctx.needs_input_grad[3]) else None
+        return (gx if ctx.needs_input_grad[0] else None), gr, gw, gb, None, None, None, None, None, None
+
+
+def token_layer_norm(x, weight, bias, eps, residual=None, out_dtype=None, lowp=False, want_sum=False, normalized_shape=None):
+    """``layer_norm(x + residual)`` over the trailing axes ``normalized_shape`` on the ``mk_token_layernorm_*`` kernels.
+    ``normalized_shape`` None: the axes that ``weight`` / ``bias`` span, and the last axis when there are no parameters -- a norm
+    without parameters over several axes has to name them; parameters of another shape are refused.  Returns ``y``, then its bf16 copy if ``lowp``, then the sum ``s`` if ``want_sum`` -- a
+    single tensor when only ``y`` is asked for.  ``out_dtype`` None is the dtype of the sum (of ``x`` without a residual), and
+    fp32 under device autocast, which is what torch's autocast gives ``layer_norm``.  There is no fallback: what
+    ``token_layer_norm_supported`` declines is the caller's torch path."""
+    ref = weight if weight is not None else bias
+    if normalized_shape is not None:
+        shape = _trailing(normalized_shape)[0]
+    else:
+        shape = tuple(ref.shape) if ref is not None else tuple(x.shape[-1:])
+    ok = token_layer_norm_supported(x, shape, weight, bias) and (
+        residual is None or (residual.shape == x.shape and token_layer_norm_supported(residual, shape)))
+    if not ok:
+        raise RuntimeError("makani_amd: token_layer_norm needs fp32 / bf16 tensors on a HIP device with contiguous trailing axes and "
+                           "fp32 parameters; there is no fallback")
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise TypeError(f"makani_amd token_layer_norm: unsupported out_dtype {out_dtype}")
+    s_dtype = x.dtype if residual is None else torch.promote_types(x.dtype, residual.dtype)
+    if out_dtype is None:
+        out_dtype = torch.float32 if torch.is_autocast_enabled() else s_dtype
+    out = _TokenLayerNorm.apply(x, residual, weight, bias, eps, len(shape), out_dtype, s_dtype, bool(lowp), bool(want_sum))
+    return out[0] if len(out) == 1 else out

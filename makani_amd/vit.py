@@ -11,8 +11,16 @@ The attention product -- at the 18 540 tokens of ``config/vit.yaml`` nearly all 
 fp32 / fp16 activations (no bf16 autocast), CPU tensors, head sizes that are no multiple of 16 in 16 ... 128, attention dropout in
 training and ``MK_ATTN=torch`` take ``F.scaled_dot_product_attention``, the reference's call.
 
-``nn.Linear`` and ``nn.LayerNorm`` are torch modules here; the token-major linears on the pixel-column engine are a separate
-piece of work.  Out of scope: ``DistributedAttention`` / ``DistributedMLP`` / ``DistributedMatmul`` -- matmul group sizes
+The norms of the blocks (``norm1``, ``norm2``) and the final ``norm`` are ``layers.LayerNorm``: under ``MK_TOKEN_NORM=hip`` (read
+and validated on every call; default ``ops.TOKEN_NORM_DEFAULT``) they run on the ``mk_token_layernorm_*`` kernels
+(csrc/toknorm.hip), and a block fuses what surrounds them: under bf16 autocast ``norm1`` writes only the bf16 operand of ``qkv``,
+and ``norm2`` is one launch for ``x + drop_path(attn)``, the norm, its fp32 result for the residual and the bf16 operand of
+``fc1`` (the sum is not stored; the backward recomputes it) -- the rounding points of the torch path under autocast.  Without
+autocast there is one output in the tokens' dtype.  ``q_norm`` / ``k_norm`` stay ``nn.LayerNorm`` in torch: they act on strided
+head views ``[B, H, N, D]`` of the projection output, whose rows the kernels do not take.
+
+``nn.Linear`` is a torch module here; the token-major linears on the pixel-column engine are a separate piece of work.  Out
+of scope: ``DistributedAttention`` / ``DistributedMLP`` / ``DistributedMatmul`` -- matmul group sizes
 (``fin``, ``fout``) above 1 raise ``NotImplementedError``; data parallelism works as for any module.
 """
 import torch
@@ -25,7 +33,7 @@ except ImportError:     # loaded by file path (the reference's registry: ``netty
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from makani_amd import comm, ops
-from makani_amd.layers import MLP, DropPath, PatchEmbed
+from makani_amd.layers import MLP, DropPath, LayerNorm, PatchEmbed
 
 
 def _matmul_parallel(comm_inp_name, comm_hidden_name):
@@ -77,14 +85,26 @@ class Block(nn.Module):
         self.attn = Attention(dim, input_format="traditional", num_heads=num_heads, qkv_bias=qkv_bias,
                               attn_drop_rate=attn_drop_rate, proj_drop_rate=mlp_drop_rate, norm_layer=norm_layer)
         self.drop_path = DropPath(path_drop_rate) if path_drop_rate > 0.0 else nn.Identity()
-        self.norm1 = norm_layer(dim)
-        self.norm2 = norm_layer(dim)
+        block_norm = LayerNorm if norm_layer is nn.LayerNorm else norm_layer
+        self.norm1 = block_norm(dim)
+        self.norm2 = block_norm(dim)
         self.mlp = MLP(in_features=dim, hidden_features=int(dim * mlp_ratio), out_features=dim, act_layer=act_layer,
                        drop_rate=mlp_drop_rate, input_format="traditional")
 
+    def _fused_norms(self, x):
+        return all(isinstance(n, LayerNorm) and n.hip_ready(x) for n in (self.norm1, self.norm2))
+
     def forward(self, x):
-        x = x + self.drop_path(self.attn(self.norm1(x)))
-        x = self.norm2(x)
+        if not self._fused_norms(x):
+            x = x + self.drop_path(self.attn(self.norm1(x)))
+            x = self.norm2(x)
+            return x + self.drop_path(self.mlp(x))
+        if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
+            # norm1's one consumer is qkv, which takes bf16; fc1 takes norm2's bf16 copy, the residual its fp32 result
+            (h,) = self.norm1.forward_add(x, out_dtype=torch.bfloat16)
+            x, h = self.norm2.forward_add(self.drop_path(self.attn(h)), x, lowp=True)
+            return x + self.drop_path(self.mlp(h))
+        (x,) = self.norm2.forward_add(self.drop_path(self.attn(self.norm1(x))), x)
         return x + self.drop_path(self.mlp(x))
 
 
@@ -116,7 +136,7 @@ class VisionTransformer(nn.Module):
             Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, mlp_drop_rate=mlp_drop_rate,
                   attn_drop_rate=attn_drop_rate, path_drop_rate=rates[i], norm_layer=nn.LayerNorm, comm_inp_name=comm_inp_name,
                   comm_hidden_name=comm_hidden_name) for i in range(depth)])
-        self.norm = nn.LayerNorm(embed_dim)
+        self.norm = LayerNorm(embed_dim)
         self.out_size = self.out_ch * self.patch_size[0] * self.patch_size[1]
         self.head = nn.Linear(embed_dim, self.out_size, bias=False)
 
