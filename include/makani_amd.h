@@ -630,6 +630,47 @@ int mk_token_layernorm_bwd(const void* x, int x_dtype, long long x_ld, const voi
                            long long gs_ld, const float* stats, const float* weight, void* gx, void* gr, float* workspace,
                            float* gwb, long long rows, long long L, void* stream);
 
+/* ---- token-major linear layers (csrc/toklinear.hip): nn.Linear on [R rows][I features] activations with [O][I] weights, the
+ * qkv / proj / fc1 / fc2 / head products of the ViT and of the "traditional" MLP / EncoderDecoder.  bf16 operands, products on
+ * bf16 MFMA, fp32 accumulation.  Every matrix is a 16-byte-aligned base pointer and a row stride in elements (a multiple of
+ * 8, at least the row length); the feature axis is contiguous.  I and O are multiples of 8, R >= 1 is any count and row
+ * offsets are 64-bit.  A ragged last tile loads zeros and stores nothing in R, O and I: columns past a row's length are
+ * neither read nor written.  Each entry point validates and returns code 1 before any launch; it is one launch on `stream`
+ * (mk_token_linear_wgrad: two when it uses more than one slab), allocates nothing, does not synchronise and can be captured.
+ * Nothing is summed across workgroups by atomics and no workgroup waits on another: the same inputs give the same bits.
+ * mk_token_linear_info: tiles[6] = row tile, output tile, contraction step of the GEMM; O tile, I tile, token step of the
+ *   weight gradient.  Needs no device.
+ * mk_token_linear_pack: w ([O][I], w_dtype 0 = fp32, 1 = bf16) rounded to nearest even into the bf16 image out [O][I], or with
+ *   `transpose` out [I][O].
+ * mk_token_linear_fwd: acc[r][o] = sum_i x[r][i] w[o][i], x bf16 [R][I], w a bf16 image [O][I]; bias fp32 [O] (16-byte
+ *   aligned) or NULL.  The epilogue is selected by the non-NULL pointers, anything else is code 1:
+ *     y                      y = bf16(acc + bias)
+ *     act (and pre)          pre = bf16(acc + bias), stored when given; act = bf16(gelu(float(pre))), exact erf GELU: act has the
+ *                            same bits with and without pre
+ *     addend and out_f32     out_f32 = addend + float(bf16(acc + bias)), both fp32 [R][O]; no bf16 output
+ *     y and aux (no bias)    y = bf16(acc * gelu'(float(aux))), aux bf16 [R][O]: with x = the gradient of fc2's output and w the
+ *                            transposed image of fc2's weight this is the gradient of fc1's pre-activation, rounded once
+ * mk_token_linear_gelu_grad: out = bf16(float(g) * gelu'(float(pre))), all bf16 [R][O].
+ * mk_token_linear_wgrad: dw[o][i] = sum_r dy[r][o] x[r][i] (fp32 [O][I]) and, db not NULL, db[o] = sum_r dy[r][o] (fp32 [O],
+ *   16-byte aligned); dy bf16 [R][O], x bf16 [R][I].  The token steps are split into `slabs` (1 ... 64) groups of whole steps;
+ *   each (slab, O tile, I tile) workgroup stores an fp32 partial panel into `workspace` and a second launch adds the panels,
+ *   and the slabs' column sums for db, in slab order in fp32.  One slab stores the results directly (one launch, no
+ *   workspace).  slabs = 0 chooses: one workgroup per compute unit where the tiles alone give fewer, no slab shorter than 4
+ *   token steps and none empty.  mk_token_linear_wgrad_workspace: the bytes `workspace` must hold (no need to clear it; 16-byte
+ *   aligned), -1 for sizes the kernels refuse. */
+int mk_token_linear_info(int* tiles);
+int mk_token_linear_pack(const void* w, int w_dtype, long long ldw, void* out, long long ldo, int O, int I, int transpose,
+                         void* stream);
+int mk_token_linear_fwd(const void* x, long long ldx, const void* w, long long ldw, const float* bias, void* y, long long ldy,
+                        void* act, long long ldact, void* pre, long long ldpre, const float* addend, long long ldadd,
+                        float* out_f32, long long ldout, const void* aux, long long ldaux, long long R, int O, int I,
+                        void* stream);
+int mk_token_linear_gelu_grad(const void* g, long long ldg, const void* pre, long long ldpre, void* out, long long ldout,
+                              long long R, int O, void* stream);
+long long mk_token_linear_wgrad_workspace(long long R, int O, int I, int slabs);
+int mk_token_linear_wgrad(const void* dy, long long lddy, const void* x, long long ldx, float* dw, long long lddw, float* db,
+                          void* workspace, long long R, int O, int I, int slabs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

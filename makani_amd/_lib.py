@@ -148,6 +148,13 @@ SIGNATURES = {
                                                                                              ctypes.c_longlong, _c_float, _vp]),
     "mk_token_layernorm_bwd": (_c_int, [_vp, _c_int, ctypes.c_longlong] * 3 + [_vp, ctypes.c_longlong]
                                + [_vp, _c_int, ctypes.c_longlong] + [_vp] * 6 + [ctypes.c_longlong] * 2 + [_vp]),
+    "mk_token_linear_info": (_c_int, [_vp]),
+    "mk_token_linear_pack": (_c_int, [_vp, _c_int, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp]),
+    "mk_token_linear_fwd": (_c_int, [_vp, ctypes.c_longlong] * 2 + [_vp] + [_vp, ctypes.c_longlong] * 6
+                            + [ctypes.c_longlong, _c_int, _c_int, _vp]),
+    "mk_token_linear_gelu_grad": (_c_int, [_vp, ctypes.c_longlong] * 3 + [ctypes.c_longlong, _c_int, _vp]),
+    "mk_token_linear_wgrad_workspace": (ctypes.c_longlong, [ctypes.c_longlong, _c_int, _c_int, _c_int]),
+    "mk_token_linear_wgrad": (_c_int, [_vp, ctypes.c_longlong] * 3 + [_vp, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp]),
 }
 
 

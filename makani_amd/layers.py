@@ -609,8 +609,32 @@ def _mlp_pattern(mods):
     return convs[0], convs[1]
 
 
-def run_pointwise_chain(mods, x, skip_last_bias=False, want_row_sums=False):
-    """Evaluate an ``nn.Sequential`` of 1x1 convs / activations / identities.
+def _token_mlp_pattern(mods):
+    """``[Linear, exact GELU, no-ops..., Linear, no-ops...]`` -> (fc1, fc2), else None."""
+    lins = [m for m in mods if isinstance(m, nn.Linear)]
+    if len(lins) != 2 or not isinstance(mods[0], Linear) or len(mods) < 3 or not _is_exact_gelu(mods[1]):
+        return None
+    rest = [m for m in mods[2:] if not _is_noop(m)]
+    if len(rest) != 1 or rest[0] is not lins[1] or not isinstance(lins[1], Linear):
+        return None
+    return lins[0], lins[1]
+
+
+def _run_token_chain(mods, x, addend):
+    """The chain on token input ``[..., features]``: the two-linear pattern as ``ops.token_mlp`` (which takes the torch calls for what
+    the kernels decline); with active dropout or another activation every module runs singly."""
+    from . import ops
+    pat = _token_mlp_pattern(mods)
+    if pat is not None:
+        fc1, fc2 = pat
+        return ops.token_mlp(x, fc1.weight, fc1.bias, fc2.weight, fc2.bias, addend)
+    for m in mods:
+        x = m(x)
+    return x if addend is None else addend + x
+
+
+def run_pointwise_chain(mods, x, skip_last_bias=False, want_row_sums=False, addend=None):
+    """Evaluate an ``nn.Sequential`` of 1x1 convs / activations / identities, or of linears / activations on token input.
 
     The two-convolution pattern of ``MLP`` and ``EncoderDecoder`` (conv + bias, exact GELU, conv) runs as one fused
     autograd node on the pixel-column engine when the field is bf16 (or autocast to it).  Otherwise every
@@ -622,9 +646,16 @@ def run_pointwise_chain(mods, x, skip_last_bias=False, want_row_sums=False):
 
     ``want_row_sums``: return ``(y, sums)`` with ``sums`` the fp64 ``[B * C, 2]`` per-row (sum, sum of squares) of ``y``
     when the engine produced them alongside (else ``None``) -- the statistics of the instance norm that follows.
+
+    ``addend`` (token input only): return ``addend + chain(x)``; the two-linear pattern adds it in ``fc2``'s epilogue.
     """
     from . import ops
     mods = list(mods)
+    if any(isinstance(m, nn.Linear) for m in mods):
+        y = _run_token_chain(mods, x, addend)
+        return (y, None) if want_row_sums else y
+    if addend is not None:
+        raise ValueError("run_pointwise_chain: addend is for token input (the traditional format) only")
     pat = _mlp_pattern(mods)
     if pat is not None and x.dim() == 4:
         fc1, fc2 = pat
@@ -692,6 +723,18 @@ class InstanceNorm2d(nn.InstanceNorm2d):
             y = super().forward(x)
             return F.gelu(y) if fuse_gelu else y
         return ops.instance_norm(x, self.weight, self.bias, self.eps, fuse_gelu, row_sums=row_sums)
+
+
+class Linear(nn.Linear):
+    """``nn.Linear`` (same constructor, parameters and ``state_dict`` entries) on the ``mk_token_linear_*`` kernels under
+    ``MK_TOKEN_LINEAR=hip`` (read and validated on every call).  On the CPU, on inputs that ``ops.token_linear_supported`` declines
+    and with ``MK_TOKEN_LINEAR=torch`` it is exactly ``nn.Linear.forward``."""
+
+    def forward(self, x):
+        from . import ops
+        if ops.token_linear_hip() and ops.token_linear_supported(x, self.weight, self.bias):
+            return ops.token_linear(x, self.weight, self.bias)
+        return super().forward(x)
 
 
 class LayerNorm(nn.LayerNorm):
@@ -776,7 +819,7 @@ class EncoderDecoder(nn.Module):
             if input_format == "nchw":
                 mods.append(Conv1x1(current_dim, hidden_dim, bias=True))
             else:
-                mods.append(nn.Linear(current_dim, hidden_dim, bias=True))
+                mods.append(Linear(current_dim, hidden_dim, bias=True))
             mods[-1].weight.is_shared_mp = ["spatial"]
             nn.init.normal_(mods[-1].weight, mean=0.0, std=math.sqrt(2.0 / current_dim))
             if mods[-1].bias is not None:
@@ -787,7 +830,7 @@ class EncoderDecoder(nn.Module):
         if input_format == "nchw":
             mods.append(Conv1x1(current_dim, output_dim, bias=False))
         else:
-            mods.append(nn.Linear(current_dim, output_dim, bias=False))
+            mods.append(Linear(current_dim, output_dim, bias=False))
         mods[-1].weight.is_shared_mp = ["spatial"]
         nn.init.normal_(mods[-1].weight, mean=0.0, std=math.sqrt(gain / current_dim))
         self.fwd = nn.Sequential(*mods)
@@ -810,7 +853,7 @@ class MLP(nn.Module):
             fc1.weight.is_shared_mp = ["spatial"]
             fc1.bias.is_shared_mp = ["spatial"]
         elif input_format == "traditional":
-            fc1 = nn.Linear(in_features, hidden_features, bias=True)
+            fc1 = Linear(in_features, hidden_features, bias=True)
         else:
             raise NotImplementedError(f"Error, input format {input_format} not supported.")
         nn.init.normal_(fc1.weight, mean=0.0, std=math.sqrt(2.0 / in_features))
@@ -824,7 +867,7 @@ class MLP(nn.Module):
             if output_bias:
                 fc2.bias.is_shared_mp = ["spatial"]
         else:
-            fc2 = nn.Linear(hidden_features, out_features, bias=output_bias)
+            fc2 = Linear(hidden_features, out_features, bias=output_bias)
         nn.init.normal_(fc2.weight, mean=0.0, std=math.sqrt(gain / hidden_features))
         if fc2.bias is not None:
             nn.init.constant_(fc2.bias, 0.0)
@@ -839,18 +882,19 @@ class MLP(nn.Module):
             drop = nn.Identity()
         self.fwd = nn.Sequential(fc1, act, drop, fc2, drop)
 
-    def _run(self, x, skip_last_bias=False, want_row_sums=False):
-        return run_pointwise_chain(self.fwd, x, skip_last_bias, want_row_sums)
+    def _run(self, x, skip_last_bias=False, want_row_sums=False, addend=None):
+        return run_pointwise_chain(self.fwd, x, skip_last_bias, want_row_sums, addend)
 
-    def checkpoint_forward(self, x, skip_last_bias=False):
-        return checkpoint(self._run, x, skip_last_bias, use_reentrant=False)
+    def checkpoint_forward(self, x, skip_last_bias=False, addend=None):
+        return checkpoint(self._run, x, skip_last_bias, False, addend, use_reentrant=False)
 
-    def forward(self, x, skip_last_bias=False, want_row_sums=False):
-        """``want_row_sums``: return ``(y, sums)`` -- see ``run_pointwise_chain``."""
+    def forward(self, x, skip_last_bias=False, want_row_sums=False, addend=None):
+        """``want_row_sums``: return ``(y, sums)`` -- see ``run_pointwise_chain``.  ``addend`` (traditional format only): return
+        ``addend + mlp(x)``, the residual add of a transformer block, which the token kernels fold into ``fc2``."""
         if self.checkpointing >= 2:
-            y = self.checkpoint_forward(x, skip_last_bias)
+            y = self.checkpoint_forward(x, skip_last_bias, addend)
             return (y, None) if want_row_sums else y
-        return self._run(x, skip_last_bias, want_row_sums)
+        return self._run(x, skip_last_bias, want_row_sums, addend)
 
 
 # The HIP path is opt-in: the rule for the default is "not slower than the torch formulation at both grids of

@@ -19,9 +19,16 @@ and ``norm2`` is one launch for ``x + drop_path(attn)``, the norm, its fp32 resu
 autocast there is one output in the tokens' dtype.  ``q_norm`` / ``k_norm`` stay ``nn.LayerNorm`` in torch: they act on strided
 head views ``[B, H, N, D]`` of the projection output, whose rows the kernels do not take.
 
-``nn.Linear`` is a torch module here; the token-major linears on the pixel-column engine are a separate piece of work.  Out
-of scope: ``DistributedAttention`` / ``DistributedMLP`` / ``DistributedMatmul`` -- matmul group sizes
-(``fin``, ``fout``) above 1 raise ``NotImplementedError``; data parallelism works as for any module.
+The linears -- ``qkv``, ``proj``, the two of the MLP and ``head`` -- are ``layers.Linear``: under ``MK_TOKEN_LINEAR=hip`` (read and
+validated on every call; default ``ops.TOKEN_LINEAR_DEFAULT``) with bf16 tokens or bf16 autocast they run on the
+``mk_token_linear_*`` kernels (csrc/toklinear.hip).  The MLP is one autograd node (``ops.token_mlp``): the GELU in ``fc1``'s epilogue,
+the block's residual add in ``fc2``'s (when ``drop_path`` is an identity; with stochastic depth the block keeps the separate add)
+and the GELU gradient in the epilogue of ``fc2``'s data gradient.  Weight gradients are accumulated and returned in fp32.  fp32
+tokens without autocast, feature counts that are no multiple of 8, CPU tensors and ``MK_TOKEN_LINEAR=torch`` take ``F.linear``.
+``PatchEmbed`` (a strided convolution) and the un-patchify einsum behind ``head`` stay torch ops.
+
+Out of scope: ``DistributedAttention`` / ``DistributedMLP`` / ``DistributedMatmul`` -- matmul group sizes (``fin``, ``fout``) above 1
+raise ``NotImplementedError``; data parallelism works as for any module.
 """
 import torch
 import torch.nn as nn
@@ -33,7 +40,7 @@ except ImportError:     # loaded by file path (the reference's registry: ``netty
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from makani_amd import comm, ops
-from makani_amd.layers import MLP, DropPath, LayerNorm, PatchEmbed
+from makani_amd.layers import MLP, DropPath, LayerNorm, Linear, PatchEmbed
 
 
 def _matmul_parallel(comm_inp_name, comm_hidden_name):
@@ -41,7 +48,7 @@ def _matmul_parallel(comm_inp_name, comm_hidden_name):
 
 
 class Attention(nn.Module):
-    """vit.py:14-55: multi-head self-attention on ``[B, N, C]`` tokens; ``qkv`` and ``proj`` are ``nn.Linear``."""
+    """vit.py:14-55: multi-head self-attention on ``[B, N, C]`` tokens; ``qkv`` and ``proj`` are ``layers.Linear``."""
 
     def __init__(self, dim, input_format="traditional", num_heads=8, qkv_bias=False, qk_norm=False, attn_drop_rate=0.0,
                  proj_drop_rate=0.0, norm_layer=nn.LayerNorm):
@@ -51,11 +58,11 @@ class Attention(nn.Module):
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = self.head_dim ** -0.5
-        self.qkv = nn.Linear(dim, 3 * dim, bias=qkv_bias)
+        self.qkv = Linear(dim, 3 * dim, bias=qkv_bias)
         self.q_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
         self.k_norm = norm_layer(self.head_dim) if qk_norm else nn.Identity()
         self.attn_drop_rate = attn_drop_rate
-        self.proj = nn.Linear(dim, dim)
+        self.proj = Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop_rate) if proj_drop_rate > 0 else nn.Identity()
 
     def forward(self, x):
@@ -94,18 +101,24 @@ class Block(nn.Module):
     def _fused_norms(self, x):
         return all(isinstance(n, LayerNorm) and n.hip_ready(x) for n in (self.norm1, self.norm2))
 
+    def _add_mlp(self, x, h):
+        """``x + drop_path(mlp(h))``; without stochastic depth the add is the MLP's (``fc2``'s epilogue on the token kernels)."""
+        if isinstance(self.drop_path, nn.Identity):
+            return self.mlp(h, addend=x)
+        return x + self.drop_path(self.mlp(h))
+
     def forward(self, x):
         if not self._fused_norms(x):
             x = x + self.drop_path(self.attn(self.norm1(x)))
             x = self.norm2(x)
-            return x + self.drop_path(self.mlp(x))
+            return self._add_mlp(x, x)
         if torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
             # norm1's one consumer is qkv, which takes bf16; fc1 takes norm2's bf16 copy, the residual its fp32 result
             (h,) = self.norm1.forward_add(x, out_dtype=torch.bfloat16)
             x, h = self.norm2.forward_add(self.drop_path(self.attn(h)), x, lowp=True)
-            return x + self.drop_path(self.mlp(h))
+            return self._add_mlp(x, h)
         (x,) = self.norm2.forward_add(self.drop_path(self.attn(self.norm1(x))), x)
-        return x + self.drop_path(self.mlp(x))
+        return self._add_mlp(x, x)
 
 
 class VisionTransformer(nn.Module):
@@ -138,7 +151,7 @@ class VisionTransformer(nn.Module):
                   comm_hidden_name=comm_hidden_name) for i in range(depth)])
         self.norm = LayerNorm(embed_dim)
         self.out_size = self.out_ch * self.patch_size[0] * self.patch_size[1]
-        self.head = nn.Linear(embed_dim, self.out_size, bias=False)
+        self.head = Linear(embed_dim, self.out_size, bias=False)
 
         nn.init.trunc_normal_(self.pos_embed, std=0.02)
         self.apply(self._init_weights)
