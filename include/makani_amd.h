@@ -173,6 +173,11 @@ int mk_irfft_affine_add(const float* xf, void* x, int x_dtype, const float* twid
  * Needs nlat >= 2, 2 <= lmax <= nlat (the length query returns 0 otherwise). */
 long long mk_latdft_table_len(int nlat, int lmax);
 int mk_latdft_table(int nlat, int lmax, float* out);
+/* The same table (length, layout, rounding) over a contiguous WINDOW of frequencies, f_l = (first + l) mod nlat: the rows the
+ * channels-last AFNO keeps (networks/afnonet.py:78-103: `total_modes - kept_modes : total_modes + kept_modes`, contiguous around
+ * the Nyquist row, not RealFFT2's low frequencies).  mk_latdft_fwd / mk_latdft_inv take either table as data.  first = 0 and
+ * lmax = nlat give mk_latdft_table's bits.  Needs 0 <= first < nlat and 2 <= lmax <= nlat. */
+int mk_latdft_table_window(int nlat, int lmax, int first, float* out);
 /* fwd: c[l][j]  = sum_k W[l][k] xf[k][j]            xf complex64 [nlat][ncols], c complex64 [lmax][ncols]
  * inv: xf[k][j] = sum_l conj(W[l][k]) c[l][j]       ncols = mmax_loc * bc; only the kept frequencies are contracted
  * (the zero padding between the high and the low modes of InverseRealFFT2.forward is implicit).  Each is the adjoint
@@ -272,6 +277,14 @@ long long mk_spec_bdmlp_wgrad_workspace(int rows, int nb, int ib, int ob);
 int mk_spec_bdmlp_wgrad(const float* x, const float* gy, float* gw, void* workspace, int rows, int nb, int ib, int ob,
                         void* stream);
 int mk_spec_bdmlp_mask(const float* gy, const float* s, float* out, long long n, void* stream);
+/* The forward product with a complex bias per output channel, the spectral MLP of the channels-last AFNO
+ * (networks/afnonet.py:81-103: `relu(x w1 + b1)`, then `x w2 + b2` in front of the soft-shrink of line 106):
+ *   y[r][k*ob + o] = act(sum_i x[r][k*ib + i] * w[k][i][o] + bias[k*ob + o])
+ * bias: interleaved complex [nb * ob], 8-byte aligned, added in fp32 on the accumulator before act (0, 2 or 3 as above); NULL is
+ * mk_spec_bdmlp_fwd, bit for bit.  The data and weight gradients are those of the family above; the bias gradient is
+ * mk_spec_cmlp_bgrad of the (masked) output gradient with cout = nb * ob on a dense spectrum. */
+int mk_spec_bdmlp_fwd_bias(const float* x, const float* w, const float* bias, float* y, int rows, int nb, int ib, int ob, int act,
+                           float lambda, void* stream);
 
 /* ---- "diagonal" spectral filter: one complex weight per (l, m) ---------------------------
  * Public layout, P = L * M contiguous: x [B][I][P], w [I][O][P], y [B][O][P] complex64.
@@ -289,6 +302,16 @@ int mk_diag_wgrad(const float* x, const float* gy, float* gw, int batch, int cin
 int mk_spec_pack(const float* c_std, float* c_prv, int bc, int lloc, int mloc, void* stream);
 int mk_spec_unpack(const float* c_prv, float* c_std, int bc, int lloc, int mloc,
                    int l_off, int m_off, void* stream);
+/* tokens [batch][n][c]  <->  fields [batch][c][n]: what lets the channels-last AFNO (networks/afnonet.py:63-112, `rfft2(x,
+ * dim=(1, 2))` on x [B, H, W, C], n = H * W) run on the planar transforms, which read channel-major fields.
+ *   tokens_to_fields: fld[b][ch][i] = tok[b][i][ch]
+ *   fields_to_tokens: tok[b][i][ch] = fld[b][ch][i] + addend[b][i][ch]     (addend NULL: the plain transpose)
+ * The addend is the filter's `x + bias` (afnonet.py:112) in the pass that brings the inverse transform's rows back to tokens.
+ * dtype: 0 fp32, 1 bf16, the same on all operands; the add is in fp32, rounded once.  Any batch, n, c >= 1 (64-bit offsets);
+ * 16-byte loads and stores where n, c are multiples of 16 bytes' worth of elements and the operands 16-byte aligned, single
+ * elements otherwise.  One launch, no allocation, no synchronisation.  Each is the adjoint of the other. */
+int mk_tokens_to_fields(const void* tok, void* fld, int dtype, int batch, int n, int c, void* stream);
+int mk_fields_to_tokens(const void* fld, const void* addend, void* tok, int dtype, int batch, int n, int c, void* stream);
 
 /* ---- fused pointwise ops of the FNO block (rows = B*C <= 65535, P = H*W multiple of 8) -------- */
 /* dtype: 0 = fp32, 1 = bf16 storage; arithmetic is fp32.

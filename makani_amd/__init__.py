@@ -7,6 +7,8 @@ Mirrors the reference's interfaces for the hot path only:
 * ``makani_amd.spectral_convolution`` SpectralConv / FactorizedSpectralConv
 * ``makani_amd.sfnonet``              FourierNeuralOperatorBlock / SphericalFourierNeuralOperatorNet
 * ``makani_amd.afnonet``              AFNO2D / Block / AdaptiveFourierNeuralOperatorNet (block-diagonal spectral MLP kernels)
+* ``makani_amd.afnonet_v1``           Mlp / AFNO2D / Block / AdaptiveFourierNeuralOperatorNet of the channels-last AFNOv1 (token <-> field
+                                      layout passes around the planar transforms, block MLP with biases)
 * ``makani_amd.vit``                  Attention / Block / VisionTransformer (scaled-dot-product attention on HIP MFMA kernels)
 * ``makani_amd.comm``                 h / w / data process groups over torch.distributed (RCCL)
 * ``makani_amd.preprocessor``         Preprocessor2D / get_preprocessor (one-pass HIP input assembly: ``assemble``)

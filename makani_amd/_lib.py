@@ -50,6 +50,7 @@ SIGNATURES = {
     "mk_legendre_inv_x3_ex": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "mk_latdft_table_len": (ctypes.c_longlong, [_c_int, _c_int]),
     "mk_latdft_table": (_c_int, [_c_int, _c_int, _vp]),
+    "mk_latdft_table_window": (_c_int, [_c_int, _c_int, _c_int, _vp]),
     "mk_latdft_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_latdft_inv": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_dhconv_fwd": (_c_int, [_vp, _vp, _vp] + [_c_int] * 7 + [_vp]),
@@ -72,12 +73,15 @@ SIGNATURES = {
     "mk_spec_bdmlp_wgrad_workspace": (ctypes.c_longlong, [_c_int] * 4),
     "mk_spec_bdmlp_wgrad": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 4 + [_vp]),
     "mk_spec_bdmlp_mask": (_c_int, [_vp, _vp, _vp, ctypes.c_longlong, _vp]),
+    "mk_spec_bdmlp_fwd_bias": (_c_int, [_vp, _vp, _vp, _vp] + [_c_int] * 5 + [_c_float, _vp]),
     "mk_affine_add":(_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_dgrad": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_diag_wgrad": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_spec_pack": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp]),
     "mk_spec_unpack": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "mk_tokens_to_fields": (_c_int, [_vp, _vp] + [_c_int] * 4 + [_vp]),
+    "mk_fields_to_tokens": (_c_int, [_vp, _vp, _vp] + [_c_int] * 4 + [_vp]),
     "mk_bias_gelu_fwd": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_bias_gelu_bwd": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _vp]),
     "mk_instnorm_fwd": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, ctypes.c_longlong, _c_float,

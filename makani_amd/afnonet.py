@@ -10,7 +10,8 @@ not ``hip_ready`` (``MK_PLANAR_FFT`` defaults to ``torch``) and every case the k
 
 Out of scope:
 
-* the channels-last ``AFNOv1`` (networks/afnonet.py);
+* the channels-last ``AFNOv1`` (networks/afnonet.py) is its own module, ``makani_amd/afnonet_v1.py``, on these kernels plus two
+  layout passes, biases in the block MLP and a latitude DFT table over its frequency window;
 * ``DistributedAFNO2Dv2`` / ``DistributedPatchEmbed``: the reference's are broken (``distributed_rfft2`` is undefined), so
   spatial or matmul group sizes above 1 raise ``NotImplementedError``; data parallelism works as for any module;
 * the engines' shape limits: 768 -> 3072 and the 1664-wide patch and head GEMMs take whatever path ``Conv1x1`` / ``MLP`` give

@@ -174,9 +174,8 @@ extern "C" long long mk_latdft_table_len(int nlat, int lmax) {
     return 2 * (long long)lmax * latdft_pad4(nlat) + 2 * (long long)nlat * latdft_pad4(lmax);
 }
 
-extern "C" int mk_latdft_table(int nlat, int lmax, float* out) {
-    MK_REQUIRE(out != nullptr, "null pointer");
-    MK_REQUIRE(nlat >= 2 && lmax >= 2 && lmax <= nlat, "need nlat >= 2 and 2 <= lmax <= nlat");
+// `first` < 0: the truncation's frequencies (latdft_freq); else the window (first + l) mod nlat
+static void latdft_fill(int nlat, int lmax, int first, float* out) {
     const long long KP = latdft_pad4(nlat), LP = latdft_pad4(lmax);
     std::memset(out, 0, sizeof(float) * (size_t)mk_latdft_table_len(nlat, lmax));
     float* fc = out;                           // analysis: cos [lmax][KP], sin [lmax][KP]
@@ -185,7 +184,7 @@ extern "C" int mk_latdft_table(int nlat, int lmax, float* out) {
     float* is = ic + (long long)nlat * LP;
     const double norm = 1.0 / std::sqrt((double)nlat);
     for (int l = 0; l < lmax; ++l) {
-        const long long f = latdft_freq(nlat, lmax, l);
+        const long long f = first < 0 ? latdft_freq(nlat, lmax, l) : (first + l) % nlat;
         for (int k = 0; k < nlat; ++k) {
             // the angle from f * k reduced modulo nlat in integers: no float64 cancellation at large f * k
             const double a = 2.0 * M_PI * (double)((f * k) % nlat) / (double)nlat;
@@ -196,5 +195,20 @@ extern "C" int mk_latdft_table(int nlat, int lmax, float* out) {
             is[k * LP + l] = s;
         }
     }
+}
+
+extern "C" int mk_latdft_table(int nlat, int lmax, float* out) {
+    MK_REQUIRE(out != nullptr, "null pointer");
+    MK_REQUIRE(nlat >= 2 && lmax >= 2 && lmax <= nlat, "need nlat >= 2 and 2 <= lmax <= nlat");
+    latdft_fill(nlat, lmax, -1, out);
+    return 0;
+}
+
+// The channels-last AFNO's rows (networks/afnonet.py:78-103): a contiguous window of frequencies, wrapping modulo nlat.
+extern "C" int mk_latdft_table_window(int nlat, int lmax, int first, float* out) {
+    MK_REQUIRE(out != nullptr, "null pointer");
+    MK_REQUIRE(nlat >= 2 && lmax >= 2 && lmax <= nlat, "need nlat >= 2 and 2 <= lmax <= nlat");
+    MK_REQUIRE(first >= 0 && first < nlat, "need 0 <= first < nlat");
+    latdft_fill(nlat, lmax, first, out);
     return 0;
 }

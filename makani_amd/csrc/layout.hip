@@ -40,7 +40,133 @@ __global__ __launch_bounds__(256) void transpose_c64_kernel(const float2* __rest
     }
 }
 
+// ---- tokens [batch][n][c] <-> fields [batch][c][n] (the channels-last AFNO on the planar transforms) ----
+// dst[b][c][r] = src[b][r][c] (+ addend[b][c][r]) for a [R][C] matrix per batch entry, through a 64 x 64 tile of 32-bit words
+// (an fp32 value's bits, or a bf16 value's 16 bits: without an addend the elements pass through bit for bit).  Rows of 65 words:
+// the row-wise fill and the column-wise drain both touch every bank equally.  Both global sides walk their own contiguous axis.
+// VEC: R and C are whole numbers of 16-byte vectors and the operands 16-byte aligned -- a vector is wholly inside the matrix
+// or wholly outside; otherwise single elements.  Ragged tiles load and store nothing outside the matrix.
+constexpr int LT = 64;
+
+template <typename T> struct LayoutElem;
+template <> struct LayoutElem<float> {
+    static __device__ __forceinline__ unsigned bits(float v) { return __float_as_uint(v); }
+    static __device__ __forceinline__ float value(unsigned b) { return __uint_as_float(b); }
+    static __device__ __forceinline__ unsigned round(float v) { return __float_as_uint(v); }
+    static __device__ __forceinline__ float from(unsigned b) { return __uint_as_float(b); }
+};
+template <> struct LayoutElem<unsigned short> {     // bf16
+    static __device__ __forceinline__ unsigned bits(unsigned short v) { return v; }
+    static __device__ __forceinline__ unsigned short from(unsigned b) { return (unsigned short)b; }
+    static __device__ __forceinline__ float value(unsigned b) { return __uint_as_float(b << 16); }
+    static __device__ __forceinline__ unsigned round(float v) {     // to nearest even; NaN stays NaN
+        const unsigned u = __float_as_uint(v);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    }
+};
+
+// word k of a 16-byte vector of T: one fp32, or the k-th of eight bf16
+template <typename T> __device__ __forceinline__ unsigned vec_word(const uint4& v, int k) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    if constexpr (sizeof(T) == 4) return w[k];
+    else return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void transpose_add_kernel(const T* __restrict__ src, const T* __restrict__ addend, T* __restrict__ dst,
+                                                            int R, int C, int tiles_r, int tiles_c) {
+    using E = LayoutElem<T>;
+    __shared__ unsigned tile[LT][LT + 1];
+    constexpr int V = 16 / (int)sizeof(T), VPR = LT / V;      // elements per vector, vectors per tile row
+    long long bid = blockIdx.x;
+    const int c0 = (int)(bid % tiles_c) * LT;
+    bid /= tiles_c;
+    const int r0 = (int)(bid % tiles_r) * LT;
+    const long long base = (bid / tiles_r) * (long long)R * C;
+    const int tid = threadIdx.x;
+    if constexpr (VEC) {
+        for (int e = tid; e < LT * VPR; e += 256) {
+            const int r = e / VPR, q = (e % VPR) * V;
+            if (r0 + r < R && c0 + q < C) {
+                const uint4 v = *reinterpret_cast<const uint4*>(src + base + (long long)(r0 + r) * C + c0 + q);
+#pragma unroll
+                for (int k = 0; k < V; ++k) tile[r][q + k] = vec_word<T>(v, k);
+            }
+        }
+    } else {
+        const int tx = tid & 63, ty = tid >> 6;
+        for (int j = ty; j < LT; j += 4)
+            if (r0 + j < R && c0 + tx < C) tile[j][tx] = E::bits(src[base + (long long)(r0 + j) * C + c0 + tx]);
+    }
+    __syncthreads();
+    if constexpr (VEC) {
+        for (int e = tid; e < LT * VPR; e += 256) {
+            const int c = e / VPR, q = (e % VPR) * V;
+            if (c0 + c < C && r0 + q < R) {
+                const long long off = base + (long long)(c0 + c) * R + r0 + q;
+                unsigned w[V];
+#pragma unroll
+                for (int k = 0; k < V; ++k) w[k] = tile[q + k][c];
+                if (addend) {
+                    const uint4 a = *reinterpret_cast<const uint4*>(addend + off);
+#pragma unroll
+                    for (int k = 0; k < V; ++k) w[k] = E::round(E::value(w[k]) + E::value(vec_word<T>(a, k)));
+                }
+                uint4 o;
+                if constexpr (sizeof(T) == 4) o = make_uint4(w[0], w[1], w[2], w[3]);
+                else o = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+                *reinterpret_cast<uint4*>(dst + off) = o;
+            }
+        }
+    } else {
+        const int tx = tid & 63, ty = tid >> 6;
+        for (int j = ty; j < LT; j += 4)
+            if (c0 + j < C && r0 + tx < R) {
+                const long long off = base + (long long)(c0 + j) * R + r0 + tx;
+                unsigned w = tile[tx][j];
+                if (addend) w = E::round(E::value(w) + E::value(E::bits(addend[off])));
+                dst[off] = E::from(w);
+            }
+    }
+}
+
+template <typename T>
+int transpose_add_launch(const char* who, const void* src, const void* addend, void* dst, int batch, int R, int C, void* stream) {
+    const long long tiles_r = mk::ceil_div(R, LT), tiles_c = mk::ceil_div(C, LT);
+    MK_REQUIRE_AS(who, tiles_r * tiles_c < 2147483647LL / batch, "grid too large");
+    constexpr int V = 16 / (int)sizeof(T);
+    const bool vec = R % V == 0 && C % V == 0 && (((uintptr_t)src | (uintptr_t)addend | (uintptr_t)dst) & 15) == 0;
+    const auto kernel = vec ? transpose_add_kernel<T, true> : transpose_add_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_r * tiles_c * batch)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const T*>(src), static_cast<const T*>(addend), static_cast<T*>(dst), R, C, (int)tiles_r,
+                       (int)tiles_c);
+    MK_LAUNCH_CHECK_AS(who);
+    return 0;
+}
+
+int layout_check(const char* who, const void* a, const void* b, const void* addend, int dtype, int batch, int n, int c) {
+    MK_REQUIRE_AS(who, a && b, "null pointer");
+    MK_REQUIRE_AS(who, dtype == 0 || dtype == 1, "unknown dtype (0 fp32 | 1 bf16)");
+    MK_REQUIRE_AS(who, batch >= 1 && n >= 1 && c >= 1, "bad sizes");
+    const uintptr_t item = dtype ? 2 : 4;
+    MK_REQUIRE_AS(who, (((uintptr_t)a | (uintptr_t)b | (uintptr_t)addend) & (item - 1)) == 0, "operands must be aligned to their elements");
+    return 0;
+}
+
 }  // namespace
+
+extern "C" int mk_tokens_to_fields(const void* tok, void* fld, int dtype, int batch, int n, int c, void* stream) {
+    if (int e = layout_check(__func__, tok, fld, nullptr, dtype, batch, n, c)) return e;
+    return dtype ? transpose_add_launch<unsigned short>(__func__, tok, nullptr, fld, batch, n, c, stream)
+                 : transpose_add_launch<float>(__func__, tok, nullptr, fld, batch, n, c, stream);
+}
+
+extern "C" int mk_fields_to_tokens(const void* fld, const void* addend, void* tok, int dtype, int batch, int n, int c, void* stream) {
+    if (int e = layout_check(__func__, fld, tok, addend, dtype, batch, n, c)) return e;
+    return dtype ? transpose_add_launch<unsigned short>(__func__, fld, addend, tok, batch, c, n, stream)
+                 : transpose_add_launch<float>(__func__, fld, addend, tok, batch, c, n, stream);
+}
 
 extern "C" int mk_spec_pack(const float* c_std, float* c_prv, int bc, int lloc, int mloc, void* stream) {
     MK_REQUIRE(c_std && c_prv, "null pointer");

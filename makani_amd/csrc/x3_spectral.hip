@@ -590,23 +590,33 @@ struct BlockParams {
     int rows, nb, ib, ob, tiles_m, tiles_n;
     float lambda;        // soft-shrink threshold
     int rg, ngroups;     // wgrad: rows per group (a multiple of 16), number of groups
+    const float* bias = nullptr;     // fwd with bias: interleaved complex [nb * ob]
 };
 
 constexpr int BD_STORE = 0, BD_RELU = 2, BD_SHRINK = 3, BD_MASK = 4;
+constexpr int BD_BIAS = 8;      // added to BD_STORE / BD_RELU / BD_SHRINK: a complex bias per column in front of the function
 
 // store f(tile) with f fixed at compile time: nothing, ReLU or soft-shrink on both components (fp32, on the accumulator), or the
-// mask (aux > 0) per component with `aux` the saved activation output at the tile's origin (row pitch ldc)
+// mask (aux > 0) per component with `aux` the saved activation output at the tile's origin (row pitch ldc).  The BD_BIAS modes add
+// bias[column] (`bias` at the tile's first column) in fp32 on the accumulator first, as CplxBiasReluEpi does for the dense MLP.
 template <int MODE>
 struct BlockEpi {
     float* cbase;
     long long ldc;
     const float* aux;
     float lambda;
+    const float* bias = nullptr;
+    static constexpr int F = MODE & 7;
     static constexpr bool PAIRED_BANDS = false;
     static __device__ __forceinline__ float shrink(float v, float l) { return v > l ? v - l : (v < -l ? v + l : 0.f); }
     __device__ __forceinline__ void store(const f32x16 (&acc)[2][2], int wr, int wc, int fi, int kg, int rvalid, int cvalid) const {
         const int col = wc * 64 + 2 * fi;
         if (col < cvalid) {
+            float b0 = 0.f, b1 = 0.f;
+            if constexpr ((MODE & BD_BIAS) != 0) {
+                b0 = bias[col];
+                b1 = bias[col + 1];
+            }
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -617,13 +627,17 @@ struct BlockEpi {
                         x3_f2 v2;
                         v2[0] = acc[a][0][r];
                         v2[1] = acc[a][1][r];
-                        if constexpr (MODE == BD_RELU) {
+                        if constexpr ((MODE & BD_BIAS) != 0) {
+                            v2[0] += b0;
+                            v2[1] += b1;
+                        }
+                        if constexpr (F == BD_RELU) {
                             v2[0] = v2[0] > 0.f ? v2[0] : 0.f;
                             v2[1] = v2[1] > 0.f ? v2[1] : 0.f;
-                        } else if constexpr (MODE == BD_SHRINK) {
+                        } else if constexpr (F == BD_SHRINK) {
                             v2[0] = shrink(v2[0], lambda);
                             v2[1] = shrink(v2[1], lambda);
-                        } else if constexpr (MODE == BD_MASK) {
+                        } else if constexpr (F == BD_MASK) {
                             const float2 m = *reinterpret_cast<const float2*>(aux + off);
                             v2[0] = m.x > 0.f ? v2[0] : 0.f;
                             v2[1] = m.y > 0.f ? v2[1] : 0.f;
@@ -654,7 +668,8 @@ __global__ __launch_bounds__(XT, 3) void spec_bdmlp_fwd_kernel(BlockParams p) {
     bs.ldk = p.ob;
     bs.kk_hi = p.ib;
     bs.ovalid = p.ob - n0 / 2;
-    const BlockEpi<MODE> epi{p.dst + ((long long)r0 * co + (long long)k * p.ob) * 2 + n0, 2 * co, nullptr, p.lambda};
+    const BlockEpi<MODE> epi{p.dst + ((long long)r0 * co + (long long)k * p.ob) * 2 + n0, 2 * co, nullptr, p.lambda,
+                             (MODE & BD_BIAS) != 0 ? p.bias + (long long)k * p.ob * 2 + n0 : nullptr};
     x3_tile(as, bs, 0, (2 * p.ib + XK - 1) / XK, p.rows - r0, 2 * p.ob - n0, epi, lds_x3);
 }
 
@@ -905,6 +920,22 @@ extern "C" int mk_spec_bdmlp_fwd(const float* x, const float* w, float* y, int r
     if (act == 2) return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_RELU>, nblk, stream, p);
     if (act == 3) return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_SHRINK>, nblk, stream, p);
     return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_STORE>, nblk, stream, p);
+}
+
+extern "C" int mk_spec_bdmlp_fwd_bias(const float* x, const float* w, const float* bias, float* y, int rows, int nb, int ib, int ob,
+                                      int act, float lambda, void* stream) {
+    if (!bias) return mk_spec_bdmlp_fwd(x, w, y, rows, nb, ib, ob, act, lambda, stream);
+    if (int e = spec_bdmlp_check(x, w, y, rows, nb, ib, ob)) return e;
+    MK_REQUIRE(((uintptr_t)bias & 7) == 0, "the complex bias must be 8-byte aligned");
+    MK_REQUIRE(act == 0 || act == 2 || act == 3, "unknown activation (0 none | 2 cartesian ReLU | 3 soft-shrink)");
+    MK_REQUIRE(act != 3 || lambda >= 0.f, "the soft-shrink threshold must not be negative");
+    BlockParams p = bdmlp_params(x, w, y, rows, nb, ib, ob, rows, ob);
+    p.lambda = lambda;
+    p.bias = bias;
+    const long long nblk = grid_blocks(nb, p.tiles_m, p.tiles_n);
+    if (act == 2) return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_BIAS + BD_RELU>, nblk, stream, p);
+    if (act == 3) return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_BIAS + BD_SHRINK>, nblk, stream, p);
+    return x3_launch(__func__, spec_bdmlp_fwd_kernel<BD_BIAS + BD_STORE>, nblk, stream, p);
 }
 
 extern "C" int mk_spec_bdmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int rows, int nb, int ib, int ob,

@@ -68,15 +68,22 @@ def fft_twiddles(nlon):
     return out
 
 
-def latdft_table(nlat, lmax):
+def latdft_table(nlat, lmax, first=None):
     """Cosine / sine tables of the truncated latitude DFT of the planar transform (``mk_latdft_table``: the analysis matrix
-    ``[2, lmax, pad4(nlat)]`` followed by its transpose ``[2, nlat, pad4(lmax)]``) as a flat fp32 CPU tensor."""
+    ``[2, lmax, pad4(nlat)]`` followed by its transpose ``[2, nlat, pad4(lmax)]``) as a flat fp32 CPU tensor.  ``first``: the
+    ``lmax`` frequencies ``(first + l) mod nlat`` in place of the truncation's (``mk_latdft_table_window``: the window of the
+    channels-last AFNO)."""
     lib = _lib.load()
     n = lib.mk_latdft_table_len(int(nlat), int(lmax))
     if n <= 0:
         raise ValueError(f"latdft_table: need nlat >= 2 and 2 <= lmax <= nlat, got nlat={nlat}, lmax={lmax}")
     out = torch.empty(n, dtype=torch.float32)
-    _lib.check(lib.mk_latdft_table(int(nlat), int(lmax), out.data_ptr()), "mk_latdft_table")
+    if first is None:
+        _lib.check(lib.mk_latdft_table(int(nlat), int(lmax), out.data_ptr()), "mk_latdft_table")
+    else:
+        if not 0 <= int(first) < nlat:
+            raise ValueError(f"latdft_table: need 0 <= first < nlat, got first={first}, nlat={nlat}")
+        _lib.check(lib.mk_latdft_table_window(int(nlat), int(lmax), int(first), out.data_ptr()), "mk_latdft_table_window")
     return out
 
 
@@ -1162,13 +1169,21 @@ def spec_bdmlp_mask_raw(gy, s, out=None):
     return out
 
 
-def spec_bdmlp_fwd_raw(x, w, act=0, lam=0.0, out=None):
-    """y[r, k * ob + o] = act(sum_i x[r, k * ib + i] w[k, i, o]) on the rows of the dense spectrum ``[L, M, B * nb * ib]``; ``w``
-    complex64 ``[nb, ib, ob]``; ``act`` 0 | 2 | 3 (none | ReLU on both components | soft-shrink with threshold ``lam`` on both)."""
+def spec_bdmlp_fwd_raw(x, w, act=0, lam=0.0, out=None, bias=None):
+    """y[r, k * ob + o] = act(sum_i x[r, k * ib + i] w[k, i, o] + bias[k * ob + o]) on the rows of the dense spectrum
+    ``[L, M, B * nb * ib]``; ``w`` complex64 ``[nb, ib, ob]``; ``bias`` complex64 of ``nb * ob`` elements or None (then
+    ``mk_spec_bdmlp_fwd``, as ever); ``act`` 0 | 2 | 3 (none | ReLU on both components | soft-shrink with threshold ``lam`` on
+    both)."""
     rows, nb, ib, ob = _bdmlp_args(x, w, 1)
     y = _bdmlp_out(out, x, nb * ib, nb * ob)
-    _lib.check(_lib.load().mk_spec_bdmlp_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), rows, nb, ib, ob, int(act), float(lam),
-                                             _stream()), "mk_spec_bdmlp_fwd")
+    if bias is None:
+        _lib.check(_lib.load().mk_spec_bdmlp_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(), rows, nb, ib, ob, int(act), float(lam),
+                                                 _stream()), "mk_spec_bdmlp_fwd")
+        return y
+    _need_cuda(bias)
+    assert bias.dtype == torch.complex64 and bias.is_contiguous() and bias.numel() == nb * ob, "contiguous complex64 bias of nb * ob"
+    _lib.check(_lib.load().mk_spec_bdmlp_fwd_bias(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), rows, nb, ib, ob, int(act),
+                                                  float(lam), _stream()), "mk_spec_bdmlp_fwd_bias")
     return y
 
 
@@ -1215,14 +1230,28 @@ def _block_weight(w):
     return torch.view_as_complex(w.detach().contiguous())
 
 
+def _block_bias(b):
+    """A real ``[n, 2]`` (re, im) bias as the kernels' contiguous complex64 ``[n]``, or None."""
+    if b is None:
+        return None
+    assert b.dim() == 2 and b.shape[1] == 2 and b.dtype == torch.float32, "fp32 [nb * ob, 2] block bias"
+    return torch.view_as_complex(b.detach().contiguous())
+
+
+def _block_bias_grad(g, batch):
+    """Sum of the dense ``[L, M, B * n]`` gradient over all rows and samples -> real ``[n, 2]``: ``mk_spec_cmlp_bgrad`` with the
+    degree offset at ``M`` (no triangle), float64 sums in a fixed order."""
+    return torch.view_as_real(spec_cmlp_bgrad_raw(g, batch, g.shape[1], 0))
+
+
 class _SpecBlockMLP(torch.autograd.Function):
     """``softshrink(relu_c(c w1) w2)`` per channel block on the dense spectrum.  Saves the input spectrum, the hidden activation
     (the second product's input and, by its signs, relu') and the output (by its zeros, softshrink')."""
 
     @staticmethod
-    def forward(ctx, c, w1, w2, batch, nb, lam):
-        h = spec_bdmlp_fwd_raw(c, _block_weight(w1), 2)
-        y = spec_bdmlp_fwd_raw(h, _block_weight(w2), 3, lam)
+    def forward(ctx, c, w1, w2, batch, nb, lam, b1, b2):
+        h = spec_bdmlp_fwd_raw(c, _block_weight(w1), 2, bias=_block_bias(b1))
+        y = spec_bdmlp_fwd_raw(h, _block_weight(w2), 3, lam, bias=_block_bias(b2))
         ctx.save_for_backward(c, h, y, w1, w2)
         ctx.args = (batch, nb)
         return y
@@ -1234,39 +1263,141 @@ class _SpecBlockMLP(torch.autograd.Function):
         need = ctx.needs_input_grad
         g = spec_bdmlp_mask_raw(gy.contiguous(), y)         # one masked copy serves both gradients of the second layer
         gw2 = torch.view_as_real(spec_bdmlp_wgrad_raw(h, g, batch, nb)) if need[2] else None
-        gc = gw1 = None
-        if need[0] or need[1]:
+        need_b1, need_b2 = need[6], need[7]
+        gb2 = _block_bias_grad(g, batch) if need_b2 else None
+        gc = gw1 = gb1 = None
+        if need[0] or need[1] or need_b1:
             gh = spec_bdmlp_dgrad_raw(g, _block_weight(w2), a=h)
             if need[1]:
                 gw1 = torch.view_as_real(spec_bdmlp_wgrad_raw(c, gh, batch, nb))
+            if need_b1:
+                gb1 = _block_bias_grad(gh, batch)
             if need[0]:
                 gc = spec_bdmlp_dgrad_raw(gh, _block_weight(w1))
-        return gc, gw1, gw2, None, None, None
+        return gc, gw1, gw2, None, None, None, gb1, gb2
 
 
-def _spec_block_mlp_torch(c, w1, w2, batch, nb, lam):
+def _spec_block_mlp_torch(c, w1, w2, batch, nb, lam, b1=None, b2=None):
     """The same function in torch ops (CPU tensors)."""
     L, M = c.shape[0], c.shape[1]
     x = c.reshape(L, M, batch, nb, -1)
     h = torch.einsum("lmbki,kio->lmbko", x, torch.view_as_complex(w1.contiguous()))
+    if b1 is not None:
+        h = h + torch.view_as_complex(b1.contiguous()).view(nb, -1)
     h = torch.complex(torch.relu(h.real), torch.relu(h.imag))
     y = torch.einsum("lmbki,kio->lmbko", h, torch.view_as_complex(w2.contiguous()))
+    if b2 is not None:
+        y = y + torch.view_as_complex(b2.contiguous()).view(nb, -1)
     y = torch.view_as_complex(torch.nn.functional.softshrink(torch.view_as_real(y), lambd=lam))
     return y.reshape(L, M, -1)
 
 
-def spec_block_mlp(c, w1, w2, batch, num_blocks, lam):
+def spec_block_mlp(c, w1, w2, batch, num_blocks, lam, b1=None, b2=None):
     """AFNO's filter arithmetic on the dense private spectrum ``c`` ``[L, M, B * C]`` (complex64): per channel block k of
-    ``C / num_blocks`` channels ``softshrink(relu_c(c_k w1[k]) w2[k], lam)``, ReLU and soft-shrink on both components.  ``w1``
-    ``[nb, bs, hb, 2]``, ``w2`` ``[nb, hb, bs, 2]``: the reference's real fp32 parameters; their gradients come back in that shape.
+    ``C / num_blocks`` channels ``softshrink(relu_c(c_k w1[k] + b1[k]) w2[k] + b2[k], lam)``, ReLU and soft-shrink on both
+    components.  ``w1`` ``[nb, bs, hb, 2]``, ``w2`` ``[nb, hb, bs, 2]``: the reference's real fp32 parameters of afnonet_v2.py; their
+    gradients come back in that shape.  ``b1`` ``[nb * hb, 2]``, ``b2`` ``[nb * bs, 2]``: real fp32 (re, im) pairs per hidden / output
+    channel (the channels-last AFNO's complex biases), or None -- without them the calls and the bits are what they were.  The
+    bias gradients are float64 sums in a fixed order (``mk_spec_cmlp_bgrad``).
     CUDA tensors run on the ``mk_spec_bdmlp_*`` kernels (even ``bs`` and ``hb``), CPU tensors on torch ops."""
     nb = int(num_blocks)
     assert c.dim() == 3 and c.shape[2] % (batch * nb) == 0 and w1.dim() == 4 and w2.dim() == 4
     bs = c.shape[2] // (batch * nb)
     assert w1.shape[0] == w2.shape[0] == nb and w1.shape[1] == w2.shape[2] == bs and w1.shape[2] == w2.shape[1], "block weight shapes"
+    assert b1 is None or tuple(b1.shape) == (nb * w1.shape[2], 2), "b1: [nb * hb, 2]"
+    assert b2 is None or tuple(b2.shape) == (nb * bs, 2), "b2: [nb * bs, 2]"
     if not c.is_cuda:
-        return _spec_block_mlp_torch(c, w1, w2, batch, nb, lam)
-    return _SpecBlockMLP.apply(c.contiguous(), w1, w2, int(batch), nb, float(lam))
+        return _spec_block_mlp_torch(c, w1, w2, batch, nb, lam, b1, b2)
+    return _SpecBlockMLP.apply(c.contiguous(), w1, w2, int(batch), nb, float(lam), b1, b2)
+
+
+# ----------------------------------------------------------------------------
+# tokens [B, N, C] <-> fields [B, C, N] (the channels-last AFNO on the planar transforms, mk_tokens_to_fields / mk_fields_to_tokens)
+# ----------------------------------------------------------------------------
+# The fused path is the default by the rule of DESIGN section 19: no row of tools/afnov1_bench.py is slower than the torch
+# formulation (DESIGN section 27).  It still needs the HIP planar transforms (MK_PLANAR_FFT=hip).
+AFNOV1_DEFAULT = "hip"
+
+
+def afnov1_hip():
+    """``MK_AFNOV1=hip|torch`` (read at call time): the channels-last ``AFNO2D`` of ``afnonet_v1`` on the layout passes, the HIP
+    planar transforms and the block MLP with biases, or the reference's formulation in torch ops."""
+    mode = os.environ.get("MK_AFNOV1", AFNOV1_DEFAULT)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"unknown MK_AFNOV1 {mode!r} (hip | torch)")
+    return mode == "hip"
+
+
+def _layout_args(x, other=None):
+    assert x.dim() == 3 and x.numel() > 0 and x.dtype in (torch.float32, torch.bfloat16), "[B, N, C] / [B, C, N] fp32 or bf16"
+    assert other is None or (other.dtype == x.dtype and other.device == x.device)
+
+
+def tokens_to_fields_raw(x, out=None):
+    """``x`` ``[B, N, C]`` contiguous -> ``[B, C, N]`` (``mk_tokens_to_fields``)."""
+    _need_cuda(x)
+    _layout_args(x)
+    assert x.is_contiguous()
+    B, N, C = x.shape
+    out = torch.empty((B, C, N), dtype=x.dtype, device=x.device) if out is None else out
+    assert tuple(out.shape) == (B, C, N) and out.is_contiguous() and out.dtype == x.dtype and out.device == x.device
+    _lib.check(_lib.load().mk_tokens_to_fields(x.data_ptr(), out.data_ptr(), _pw_dtype(x), B, N, C, _stream()), "mk_tokens_to_fields")
+    return out
+
+
+def fields_to_tokens_raw(r, addend=None, out=None):
+    """``r`` ``[B, C, N]`` contiguous (+ ``addend`` ``[B, N, C]`` contiguous) -> ``[B, N, C]`` (``mk_fields_to_tokens``)."""
+    _need_cuda(r)
+    _layout_args(r, addend)
+    assert r.is_contiguous()
+    B, C, N = r.shape
+    assert addend is None or (tuple(addend.shape) == (B, N, C) and addend.is_contiguous())
+    out = torch.empty((B, N, C), dtype=r.dtype, device=r.device) if out is None else out
+    assert tuple(out.shape) == (B, N, C) and out.is_contiguous() and out.dtype == r.dtype and out.device == r.device
+    _lib.check(_lib.load().mk_fields_to_tokens(r.data_ptr(), addend.data_ptr() if addend is not None else 0, out.data_ptr(),
+                                               _pw_dtype(r), B, N, C, _stream()), "mk_fields_to_tokens")
+    return out
+
+
+class _TokensToFields(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return tokens_to_fields_raw(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        return fields_to_tokens_raw(g.contiguous())
+
+
+class _FieldsToTokens(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, r, addend):
+        return fields_to_tokens_raw(r.contiguous(), None if addend is None else addend.contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        need = ctx.needs_input_grad
+        return tokens_to_fields_raw(g.contiguous()) if need[0] else None, g if need[1] else None
+
+
+def tokens_to_fields(x):
+    """``[B, N, C]`` tokens -> ``[B, C, N]`` fields (fp32 / bf16): one ``mk_tokens_to_fields`` pass on the device, its backward one
+    ``mk_fields_to_tokens`` pass; CPU tensors take ``x.transpose(1, 2).contiguous()``."""
+    _layout_args(x)
+    if not x.is_cuda:
+        return x.transpose(1, 2).contiguous()
+    return _TokensToFields.apply(x)
+
+
+def fields_to_tokens(r, addend=None):
+    """``[B, C, N]`` fields -> ``[B, N, C]`` tokens, ``+ addend`` (``[B, N, C]``, same dtype; the add in fp32, rounded once) in the
+    same pass.  The backward is one ``mk_tokens_to_fields`` pass; the addend's gradient is the incoming gradient.  CPU tensors take
+    ``r.transpose(1, 2) + addend``."""
+    _layout_args(r, addend)
+    if not r.is_cuda:
+        t = r.transpose(1, 2)
+        return (t if addend is None else t + addend).contiguous()
+    return _FieldsToTokens.apply(r, addend)
 
 
 def rfft(x, twiddles, mmax, kmajor=False, scale=None):
