@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmakani_amd.so")
 STAMP = LIB + ".stamp"
 SOURCES = ["host.cpp", "fft.hip", "gemm.hip", "x3_legendre.hip", "x3_spectral.hip", "x3_latdft.hip", "x3_conv.hip", "layout.hip", "diag.hip", "pointwise.hip", "conv_gemm.hip", "pce.hip", "pce_mlp.hip", "adam.hip", "optim.hip", "metrics.hip", "lploss.hip", "preproc.hip", "zenith.hip", "chnorm.hip", "specnorm.hip", "attn.hip", "toknorm.hip", "toklinear.hip"]
-HEADERS = ["common.h", "x3_engine.h", "fft_split.h", "pce_common.h", "gelu.h", "stream_io.h", "tile_map.h", os.path.join("..", "..", "include", "makani_amd.h")]
+HEADERS = ["common.h", "mfma_tile.h", "x3_engine.h", "fft_split.h", "pce_common.h", "gelu.h", "stream_io.h", "tile_map.h", os.path.join("..", "..", "include", "makani_amd.h")]
 
 
 def _hipcc():
@@ -21,6 +21,11 @@ def _hipcc():
 
 def have_hipcc():
     return any(c and os.path.exists(c) for c in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"))
+
+
+def compile_flags():
+    """The flags every source is compiled with, here and in tools/kernel_asm_diff.py."""
+    return ["-O3", "-std=c++20", "--offload-arch=gfx950", "-fPIC", "-x", "hip"] + os.environ.get("MK_EXTRA_HIPCC_FLAGS", "").split()
 
 
 def _source_digest():
@@ -54,8 +59,7 @@ def build(force=False, verbose=True):
     procs = []
     for src in SOURCES:
         obj = os.path.join(bdir, src + ".o")
-        cmd = [hipcc, "-O3", "-std=c++20", "--offload-arch=gfx950", "-fPIC", "-x", "hip",
-               "-c", os.path.join(CSRC, src), "-o", obj] + os.environ.get("MK_EXTRA_HIPCC_FLAGS", "").split()
+        cmd = [hipcc] + compile_flags() + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -22,6 +22,7 @@
 // read from or written to memory.  A ragged last key tile is masked in the score; rows past the end load as zeros and
 // are not stored.
 #include "common.h"
+#include "mfma_tile.h"
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
@@ -29,9 +30,15 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using mk::mfma::bf16x4;
+using mk::mfma::bf16x8;
+using mk::mfma::bf_hi;
+using mk::mfma::bf_lo;
+using mk::mfma::f32x16;
+using mk::mfma::read_row_frag;
+using mk::mfma::RowStage;
+using mk::mfma::tile_row;
+using mk::mfma::zero;
 typedef __hip_bfloat16 bf16;
 
 constexpr int kT = 256;                 // 4 waves
@@ -44,35 +51,17 @@ constexpr int dkv_sweep(int DP) { return 4096 / DP; }      // query tile of dkv:
 
 struct Str { long long b, h, n; };      // element strides of batch, head, token; the D axis is contiguous
 
-__device__ __forceinline__ int tile_row(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }   // C/D row of register r
-
-// ---- staging of a [ROWS][D] tile through registers ---------------------------------------------------------------------
+// ---- staging of a [ROWS][D] tile through registers: the row-major image of RowStage, and the transposed one -------------------
 template <int ROWS, int DP>
-struct Stage {
-    static constexpr int CPR = DP / 8, NV = ROWS * CPR / kT;
-    static_assert(ROWS * CPR % kT == 0, "tile does not divide among the threads");
-    uint4 r[NV];
-    // base: the tile's first row; rows at or past rows_valid and d at or past D become zeros, and are not read
-    __device__ __forceinline__ void load(const bf16* base, long long sn, int rows_valid, int D, int tid) {
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int v = tid + i * kT, row = v / CPR, c = v % CPR;
-            r[i] = (row < rows_valid && c * 8 < D) ? *reinterpret_cast<const uint4*>(base + row * sn + c * 8) : make_uint4(0, 0, 0, 0);
-        }
-    }
-    __device__ __forceinline__ void put_rows(char* img, int tid) const {      // [row][d], 16-byte chunks swizzled
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int v = tid + i * kT, row = v / CPR, c = v % CPR;
-            *reinterpret_cast<uint4*>(img + row * (DP * 2) + ((c ^ (row & 7)) << 4)) = r[i];
-        }
-    }
+struct Stage : RowStage<ROWS, DP, kT> {
+    using RowStage<ROWS, DP, kT>::CPR;
+    using RowStage<ROWS, DP, kT>::NV;
     __device__ __forceinline__ void put_cols(char* img, int tid) const {      // [d][row], pitch ROWS + 2
         uint16_t* t = reinterpret_cast<uint16_t*>(img);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int v = tid + i * kT, row = v / CPR, c = v % CPR;
-            const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+            const uint32_t w[4] = {this->r[i].x, this->r[i].y, this->r[i].z, this->r[i].w};
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[(c * 8 + e) * (ROWS + 2) + row] = (uint16_t)(w[e >> 1] >> (16 * (e & 1)));
         }
@@ -81,11 +70,6 @@ struct Stage {
 template <int ROWS, int DP> constexpr int rows_bytes() { return ROWS * DP * 2; }
 template <int ROWS, int DP> constexpr int cols_bytes() { return (DP * (ROWS + 2) * 2 + 15) / 16 * 16; }
 
-// operand fragment of k-step ks for MFMA row / column `row`: 8 consecutive d of one token
-template <int DP>
-__device__ __forceinline__ bf16x8 read_row_frag(const char* img, int row, int ks, int fh) {
-    return *reinterpret_cast<const bf16x8*>(img + row * (DP * 2) + (((2 * ks + fh) ^ (row & 7)) << 4));
-}
 // A fragment over the swept token for one d, in the k order of an accumulator tile used as B: rows r0 .. r0 + 3, r0 + 8 .. r0 + 11
 template <int ROWS>
 __device__ __forceinline__ bf16x8 read_col_frag(const char* img, int d, int r0) {
@@ -125,13 +109,6 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[DP / 32], bf16* row,
             }
         }
 }
-template <int N>
-__device__ __forceinline__ void zero(f32x16 (&a)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[i][r] = 0.f;
-}
 
 struct Params {
     const bf16 *q, *k, *v, *dO;
@@ -168,7 +145,7 @@ __global__ __launch_bounds__(kT) void attn_fwd_kernel(Params p) {
     stv.load(vbase, p.sv.n, p.Nk, p.D, tid);
     for (int t = 0; t < nt; ++t) {
         __syncthreads();                // the previous tile's reads are done
-        stk.put_rows(k_img, tid);
+        stk.put(k_img, tid);
         stv.put_cols(vt_img, tid);
         __syncthreads();
         if (t + 1 < nt) {
@@ -239,8 +216,8 @@ __global__ __launch_bounds__(kT) void attn_delta_kernel(Params p, long long tota
         const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, cw[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            s = fmaf(__uint_as_float(aw[e] << 16), __uint_as_float(cw[e] << 16), s);
-            s = fmaf(__uint_as_float(aw[e] & 0xFFFF0000u), __uint_as_float(cw[e] & 0xFFFF0000u), s);
+            s = fmaf(bf_lo(aw[e]), bf_lo(cw[e]), s);
+            s = fmaf(bf_hi(aw[e]), bf_hi(cw[e]), s);
         }
     }
     p.lse_out[i] = s;               // the delta buffer
@@ -274,9 +251,9 @@ __global__ __launch_bounds__(kT) void attn_bwd_dq_kernel(Params p) {
     stv.load(vbase, p.sv.n, p.Nk, p.D, tid);
     for (int t = 0; t < nt; ++t) {
         __syncthreads();
-        stk.put_rows(k_img, tid);
+        stk.put(k_img, tid);
         stk.put_cols(kt_img, tid);
-        stv.put_rows(v_img, tid);
+        stv.put(v_img, tid);
         __syncthreads();
         if (t + 1 < nt) {
             const long long k1 = (long long)(t + 1) * TK;
@@ -345,9 +322,9 @@ __global__ __launch_bounds__(kT) void attn_bwd_dkv_kernel(Params p) {
     if (tid < TQ && tid < p.Nq) rl = lbase[tid] * kLog2e, rd = dbase[tid];
     for (int t = 0; t < nt; ++t) {
         __syncthreads();
-        stq.put_rows(q_img, tid);
+        stq.put(q_img, tid);
         stq.put_cols(qt_img, tid);
-        stg.put_rows(g_img, tid);
+        stg.put(g_img, tid);
         stg.put_cols(gt_img, tid);
         if (tid < TQ) lse_s[tid] = rl, del_s[tid] = rd;
         __syncthreads();

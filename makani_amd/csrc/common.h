@@ -49,4 +49,21 @@ template <auto Kernel> int raise_lds_limit(int bytes) {
     return 0;
 }
 
+// compute units of the current device, asked once per device; 256 (an MI355X) where there is no device to ask
+inline int cu_count() {
+    static std::atomic<int> known[64];
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        (void)hipGetLastError();
+        return 256;
+    }
+    if ((n = known[dev].load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) {
+        (void)hipGetLastError();
+        return 256;
+    }
+    known[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
 }  // namespace mk

@@ -10,6 +10,7 @@
 // combined with fp32 atomics (shaped as 128-byte row segments).  All blocks of one pixel slab are dealt
 // to the same XCD so the slab is read from HBM once and re-read from that XCD's L2.
 #include "common.h"
+#include "mfma_tile.h"
 #include "../../include/makani_amd.h"
 #include "pce_common.h"
 
@@ -19,8 +20,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using mk::mfma::bf16x8;
+using mk::mfma::f32x16;
 
 // GELU on the 8 bf16 values of a staged vector (the x operand of `mk_conv1x1_wgrad_act`: the weight gradient of the second
 // convolution of an MLP reads the kept PRE-activation and applies the activation on the way into LDS, so the hidden
@@ -358,13 +359,9 @@ static int wgrad_big_launch(WgradParams& p, int batch, hipStream_t st) {
     const long long nblk1 = (long long)p.nblk_o * p.nblk_i;
     wgrad_slabs(p, nblk1, 32, batch);                 // 32 workgroup slots per XCD (one 512-thread workgroup per CU)
     const long long grid = (((long long)p.nslab * batch + 7) / 8) * 8 * nblk1;
-    if (grid >= 2147483647LL) return 1;
-    static const bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_wgrad_big_kernel<WR, WC, RT, CT, ACT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        return true;
-    }();
-    (void)once;
+    MK_REQUIRE_AS("mk_conv1x1_wgrad_act", grid < 2147483647LL, "grid too large");
+    MK_REQUIRE_AS("mk_conv1x1_wgrad_act", (mk::raise_lds_limit<conv1x1_wgrad_big_kernel<WR, WC, RT, CT, ACT>>(LDS) == 0),
+                  "cannot raise the dynamic LDS limit on this device");
     hipLaunchKernelGGL((conv1x1_wgrad_big_kernel<WR, WC, RT, CT, ACT>), dim3((unsigned)grid), dim3(WT8), LDS, st, p);
     return 0;
 }
@@ -376,13 +373,9 @@ static int wgrad_block_launch(WgradParams& p, int batch, hipStream_t st) {
     p.nblk_i = mk::ceil_div(p.I, WTI);
     wgrad_slabs(p, (long long)p.nblk_o * p.nblk_i, MT == 4 ? 32 : 64, batch);
     const long long grid = (((long long)p.nslab * batch + 7) / 8) * 8 * p.nblk_o * p.nblk_i;
-    if (grid >= 2147483647LL) return 1;
-    static const bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_wgrad_kernel<MT, 64, 1, ACT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        return true;
-    }();
-    (void)once;
+    MK_REQUIRE_AS("mk_conv1x1_wgrad_act", grid < 2147483647LL, "grid too large");
+    MK_REQUIRE_AS("mk_conv1x1_wgrad_act", (mk::raise_lds_limit<conv1x1_wgrad_kernel<MT, 64, 1, ACT>>(LDS) == 0),
+                  "cannot raise the dynamic LDS limit on this device");
     hipLaunchKernelGGL((conv1x1_wgrad_kernel<MT, 64, 1, ACT>), dim3((unsigned)grid), dim3(WT), LDS, st, p);
     return 0;
 }
@@ -421,7 +414,7 @@ extern "C" int mk_conv1x1_wgrad_act(const void* gy, const void* x, float* gw, in
         else if (big_ok && cout % 192 == 0 && cin % 256 == 0) rc = wgrad_big_launch<2, 4, 3, 2, false>(p, batch, st);   // 192 x 256
         else rc = wgrad_block_launch<2, false>(p, batch, st);                                                       // 128 x 128
     }
-    MK_REQUIRE(rc == 0, "grid too large");
+    if (rc) return rc;
     MK_LAUNCH_CHECK();
     return 0;
 }

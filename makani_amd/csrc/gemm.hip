@@ -20,6 +20,7 @@
 // are dealt to the same XCD (blockIdx % 8) back to back, so the operand panels they
 // share stay in that XCD's L2.
 #include "common.h"
+#include "mfma_tile.h"
 #include "tile_map.h"
 #include "../../include/makani_amd.h"
 
@@ -27,7 +28,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using mk::mfma::f32x16;
 
 constexpr int kThreads = 256;
 constexpr int TM = 64, TN = 128, TK = 32;

@@ -699,29 +699,12 @@ static bool pce_config(int M, int K, PceCfg* c) {
 }
 static long long pce_image_core_bytes(const PceCfg& c) { return (long long)c.npass * c.NPH * c.KSP * 2 * c.TH * 1024; }
 
-static int pce_cu_count() {
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return ncu;
-}
-
 template <int KSP, int NPH, int TH, bool HAS_IN>
 static int pce_launch(const PceParams& p, hipStream_t st) {
     constexpr int LDS = (NPH > 1 ? 2 : 1) * 16 * KSP * XROW + 3 * 2 * 2 * TH * 1024 + 8 * 2048 + 4 * 64 * TH * 4;   // X regions + three weight groups + 8 staging tiles + the bias of up to four passes
-    static const bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pce_kernel<KSP, NPH, TH, HAS_IN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        return true;
-    }();
-    (void)once;
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    MK_REQUIRE_AS("mk_pce_gemm_ex", (mk::raise_lds_limit<pce_kernel<KSP, NPH, TH, HAS_IN>>(LDS) == 0),
+                  "cannot raise the dynamic LDS limit on this device");
+    const int ncu = mk::cu_count();
     const long long grid = p.ntiles < ncu ? p.ntiles : ncu;
     PceParams q = p;
     // MK_PCE_XCD_RUNS: 0 plain tile order, 1 (default) XCD runs where rows are not whole 128-byte lines, 2 always
@@ -854,10 +837,11 @@ extern "C" int mk_pce_gemm_ex(const void* x, const void* wimg, void* y, const fl
         p.split = 0;        // likewise
         p.Mb = M;
         bool done = false;
+        int rc = 0;
 #define MK_PCE_CASE(KSP_, NPH_, TH_) \
         if (!done && c.KSP == KSP_ && c.NPH == NPH_ && c.TH == TH_) {                                         \
-            if (p.addend || p.aux_in) pce_launch<KSP_, NPH_, TH_, true>(p, st);                               \
-            else pce_launch<KSP_, NPH_, TH_, false>(p, st);                                                   \
+            if (p.addend || p.aux_in) rc = pce_launch<KSP_, NPH_, TH_, true>(p, st);                          \
+            else rc = pce_launch<KSP_, NPH_, TH_, false>(p, st);                                              \
             done = true;                                                                                        \
         }
         MK_PCE_CASE(2, 1, 1) MK_PCE_CASE(2, 1, 2) MK_PCE_CASE(2, 1, 6)
@@ -868,6 +852,7 @@ extern "C" int mk_pce_gemm_ex(const void* x, const void* wimg, void* y, const fl
         MK_PCE_CASE(8, 6, 1) MK_PCE_CASE(8, 6, 2) MK_PCE_CASE(8, 6, 6)
 #undef MK_PCE_CASE
         MK_REQUIRE(done, "no kernel instance for this shape");
+        if (rc) return rc;
         MK_LAUNCH_CHECK();
     }
     return 0;

@@ -4,15 +4,17 @@
 // in flight), raw barriers.
 #pragma once
 #include "gelu.h"
+#include "mfma_tile.h"
 
 #include <hip/hip_bf16.h>
 #include <cstdint>
 
 namespace pce {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+using mk::mfma::bf16x2;
+using mk::mfma::bf16x8;
+using mk::mfma::f32x16;
+using mk::mfma::s16x4;
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -75,7 +77,6 @@ __device__ __forceinline__ float lds_read_b32(uint32_t addr) {
     asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(addr) : "memory");
     return v;
 }
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const bf16x2 t = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(uint32_t, t);

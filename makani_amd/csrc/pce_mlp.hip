@@ -736,26 +736,19 @@ static unsigned long long* mlp_dbg_buffer() {
 }
 
 template <int KS1, int MT, int MODE>
-static void mlp_launch(const MlpParams& p, hipStream_t st) {
+static int mlp_launch(const MlpParams& p, hipStream_t st) {
     constexpr int PHS = KS1 < 6 ? KS1 : 6, NPX = (KS1 + PHS - 1) / PHS, NREGX = NPX >= 2 ? 2 : 1;
     constexpr int SLOTF = (KS1 + 1) / 2 + 2 * ((MT + 1) / 2);
     constexpr int LDS = NREGX * PHS * 16 * QXROW + 3 * SLOTF * 1024 + 16 * QSTG + (QNCMAX + 3 * QMTMAX) * 32 * 4;
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    static const bool once = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pce_mlp_kernel<KS1, MT, MODE>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        return true;
-    }();
-    (void)once;
-    static const int ncu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    MK_REQUIRE_AS("mk_pce_mlp", (mk::raise_lds_limit<pce_mlp_kernel<KS1, MT, MODE>>(LDS) == 0),
+                  "cannot raise the dynamic LDS limit on this device");
+    const int ncu = mk::cu_count();
     const long long grid = p.ntiles < ncu ? p.ntiles : ncu;
     MlpParams q = p;
     q.xcd_runs = grid % 8 == 0 && (p.P * 2) % 128 != 0;      // tile order by XCD runs where rows are not whole 128-byte lines (pce.hip)
     hipLaunchKernelGGL((pce_mlp_kernel<KS1, MT, MODE>), dim3((unsigned)grid), dim3(QT), LDS, st, q);
+    return 0;
 }
 
 }  // namespace
@@ -845,15 +838,17 @@ extern "C" int mk_pce_mlp(const void* x, const void* wimg, void* y, void* mid_ou
     p.xcd_runs = 0;
     p.dbg = mlp_dbg_buffer();
     bool done = false;
+    int rc = 0;
 #define MK_MLP_CASE(KS1_, MT_)                                        \
     if (!done && c.KS1 == KS1_ && c.MT == MT_) {                      \
-        if (mode == 0) mlp_launch<KS1_, MT_, 0>(p, st);               \
-        else mlp_launch<KS1_, MT_, 1>(p, st);                         \
+        if (mode == 0) rc = mlp_launch<KS1_, MT_, 0>(p, st);          \
+        else rc = mlp_launch<KS1_, MT_, 1>(p, st);                    \
         done = true;                                                  \
     }
     MK_MLP_CASE(5, 3) MK_MLP_CASE(5, 12) MK_MLP_CASE(12, 3) MK_MLP_CASE(12, 12) MK_MLP_CASE(24, 3) MK_MLP_CASE(24, 12)
 #undef MK_MLP_CASE
     MK_REQUIRE(done, "no kernel instance for this shape");
+    if (rc) return rc;
     MK_LAUNCH_CHECK();
     return 0;
 }

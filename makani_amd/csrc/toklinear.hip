@@ -19,6 +19,7 @@
 // written.
 #include "common.h"
 #include "gelu.h"
+#include "mfma_tile.h"
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
@@ -26,11 +27,16 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+using mk::mfma::bf16x2;
+using mk::mfma::bf16x4;
+using mk::mfma::bf16x8;
+using mk::mfma::bf_hi;
+using mk::mfma::bf_lo;
+using mk::mfma::f32x16;
+using mk::mfma::read_row_frag;
+using mk::mfma::s16x4;
+using mk::mfma::tile_row;
+using mk::mfma::zero;
 typedef __hip_bfloat16 bf16;
 using Gelu = mk::gelu::Act<__hip_bfloat16>;
 
@@ -39,32 +45,8 @@ constexpr int kTR = 128, kTC = 128, kTK = 64;            // forward: rows, outpu
 constexpr int kTO = 128, kTI = 128, kTS = 64;            // weight gradient: outputs, inputs, token step
 constexpr int kMaxSlabs = 64;
 
-__device__ __forceinline__ int tile_row(int r, int fh) { return (r & 3) + 8 * (r >> 2) + 4 * fh; }   // C/D row of register r
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
-
 // ---- a [128][64] tile of a [rows, K] operand: rows of the image are rows of the operand ---------------------------------------
-struct RowStage {
-    uint4 r[4];
-    // base: the tile's first row at the step's first k; rows at or past rows_valid and k at or past k_valid are zeros, not read
-    __device__ __forceinline__ void load(const bf16* base, long long ld, long long rows_valid, int k_valid, int tid) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = tid + i * kT, row = v >> 3, c = v & 7;
-            r[i] = (row < rows_valid && c * 8 < k_valid) ? *reinterpret_cast<const uint4*>(base + row * ld + c * 8) : make_uint4(0, 0, 0, 0);
-        }
-    }
-    __device__ __forceinline__ void put(char* img, int tid) const {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = tid + i * kT, row = v >> 3, c = v & 7;
-            *reinterpret_cast<uint4*>(img + row * (kTK * 2) + ((c ^ (row & 7)) << 4)) = r[i];
-        }
-    }
-};
-__device__ __forceinline__ bf16x8 read_row_frag(const char* img, int row, int ks, int fh) {
-    return *reinterpret_cast<const bf16x8*>(img + row * (kTK * 2) + (((2 * ks + fh) ^ (row & 7)) << 4));
-}
+using RowStage = mk::mfma::RowStage<kTR, kTK, kT>;
 
 // ---- a [64 tokens][128 features] tile of an operand that is contracted over its tokens ---------------------------------------
 // The image stays token-major as it comes from memory (16-byte stores); ds_read_b64_tr_b16 delivers it feature-major: per group
@@ -111,15 +93,6 @@ __device__ __forceinline__ bf16x8 read_tr_frag(char* img, int f0, int ks, int la
     v.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
         (s16x4 __attribute__((address_space(3)))*)(__attribute__((address_space(3))) char*)(img + tok_off(row + 4, ch) + 8 * (p & 1)));
     return __builtin_bit_cast(bf16x8, v);
-}
-
-__device__ __forceinline__ void zero(f32x16 (&a)[2][2]) {
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a[m][n][r] = 0.f;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
@@ -174,9 +147,9 @@ __global__ __launch_bounds__(kT) void toklinear_fwd_kernel(FwdParams p) {
         for (int ks = 0; ks < kTK / 16; ++ks) {
             bf16x8 a[2], b[2];
 #pragma unroll
-            for (int m = 0; m < 2; ++m) a[m] = read_row_frag(w_img, wo * 64 + m * 32 + fr, ks, fh);
+            for (int m = 0; m < 2; ++m) a[m] = read_row_frag<kTK>(w_img, wo * 64 + m * 32 + fr, ks, fh);
 #pragma unroll
-            for (int n = 0; n < 2; ++n) b[n] = read_row_frag(x_img, wr * 64 + n * 32 + fr, ks, fh);
+            for (int n = 0; n < 2; ++n) b[n] = read_row_frag<kTK>(x_img, wr * 64 + n * 32 + fr, ks, fh);
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -465,28 +438,12 @@ int check_operand(const char* who, const void* ptr, long long ld, int len) {
     return 0;
 }
 
-// compute units of the current device, asked once per device; 256 (an MI355X) where there is no device to ask
-int cu_count() {
-    static std::atomic<int> known[64];
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        (void)hipGetLastError();
-        return 256;
-    }
-    if ((n = known[dev].load(std::memory_order_relaxed)) > 0) return n;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) {
-        (void)hipGetLastError();
-        return 256;
-    }
-    known[dev].store(n, std::memory_order_relaxed);
-    return n;
-}
 // slabs = 0: one workgroup per compute unit where the (O, I) tiles alone do not give that many, every slab at least 4 token
 // steps long, and no slab empty
 int resolve_slabs(long long R, int O, int I, int slabs) {
     if (slabs > 0) return slabs;
     const long long tiles = (long long)mk::ceil_div(O, kTO) * mk::ceil_div(I, kTI), steps = mk::ceil_div_ll(R, kTS);
-    long long s = mk::ceil_div_ll(cu_count(), tiles);
+    long long s = mk::ceil_div_ll(mk::cu_count(), tiles);
     if (s > steps / 4) s = steps / 4;
     if (s > kMaxSlabs) s = kMaxSlabs;
     if (s < 1) s = 1;

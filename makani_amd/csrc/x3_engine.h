@@ -34,6 +34,7 @@
 // (the Legendre tables) are laid out once, tile by tile, so staging them is a straight walk over 16 KB.
 #pragma once
 #include "common.h"
+#include "mfma_tile.h"
 #include "tile_map.h"
 #include "../../include/makani_amd.h"
 
@@ -42,8 +43,8 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using mk::mfma::bf16x8;
+using mk::mfma::f32x16;
 typedef float x3_f2 __attribute__((ext_vector_type(2)));
 typedef float x3_f4 __attribute__((ext_vector_type(4)));
 

@@ -907,10 +907,7 @@ def planar_fft_hip():
     """The planar transforms run on this package's kernels: ``MK_PLANAR_FFT`` (``hip`` | ``torch``, read at call time), and
     the bf16x3 engine selected -- ``MK_SPECTRAL_GEMM=f32`` has no fp32-MFMA variant of the latitude DFT."""
     from . import ops
-    mode = os.environ.get("MK_PLANAR_FFT", PLANAR_FFT_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"MK_PLANAR_FFT={mode!r} (hip | torch)")
-    return mode == "hip" and ops.SPECTRAL_GEMM == "bf16x3"
+    return ops._hip_or_torch("MK_PLANAR_FFT", PLANAR_FFT_DEFAULT) and ops.SPECTRAL_GEMM == "bf16x3"
 
 
 class _PlanarFFT2Base(nn.Module):

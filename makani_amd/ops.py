@@ -31,6 +31,21 @@ def _need_cuda(*tensors):
                                "there is no CPU fallback")
 
 
+def _hip_or_torch(env, default):
+    """A family's ``hip | torch`` switch, read and validated at call time; True for ``hip``."""
+    mode = os.environ.get(env, default)
+    if mode not in ("hip", "torch"):
+        raise ValueError(f"unknown {env} {mode!r} (hip | torch)")
+    return mode == "hip"
+
+
+def _autocast_dtype():
+    """The device's autocast dtype, or None outside autocast."""
+    if not torch.is_autocast_enabled():
+        return None
+    return torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+
+
 # ----------------------------------------------------------------------------
 # host-side precompute (float64 in C, no GPU needed)
 # ----------------------------------------------------------------------------
@@ -990,10 +1005,7 @@ CMLP_ACT = {None: 0, "none": 0, "real": 1, "cartesian": 2}
 def spec_attn_hip():
     """``MK_SPEC_ATTN=hip|torch`` (read at call time): the channel MLP of ``SpectralAttention`` on the ``mk_spec_cmlp_*`` kernels,
     or the torch einsums on the public spectrum."""
-    mode = os.environ.get("MK_SPEC_ATTN", SPEC_ATTN_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown MK_SPEC_ATTN {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _hip_or_torch("MK_SPEC_ATTN", SPEC_ATTN_DEFAULT)
 
 
 def _cmlp_weight(w, lloc):
@@ -1131,10 +1143,7 @@ AFNO_DEFAULT = "hip"
 def afno_hip():
     """``MK_AFNO=hip|torch`` (read at call time): ``AFNO2D`` on the HIP planar transforms with the ``mk_spec_bdmlp_*`` block MLP
     in between, or the reference's formulation in torch ops."""
-    mode = os.environ.get("MK_AFNO", AFNO_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown MK_AFNO {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _hip_or_torch("MK_AFNO", AFNO_DEFAULT)
 
 
 def _bdmlp_args(x, w, cols):
@@ -1322,10 +1331,7 @@ AFNOV1_DEFAULT = "hip"
 def afnov1_hip():
     """``MK_AFNOV1=hip|torch`` (read at call time): the channels-last ``AFNO2D`` of ``afnonet_v1`` on the layout passes, the HIP
     planar transforms and the block MLP with biases, or the reference's formulation in torch ops."""
-    mode = os.environ.get("MK_AFNOV1", AFNOV1_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown MK_AFNOV1 {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _hip_or_torch("MK_AFNOV1", AFNOV1_DEFAULT)
 
 
 def _layout_args(x, other=None):
@@ -2081,10 +2087,7 @@ ATTN_DEFAULT = "hip"
 
 def attn_hip():
     """``MK_ATTN=hip|torch`` (read at call time): bf16 attention on the ``mk_attn_*`` kernels, or ``F.scaled_dot_product_attention``."""
-    mode = os.environ.get("MK_ATTN", ATTN_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown MK_ATTN {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _hip_or_torch("MK_ATTN", ATTN_DEFAULT)
 
 
 def attn_info(head_dim):
@@ -2227,10 +2230,8 @@ def _attn_scale(scale, D):
 def _attn_autocast(*tensors):
     """Under device autocast ``F.scaled_dot_product_attention`` takes its operands in the autocast dtype; so do these ops (the
     fp32 output of a ``qk_norm`` LayerNorm reaches the product as bf16 either way)."""
-    if tensors[0].is_cuda and torch.is_autocast_enabled():
-        dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-        return tuple(t.to(dt) for t in tensors)
-    return tensors
+    dt = _autocast_dtype() if tensors[0].is_cuda else None
+    return tensors if dt is None else tuple(t.to(dt) for t in tensors)
 
 
 def attention(q, k, v, scale=None, dropout_p=0.0):
@@ -2274,10 +2275,7 @@ TOKEN_NORM_DEFAULT = "torch"
 def token_norm_hip():
     """``MK_TOKEN_NORM=hip|torch`` (read at call time): trailing-axis layer norms on the ``mk_token_layernorm_*`` kernels, or
     ``F.layer_norm``."""
-    mode = os.environ.get("MK_TOKEN_NORM", TOKEN_NORM_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown MK_TOKEN_NORM {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _hip_or_torch("MK_TOKEN_NORM", TOKEN_NORM_DEFAULT)
 
 
 def _trailing(normalized_shape):
@@ -2437,10 +2435,7 @@ TOKEN_LINEAR_DEFAULT = "torch"
 
 def token_linear_hip():
     """``MK_TOKEN_LINEAR=hip|torch`` (read at call time): token-major linears on the ``mk_token_linear_*`` kernels, or ``F.linear``."""
-    mode = os.environ.get("MK_TOKEN_LINEAR", TOKEN_LINEAR_DEFAULT)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown MK_TOKEN_LINEAR {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _hip_or_torch("MK_TOKEN_LINEAR", TOKEN_LINEAR_DEFAULT)
 
 
 def token_linear_info():
@@ -2449,13 +2444,6 @@ def token_linear_info():
     t = (ctypes.c_int * 6)()
     _lib.check(_lib.load().mk_token_linear_info(ctypes.addressof(t)), "mk_token_linear_info")
     return dict(zip(("tr", "tc", "tk", "to", "ti", "ts"), t))
-
-
-def _bf16_autocast():
-    if not torch.is_autocast_enabled():
-        return False
-    dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
-    return dt == torch.bfloat16
 
 
 def _row_stride(t):
@@ -2500,7 +2488,7 @@ def token_linear_supported(x, weight, bias=None):
     O, I = weight.shape
     if x.shape[-1] != I or I % 8 or O % 8 or I < 8 or O < 8:
         return False
-    if x.dtype != torch.bfloat16 and not (x.is_floating_point() and _bf16_autocast()):
+    if x.dtype != torch.bfloat16 and not (x.is_floating_point() and _autocast_dtype() == torch.bfloat16):
         return False
     if not _toklin_param_ok(weight, (O, I), x.device) or (bias is not None and not _toklin_param_ok(bias, (O,), x.device)):
         return False

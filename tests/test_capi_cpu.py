@@ -1,5 +1,6 @@
 """CPU tests of the C-ABI library: it loads, exports every symbol the header declares,
 and its host-side float64 precompute agrees with the oracle.  No kernel launches here."""
+import ctypes
 import os
 import re
 
@@ -28,6 +29,37 @@ def test_library_exports_every_declared_symbol():
         assert n in _lib.SIGNATURES, f"{n} has no ctypes signature"
     assert set(_lib.SIGNATURES) == set(names)
     assert lib.mk_version() >= 100
+
+
+_I, _F, _LL, _P8 = ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_void_p
+PINNED_SIGNATURES = {      # written out by hand from the header: together they use every C type it declares
+    "mk_last_error": (ctypes.c_char_p, []),
+    "mk_legendre_x3_bytes": (_LL, [_I, _I, _I, _I]),
+    "mk_quadrature": (_I, [_I, _I, _P8, _P8]),                                            # double*
+    "mk_rfft": (_I, [_P8, _I, _P8, _P8, _I, _I, _I, _I, _F, _F, _F, _P8]),
+    "mk_latdft_fwd": (_I, [_P8, _P8, _P8, _I, _I, _LL, _P8]),
+    "mk_token_layernorm_fwd": (_I, [_P8, _I, _LL, _P8, _I, _LL, _P8, _P8, _P8, _I, _LL, _P8, _LL, _P8, _I, _LL, _P8, _LL, _LL,
+                                    _F, _P8]),
+    "mk_token_linear_fwd": (_I, [_P8, _LL, _P8, _LL, _P8, _P8, _LL, _P8, _LL, _P8, _LL, _P8, _LL, _P8, _LL, _P8, _LL, _LL, _I,
+                                 _I, _P8]),
+    "mk_attn_bwd_dkv": (_I, [_P8] * 8 + [_I] * 5 + [_P8, _F, _P8]),                       # const long long* strides
+}
+
+
+def test_derived_signatures_match_pinned_literals():
+    """_lib.SIGNATURES is parsed from the header; these rows pin what the parser makes of each C type the header uses."""
+    for name, want in PINNED_SIGNATURES.items():
+        assert _lib.SIGNATURES[name] == want, name
+
+
+def test_signature_parser_refuses_an_unknown_type():
+    """A type the parser has no ctypes for raises and names the declaration: it never becomes an int."""
+    ok = "/* c */\n#include <x.h>\nint mk_a(const float* x, long long n /* rows */, void* stream);\nlong long mk_b(void);\n"
+    assert _lib.parse_signatures(ok) == {"mk_a": (_I, [_P8, _LL, _P8]), "mk_b": (_LL, [])}
+    with pytest.raises(ValueError, match=r"unknown parameter type 'size_t'.*mk_c\("):
+        _lib.parse_signatures(ok + "int mk_c(const float* x, size_t n);\n")
+    with pytest.raises(ValueError, match=r"unknown return type 'unsigned'.*mk_d\("):
+        _lib.parse_signatures(ok + "unsigned mk_d(int n);\n")
 
 
 def test_build_header_list_is_what_the_sources_include():

@@ -31,52 +31,14 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from event_timing import rel, timed, with_knob  # noqa: E402
 
 SHAPES = [(1, 8, 18540, 48), (1, 8, 18540, 128), (2, 12, 4050, 64)]
-
-
-def window(fn, calls):
-    """``calls`` back-to-back calls between two device events -> seconds per call."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / calls
-
-
-def timed(fns, seconds, rounds):
-    """Alternates the callables; per callable the median seconds per call over ``rounds`` windows of >= ``seconds``."""
-    calls = []
-    for f in fns:
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        est = window(f, 2)
-        calls.append(max(2, int(np.ceil(1.1 * seconds / est))))
-    out = [[] for _ in fns]
-    for _ in range(rounds):
-        for f, n, ts in zip(fns, calls, out):
-            ts.append(window(f, n))
-    return [float(np.median(ts)) for ts in out]
-
-
-def rel(a, b):
-    a, b = a.float(), b.float()
-    return (torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b)).item()
-
-
-def with_knob(value, fn):
-    def run():
-        os.environ["MK_ATTN"] = value        # read at call time
-        return fn()
-    return run
 
 
 def main():
@@ -101,8 +63,8 @@ def main():
         def fwd_bwd():
             return torch.autograd.grad(call(), inputs + params, g)
 
-        hip_f, torch_f = with_knob("hip", fwd), with_knob("torch", fwd)
-        hip_fb, torch_fb = with_knob("hip", fwd_bwd), with_knob("torch", fwd_bwd)
+        hip_f, torch_f = with_knob("MK_ATTN", "hip", fwd), with_knob("MK_ATTN", "torch", fwd)
+        hip_fb, torch_fb = with_knob("MK_ATTN", "hip", fwd_bwd), with_knob("MK_ATTN", "torch", fwd_bwd)
         err = rel(hip_f(), torch_f())          # the same function on these inputs, before any timing (a sanity bound; tests/ has parity)
         gerr = rel(hip_fb()[0], torch_fb()[0])
         assert err < 3e-2 and gerr < 3e-2, (name, shape, err, gerr)

@@ -28,54 +28,16 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from event_timing import rel, timed, with_knob  # noqa: E402
 
 E, FACTOR, LMAX, MMAX = 384, 2, 240, 241
 GRIDS = {"down": ((721, 1440, "equiangular"), (240, 480, "legendre-gauss")),
          "low": ((240, 480, "legendre-gauss"), (240, 480, "legendre-gauss"))}
-
-
-def window(fn, calls):
-    """``calls`` back-to-back calls between two device events -> seconds per call."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / calls
-
-
-def timed(fns, seconds, rounds):
-    """Alternates the callables; per callable the median seconds per call over ``rounds`` windows of >= ``seconds``."""
-    calls = []
-    for f in fns:
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        est = window(f, 2)
-        calls.append(max(2, int(np.ceil(1.1 * seconds / est))))
-    out = [[] for _ in fns]
-    for _ in range(rounds):
-        for f, n, ts in zip(fns, calls, out):
-            ts.append(window(f, n))
-    return [float(np.median(ts)) for ts in out]
-
-
-def rel(a, b):
-    a, b = (a if a.is_complex() else a.float()), (b if b.is_complex() else b.float())
-    return (torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b)).item()
-
-
-def with_knob(value, fn):
-    def run():
-        os.environ["MK_SPEC_ATTN"] = value        # read at call time
-        return fn()
-    return run
 
 
 TRACE_NET = dict(inp_shape=(240, 480), out_shape=(240, 480), scale_factor=2, inp_chans=8, out_chans=8, embed_dim=32, num_layers=2,
@@ -142,8 +104,8 @@ def main():
                     def fwd_bwd():
                         return torch.autograd.grad(mod(x)[0], [x] + params, g)
 
-                    hip_f, torch_f = with_knob("hip", fwd), with_knob("torch", fwd)
-                    hip_fb, torch_fb = with_knob("hip", fwd_bwd), with_knob("torch", fwd_bwd)
+                    hip_f, torch_f = with_knob("MK_SPEC_ATTN", "hip", fwd), with_knob("MK_SPEC_ATTN", "torch", fwd)
+                    hip_fb, torch_fb = with_knob("MK_SPEC_ATTN", "hip", fwd_bwd), with_knob("MK_SPEC_ATTN", "torch", fwd_bwd)
                     err = rel(hip_f(), torch_f())          # the same function on these inputs, before any timing
                     gerr = rel(hip_fb()[0], torch_fb()[0])
                     # (the gradient: of the 4e7 pre-activation components a few dozen lie within fp32 rounding of zero, where the

@@ -34,6 +34,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from event_timing import rel, timed, with_knob  # noqa: E402
 
 # (name, leading shape, C): the linears of a block follow from C
 SHAPES = [("vit_73ch", (1, 18540), 384), ("vit_73ch_big", (1, 18540), 1024), ("2x4050", (2, 4050), 768)]
@@ -43,45 +45,6 @@ HEAD = ("head", (1, 18540), 384, 4088)
 def block_linears(C):
     """(name, I, O, epilogue) of the four linears of a block of width C."""
     return [("qkv", C, 3 * C, "plain"), ("proj", C, C, "plain"), ("fc1", C, 4 * C, "gelu"), ("fc2", 4 * C, C, "addend")]
-
-
-def window(fn, calls):
-    """``calls`` back-to-back calls between two device events -> seconds per call."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / calls
-
-
-def timed(fns, seconds, rounds):
-    """Alternates the callables; per callable the median seconds per call over ``rounds`` windows of >= ``seconds``."""
-    calls = []
-    for f in fns:
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        est = window(f, 2)
-        calls.append(max(2, int(np.ceil(1.1 * seconds / est))))
-    out = [[] for _ in fns]
-    for _ in range(rounds):
-        for f, n, ts in zip(fns, calls, out):
-            ts.append(window(f, n))
-    return [float(np.median(ts)) for ts in out]
-
-
-def rel(a, b):
-    a, b = a.float(), b.float()
-    return (torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b)).item()
-
-
-def with_knob(value, fn):
-    def run():
-        os.environ["MK_TOKEN_LINEAR"] = value        # read at call time
-        return fn()
-    return run
 
 
 def trace_steps(n):
@@ -129,8 +92,8 @@ def main():
         def fwd_bwd():
             return torch.autograd.grad(call(), inputs + params, g)
 
-        hip_f, torch_f = with_knob("hip", fwd), with_knob("torch", fwd)
-        hip_fb, torch_fb = with_knob("hip", fwd_bwd), with_knob("torch", fwd_bwd)
+        hip_f, torch_f = with_knob("MK_TOKEN_LINEAR", "hip", fwd), with_knob("MK_TOKEN_LINEAR", "torch", fwd)
+        hip_fb, torch_fb = with_knob("MK_TOKEN_LINEAR", "hip", fwd_bwd), with_knob("MK_TOKEN_LINEAR", "torch", fwd_bwd)
         err = rel(hip_f(), torch_f())          # the same function on these inputs, before any timing (a sanity bound; tests/ has parity)
         gh, gt = hip_fb(), torch_fb()
         gerr = max(rel(a, b) for a, b in zip(gh, gt))

@@ -30,49 +30,18 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from event_timing import rel, timed  # noqa: E402
 
 TOKEN_SHAPES = [(18540, 384), (8100, 768)]
 AFNO_SHAPES = [(768, 90, 180), (1536, 90, 180)]
 F32, BF16 = torch.float32, torch.bfloat16
 EPS = 1e-6
-
-
-def window(fn, calls):
-    """``calls`` back-to-back calls between two device events -> seconds per call."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e-3 / calls
-
-
-def timed(fns, seconds, rounds):
-    """Alternates the callables; per callable the median seconds per call over ``rounds`` windows of >= ``seconds``."""
-    calls = []
-    for f in fns:
-        for _ in range(2):
-            f()
-        torch.cuda.synchronize()
-        est = window(f, 2)
-        calls.append(max(2, int(np.ceil(1.1 * seconds / est))))
-    out = [[] for _ in fns]
-    for _ in range(rounds):
-        for f, n, ts in zip(fns, calls, out):
-            ts.append(window(f, n))
-    return [float(np.median(ts)) for ts in out]
-
-
-def rel(a, b):
-    a, b = a.float(), b.float()
-    return (torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b)).item()
 
 
 def main():
