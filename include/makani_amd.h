@@ -312,6 +312,28 @@ int mk_spec_unpack(const float* c_prv, float* c_std, int bc, int lloc, int mloc,
  * elements otherwise.  One launch, no allocation, no synchronisation.  Each is the adjoint of the other. */
 int mk_tokens_to_fields(const void* tok, void* fld, int dtype, int batch, int n, int c, void* stream);
 int mk_fields_to_tokens(const void* fld, const void* addend, void* tok, int dtype, int batch, int n, int c, void* stream);
+/* image [batch][C][H][W]  <->  patch rows [batch hp wp][ldt] (csrc/patch.hip): the gather in front of the patch-embedding GEMM of
+ * ViT / AFNOv1 (a non-overlapping strided convolution is one GEMM on these rows) and the un-patchify behind their heads.
+ * hp = H / p0, wp = W / p1; row r = (b hp + y) wp + x holds the patch at (y p0, x p1); element (b, c, y p0 + i, x p1 + j) is feature
+ *   order 0: f = (c p0 + i) p1 + j      the order of a convolution weight [E][C][p0][p1] seen as [E][C p0 p1]
+ *   order 1: f = (i p1 + j) C + c       the order both heads write (`einsum("nhwpqc->nchpwq")`, `permute(0, 5, 1, 3, 2, 4)`)
+ *   mk_patchify:   tok[r][f] = img[b][c][y p0 + i][x p1 + j]
+ *   mk_unpatchify: the inverse; for one order each is the other's inverse and adjoint.
+ * dtypes: 0 fp32, 1 bf16 on either side, in every combination: narrowing rounds once to nearest even (a NaN becomes 0x7fc0),
+ * widening is exact, equal dtypes pass bit for bit.  ldt >= C p0 p1 is the row stride in elements; columns past C p0 p1 are
+ * neither read nor written.  Any batch, C, p0, p1 >= 1 and H, W the patch divides; bases aligned to their elements; 64-bit
+ * offsets.  16-byte loads and stores on a side whose base is 16-byte aligned and whose contiguous runs are whole vectors, single
+ * elements otherwise; both sides walk their contiguous axis (a tile goes through LDS).  Every destination element is written
+ * exactly once.  One launch, no allocation, no synchronisation; arguments are validated (code 1) before the launch. */
+/* The tile the two kernels use for a geometry (no device needed): tile[14] = CC channels, IT patch rows, TX patches across, JT
+ * patch columns, the LDS row pitch in words, the tile counts along channels / patch rows / patches across / patch columns, the
+ * words of LDS a workgroup has, and whether 16-byte-aligned bases would take 16-byte accesses on the image side (fp32, bf16)
+ * and on the token side (fp32, bf16) at row stride ldt.  tests/test_patch_cpu.py runs a model of the index maps on it. */
+int mk_patch_tile_info(int C, int H, int W, int p0, int p1, int order, long long ldt, int* tile);
+int mk_patchify(const void* img, int img_dtype, void* tok, int tok_dtype, long long ldt, int batch, int C, int H, int W, int p0,
+                int p1, int order, void* stream);
+int mk_unpatchify(const void* tok, int tok_dtype, long long ldt, void* img, int img_dtype, int batch, int C, int H, int W, int p0,
+                  int p1, int order, void* stream);
 
 /* ---- fused pointwise ops of the FNO block (rows = B*C <= 65535, P = H*W multiple of 8) -------- */
 /* dtype: 0 = fp32, 1 = bf16 storage; arithmetic is fp32.

@@ -18,7 +18,9 @@ hard_thresholding_fraction)`` the latitude rows ``t - k ... min(t + k, H) - 1`` 
 
 A block's norms are ``layers.LayerNorm`` (``norm2`` one launch for the add of ``double_skip``, the norm and the sum, under
 ``MK_TOKEN_NORM=hip``), its MLP one ``ops.token_mlp`` node with the last residual add in ``fc2``'s epilogue (under
-``MK_TOKEN_LINEAR=hip`` and bf16 autocast).  Patch embedding, the position add and the un-patchify permute stay torch ops.
+``MK_TOKEN_LINEAR=hip`` and bf16 autocast).  Under ``MK_PATCH=hip`` (default ``ops.PATCH_DEFAULT``) patch embedding and the position
+add are ``PatchEmbed.forward_tokens`` -- ``mk_patchify`` and the token GEMM, for bf16 images or under bf16 autocast -- and the
+un-patchify behind ``head`` one ``mk_unpatchify`` pass (csrc/patch.hip); ``MK_PATCH=torch`` keeps the convolution and the permute.
 ``MK_AFNOV1=torch`` (the default is ``hip``, timings: DESIGN section 27), a pair that is not ``hip_ready`` (``MK_PLANAR_FFT`` defaults to
 ``torch``) and every case the kernels do not take run ``AFNO2D._forward_torch``, the reference's formulation in torch ops.
 
@@ -286,8 +288,7 @@ class AdaptiveFourierNeuralOperatorNet(nn.Module):
 
     def forward_features(self, x):
         B = x.shape[0]
-        x = self.patch_embed(x).transpose(1, 2)
-        x = x + self.pos_embed
+        x = self.patch_embed.forward_tokens(x, self.pos_embed)
         x = self.pos_drop(x)
         x = x.reshape(B, self.h, self.w, self.embed_dim)
         for blk in self.blocks:
@@ -297,7 +298,5 @@ class AdaptiveFourierNeuralOperatorNet(nn.Module):
     def forward(self, x):
         x = self.forward_features(x)
         x = self.head(x)
-        b = x.shape[0]
-        xv = x.view(b, self.h, self.w, self.patch_size[0], self.patch_size[1], -1)
-        xvt = torch.permute(xv, (0, 5, 1, 3, 2, 4)).contiguous()
-        return xvt.view(b, -1, (self.h * self.patch_size[0]), (self.w * self.patch_size[1]))
+        # features (p0, p1, c): permute(0, 5, 1, 3, 2, 4) of [b, h, w, p0, p1, c] is order 1
+        return ops.unpatchify(x, self.patch_size, self.out_chans, (self.h * self.patch_size[0], self.w * self.patch_size[1]), order=1)

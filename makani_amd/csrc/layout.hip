@@ -2,6 +2,7 @@
 // private channels-last spectral layout [L][M][BC] complex64 (see makani_amd.h).
 // A complex transpose of a [BC] x [L*M] matrix through 32 x 32 LDS tiles; HBM bound.
 #include "common.h"
+#include "layout_elem.h"
 #include "../../include/makani_amd.h"
 
 namespace {
@@ -47,31 +48,6 @@ __global__ __launch_bounds__(256) void transpose_c64_kernel(const float2* __rest
 // VEC: R and C are whole numbers of 16-byte vectors and the operands 16-byte aligned -- a vector is wholly inside the matrix
 // or wholly outside; otherwise single elements.  Ragged tiles load and store nothing outside the matrix.
 constexpr int LT = 64;
-
-template <typename T> struct LayoutElem;
-template <> struct LayoutElem<float> {
-    static __device__ __forceinline__ unsigned bits(float v) { return __float_as_uint(v); }
-    static __device__ __forceinline__ float value(unsigned b) { return __uint_as_float(b); }
-    static __device__ __forceinline__ unsigned round(float v) { return __float_as_uint(v); }
-    static __device__ __forceinline__ float from(unsigned b) { return __uint_as_float(b); }
-};
-template <> struct LayoutElem<unsigned short> {     // bf16
-    static __device__ __forceinline__ unsigned bits(unsigned short v) { return v; }
-    static __device__ __forceinline__ unsigned short from(unsigned b) { return (unsigned short)b; }
-    static __device__ __forceinline__ float value(unsigned b) { return __uint_as_float(b << 16); }
-    static __device__ __forceinline__ unsigned round(float v) {     // to nearest even; NaN stays NaN
-        const unsigned u = __float_as_uint(v);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    }
-};
-
-// word k of a 16-byte vector of T: one fp32, or the k-th of eight bf16
-template <typename T> __device__ __forceinline__ unsigned vec_word(const uint4& v, int k) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    if constexpr (sizeof(T) == 4) return w[k];
-    else return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-}
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(256) void transpose_add_kernel(const T* __restrict__ src, const T* __restrict__ addend, T* __restrict__ dst,

@@ -787,7 +787,8 @@ class DropPath(nn.Module):
 
 
 class PatchEmbed(nn.Module):
-    """layers.py:65-83: a strided convolution over non-overlapping patches, ``[B, C, H, W]`` -> ``[B, embed_dim, patches]``."""
+    """layers.py:65-83: a strided convolution over non-overlapping patches, ``[B, C, H, W]`` -> ``[B, embed_dim, patches]``;
+    ``forward_tokens`` gives the token-major form the patch networks consume, on HIP kernels under ``MK_PATCH=hip``."""
 
     def __init__(self, img_size=(224, 224), patch_size=(16, 16), in_chans=3, embed_dim=768):
         super().__init__()
@@ -804,6 +805,20 @@ class PatchEmbed(nn.Module):
         assert H == self.img_size[0] and W == self.img_size[1], \
             f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
         return self.proj(x).flatten(2)
+
+    def forward_tokens(self, x, pos_embed=None):
+        """The tokens ``[B, patches, embed_dim]`` (``+ pos_embed``): ``forward(x).transpose(1, 2)`` as both patch networks use it.
+        Under ``MK_PATCH=hip`` (read and validated on every call), for what ``ops.patch_embed_supported`` takes -- an fp32 or bf16
+        image under bf16 autocast, or bf16 image and parameters without it -- one ``ops.patch_embed`` node: ``mk_patchify`` and the token GEMM with the bias and
+        the position add in its epilogue.  Everything else is the convolution."""
+        H, W = x.shape[-2], x.shape[-1]
+        assert H == self.img_size[0] and W == self.img_size[1], \
+            f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
+        from . import ops
+        if ops.patch_hip() and ops.patch_embed_supported(x, self.proj.weight, self.proj.bias):
+            return ops.patch_embed(x, self.proj.weight, self.proj.bias, pos_embed)
+        x = self.proj(x).flatten(2).transpose(1, 2)
+        return x if pos_embed is None else x + pos_embed
 
 
 class EncoderDecoder(nn.Module):

@@ -2707,3 +2707,235 @@ def token_mlp(x, w1, b1, w2, b2, addend=None):
     F = torch.nn.functional
     y = F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
     return y if addend is None else addend + y
+
+
+# ----------------------------------------------------------------------------
+# patch rows (csrc/patch.hip): the gather in front of the patch-embedding GEMM and the un-patchify behind the heads
+# ----------------------------------------------------------------------------
+# Opt-in by the rule of DESIGN section 19 until every row of tools/patch_bench.py has been measured faster than the torch path
+# (DESIGN section 29).
+PATCH_DEFAULT = "torch"
+_PATCH_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def patch_hip():
+    """``MK_PATCH=hip|torch`` (read at call time): patch embedding and un-patchify on ``mk_patchify`` / ``mk_unpatchify`` around the
+    ``mk_token_linear_*`` GEMM, or ``nn.Conv2d`` and torch's permuted copies."""
+    return _hip_or_torch("MK_PATCH", PATCH_DEFAULT)
+
+
+def _patch_geometry(C, H, W, patch):
+    p0, p1 = int(patch[0]), int(patch[1])
+    if p0 < 1 or p1 < 1 or H % p0 or W % p1:
+        raise ValueError(f"patch {p0} x {p1} does not divide the grid {H} x {W}")
+    return p0, p1, H // p0, W // p1, C * p0 * p1
+
+
+def _patchify_torch(img, patch, order):
+    B, C, H, W = img.shape
+    p0, p1, hp, wp, F = _patch_geometry(C, H, W, patch)
+    v = img.reshape(B, C, hp, p0, wp, p1)
+    v = v.permute(0, 2, 4, 1, 3, 5) if order == 0 else v.permute(0, 2, 4, 3, 5, 1)
+    return v.reshape(B, hp * wp, F)
+
+
+def _patch_batch(tok, hp, wp, F):
+    """The batch of token rows ``[B, ..., F]`` with ``hp wp`` rows per sample; refuses any other shape."""
+    if tok.dim() < 2 or tok.shape[-1] != F or tok.numel() == 0 or tok.numel() % (hp * wp * F):
+        raise ValueError(f"token rows of shape {tuple(tok.shape)} are not [B, ..., {F}] with {hp * wp} rows per sample")
+    return tok.numel() // (hp * wp * F)
+
+
+def _unpatchify_torch(tok, patch, C, H, W, order):
+    p0, p1, hp, wp, F = _patch_geometry(C, H, W, patch)
+    B = _patch_batch(tok, hp, wp, F)
+    if order == 0:
+        v = tok.reshape(B, hp, wp, C, p0, p1).permute(0, 3, 1, 4, 2, 5)
+    else:
+        v = tok.reshape(B, hp, wp, p0, p1, C).permute(0, 5, 1, 3, 2, 4)
+    return v.reshape(B, C, H, W)
+
+
+def _patch_order(order):
+    if order not in (0, 1):
+        raise ValueError(f"unknown patch feature order {order!r} (0: (c, i, j), the convolution's | 1: (i, j, c), the heads')")
+    return int(order)
+
+
+def patchify_raw(img, tok, patch, order=0, ldt=None):
+    """``mk_patchify``: ``img`` ``[B, C, H, W]`` contiguous -> the preallocated rows ``tok`` (``B hp wp`` rows at stride ``ldt``,
+    default the features of a token), fp32 or bf16 on either side."""
+    _need_cuda(img, tok)
+    B, C, H, W = img.shape
+    assert img.is_contiguous() and img.device == tok.device
+    _lib.check(_lib.load().mk_patchify(img.data_ptr(), _PATCH_DTYPES[img.dtype], tok.data_ptr(), _PATCH_DTYPES[tok.dtype],
+                                       C * patch[0] * patch[1] if ldt is None else ldt, B, C, H, W, patch[0], patch[1], order,
+                                       _stream()), "mk_patchify")
+    return tok
+
+
+def unpatchify_raw(tok, img, patch, order=0, ldt=None):
+    """``mk_unpatchify``: the rows ``tok`` (stride ``ldt``) -> the preallocated contiguous ``img`` ``[B, C, H, W]``."""
+    _need_cuda(img, tok)
+    B, C, H, W = img.shape
+    assert img.is_contiguous() and img.device == tok.device
+    _lib.check(_lib.load().mk_unpatchify(tok.data_ptr(), _PATCH_DTYPES[tok.dtype], C * patch[0] * patch[1] if ldt is None else ldt,
+                                         img.data_ptr(), _PATCH_DTYPES[img.dtype], B, C, H, W, patch[0], patch[1], order, _stream()),
+               "mk_unpatchify")
+    return img
+
+
+class _Patchify(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, patch, order, dtype):
+        B, C, H, W = img.shape
+        p0, p1, hp, wp, F = _patch_geometry(C, H, W, patch)
+        ctx.cfg = (tuple(img.shape), img.dtype, (p0, p1), order)
+        return patchify_raw(img.contiguous(), torch.empty(B, hp * wp, F, dtype=dtype, device=img.device), (p0, p1), order)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        shape, dtype, patch, order = ctx.cfg
+        g = g if g.dtype in _PATCH_DTYPES else g.float()
+        return unpatchify_raw(g.contiguous(), torch.empty(shape, dtype=dtype, device=g.device), patch, order), None, None, None
+
+
+class _Unpatchify(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tok, patch, C, H, W, order, dtype):
+        p0, p1, hp, wp, F = _patch_geometry(C, H, W, patch)
+        B = _patch_batch(tok, hp, wp, F)
+        ctx.cfg = (tuple(tok.shape), tok.dtype, (p0, p1), order)
+        return unpatchify_raw(tok.contiguous(), torch.empty(B, C, H, W, dtype=dtype, device=tok.device), (p0, p1), order)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        shape, dtype, patch, order = ctx.cfg
+        g = g if g.dtype in _PATCH_DTYPES else g.float()
+        return (patchify_raw(g.contiguous(), torch.empty(shape, dtype=dtype, device=g.device), patch, order),) + (None,) * 6
+
+
+def _patch_kernels_take(t, dtype):
+    return t.is_cuda and t.numel() > 0 and t.dtype in _PATCH_DTYPES and dtype in _PATCH_DTYPES
+
+
+def patchify(img, patch, order=0, dtype=None):
+    """``img`` ``[B, C, H, W]`` -> the patch rows ``[B, hp wp, C p0 p1]`` in ``dtype`` (default the image's): row ``y wp + x`` is the
+    patch at ``(y p0, x p1)``, its features in ``order`` 0 ``(c, i, j)`` -- a convolution weight's ``view(E, -1)`` -- or 1
+    ``(i, j, c)``, the heads'.  One ``mk_patchify`` pass on the device (fp32 / bf16; the cast in the same pass), its backward one
+    ``mk_unpatchify`` pass into the image's dtype.  CPU tensors, other dtypes and ``MK_PATCH=torch`` take ``reshape`` / ``permute``."""
+    order = _patch_order(order)
+    dtype = img.dtype if dtype is None else dtype
+    assert img.dim() == 4, "[B, C, H, W]"
+    if patch_hip() and _patch_kernels_take(img, dtype):
+        return _Patchify.apply(img, tuple(patch), order, dtype)
+    return _patchify_torch(img, patch, order).to(dtype)
+
+
+def unpatchify(tok, patch, out_chans, img_shape, order, dtype=None):
+    """The inverse of ``patchify``: ``tok`` ``[B, ..., C p0 p1]`` (``hp wp`` rows per sample) -> ``[B, C, H, W]`` with ``C =
+    out_chans``, ``(H, W) = img_shape``.  ``order`` 1 is the rearrangement behind both patch heads (``einsum("nhwpqc->nchpwq")`` of
+    ViT, ``permute(0, 5, 1, 3, 2, 4)`` of AFNOv1).  One ``mk_unpatchify`` pass, its backward one ``mk_patchify`` pass into the
+    rows' dtype; same dispatch as ``patchify``."""
+    order = _patch_order(order)
+    dtype = tok.dtype if dtype is None else dtype
+    H, W = int(img_shape[0]), int(img_shape[1])
+    if patch_hip() and _patch_kernels_take(tok, dtype):
+        return _Unpatchify.apply(tok, tuple(patch), int(out_chans), H, W, order, dtype)
+    return _unpatchify_torch(tok, patch, int(out_chans), H, W, order).to(dtype)
+
+
+def patch_embed_supported(img, weight, bias=None):
+    """True for what ``_PatchEmbed`` takes: ``img`` ``[B, C, H, W]`` on the device, fp32 or bf16 under bf16 device autocast -- which
+    takes it in bf16 as the convolution does -- or, without autocast, bf16 with bf16 parameters (``nn.Conv2d`` refuses mixed dtypes
+    there, and so does this); ``weight`` ``[E, C, p0, p1]`` with a patch that divides the grid, ``C p0 p1`` and ``E`` multiples of 8,
+    ``weight`` and ``bias`` ``[E]`` (or None) fp32 or bf16 on the same device.  Independent of ``MK_TOKEN_LINEAR``."""
+    if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.numel() > 0 and torch.is_tensor(weight) and weight.dim() == 4):
+        return False
+    E, C, p0, p1 = weight.shape
+    F = C * p0 * p1
+    if img.shape[1] != C or img.shape[2] % p0 or img.shape[3] % p1 or F % 8 or E % 8:
+        return False
+    if img.dtype not in _PATCH_DTYPES:
+        return False
+    if _autocast_dtype() != torch.bfloat16 and not all(t.dtype == torch.bfloat16 for t in (img, weight, bias) if t is not None):
+        return False
+    return _toklin_param_ok(weight, (E, C, p0, p1), img.device) and (bias is None or _toklin_param_ok(bias, (E,), img.device))
+
+
+class _PatchEmbed(torch.autograd.Function):
+    """A non-overlapping strided convolution as one GEMM on patch rows: ``mk_patchify`` (order 0, to bf16: the autocast cast of the
+    image in the same pass), the weight's bf16 image, ``mk_token_linear_fwd`` with the fp32 bias.  With ``pos`` (fp32 ``[N, E]``)
+    one GEMM launch per sample with ``pos`` as its addend: ``pos + float(bf16(acc + bias))``, fp32.  Saves the patch rows and the
+    weight image.  Backward: the slab kernel for ``dW`` / ``db``; the batch sum of the gradient for ``pos``; for the image, where it
+    asks, a transposed pack, the GEMM to bf16 rows and ``mk_unpatchify`` into the image's dtype."""
+
+    @staticmethod
+    def forward(ctx, img, weight, bias, pos):
+        B, C, H, W = img.shape
+        E, _, p0, p1 = weight.shape
+        _, _, hp, wp, F = _patch_geometry(C, H, W, (p0, p1))
+        N = hp * wp
+        rows = patchify_raw(img.detach().contiguous(), torch.empty(B * N, F, dtype=torch.bfloat16, device=img.device), (p0, p1), 0)
+        wimg = token_linear_pack_raw(weight.detach().reshape(E, F))
+        bf = _toklin_bias(bias)
+        if pos is not None:
+            pr, p_ld = _toklin_rows(pos.detach().reshape(N, E))
+            out = torch.empty(B, N, E, dtype=torch.float32, device=img.device)
+            for b in range(B):
+                token_linear_fwd_raw(rows[b * N:(b + 1) * N], F, wimg, bf, N, addend=pr, addend_ld=p_ld, out_f32=out[b])
+        else:
+            out = torch.empty(B, N, E, dtype=torch.bfloat16, device=img.device)
+            token_linear_fwd_raw(rows, F, wimg, bf, B * N, y=out)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(rows, wimg)
+        ctx.cfg = (tuple(img.shape), img.dtype, tuple(weight.shape), weight.dtype, None if bias is None else bias.dtype,
+                   None if pos is None else tuple(pos.shape))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        img_shape, img_dtype, w_shape, w_dtype, b_dtype, pos_shape = ctx.cfg
+        need = ctx.needs_input_grad
+        dpos = g.sum(0).reshape(pos_shape) if (pos_shape is not None and need[3]) else None
+        if not ctx.saved_tensors:
+            return None, None, None, dpos
+        rows, wimg = ctx.saved_tensors
+        E, F = wimg.shape
+        R = rows.shape[0]
+        gr, g_ld = _toklin_grad_rows(g, E)
+        dx = dw = db = None
+        want_db = b_dtype is not None and need[2]
+        if need[1] or want_db:
+            dw, db = token_linear_wgrad_raw(gr, g_ld, rows, F, R, E, F, want_db)
+            dw = _toklin_param_grad(dw, w_dtype).view(w_shape) if need[1] else None
+            db = _toklin_param_grad(db, b_dtype)
+        if need[0]:
+            dxr = torch.empty(R, F, dtype=torch.bfloat16, device=g.device)
+            token_linear_fwd_raw(gr, g_ld, token_linear_pack_raw(wimg, transpose=True), None, R, y=dxr)
+            dx = unpatchify_raw(dxr, torch.empty(img_shape, dtype=img_dtype, device=g.device), w_shape[2:], 0)
+        return dx, dw, db, dpos
+
+
+def _patch_pos_fused(pos, img, N, E):
+    return (torch.is_tensor(pos) and pos.dtype == torch.float32 and pos.device == img.device
+            and tuple(pos.shape) in ((1, N, E), (N, E)))
+
+
+def patch_embed(img, weight, bias=None, pos=None):
+    """``F.conv2d(img, weight, bias, stride=patch).flatten(2).transpose(1, 2)`` (``+ pos``): ``[B, C, H, W]`` -> ``[B, N, E]`` for
+    ``weight`` ``[E, C, p0, p1]``.  Under ``MK_PATCH=hip``, for what ``patch_embed_supported`` takes, one autograd function on
+    ``mk_patchify`` and the ``mk_token_linear_*`` kernels: a bf16 result, or with an fp32 ``pos`` (``[1, N, E]`` or ``[N, E]``) the
+    fp32 sum ``pos + float(bf16(conv))`` from the GEMM's epilogue -- the rounding points of the torch expression under bf16
+    autocast.  Everything else takes the torch expression."""
+    if patch_hip() and patch_embed_supported(img, weight, bias):
+        E, _, p0, p1 = weight.shape
+        N = (img.shape[2] // p0) * (img.shape[3] // p1)
+        if pos is None or _patch_pos_fused(pos, img, N, E):
+            return _PatchEmbed.apply(img, weight, bias, pos)
+        return _PatchEmbed.apply(img, weight, bias, None) + pos
+    y = torch.nn.functional.conv2d(img, weight, bias, stride=tuple(weight.shape[2:])).flatten(2).transpose(1, 2)
+    return y if pos is None else y + pos

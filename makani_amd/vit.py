@@ -25,7 +25,12 @@ validated on every call; default ``ops.TOKEN_LINEAR_DEFAULT``) with bf16 tokens 
 the block's residual add in ``fc2``'s (when ``drop_path`` is an identity; with stochastic depth the block keeps the separate add)
 and the GELU gradient in the epilogue of ``fc2``'s data gradient.  Weight gradients are accumulated and returned in fp32.  fp32
 tokens without autocast, feature counts that are no multiple of 8, CPU tensors and ``MK_TOKEN_LINEAR=torch`` take ``F.linear``.
-``PatchEmbed`` (a strided convolution) and the un-patchify einsum behind ``head`` stay torch ops.
+
+Patch embedding and the un-patchify behind ``head`` run on the layout passes of csrc/patch.hip under ``MK_PATCH=hip`` (read and
+validated on every call; default ``ops.PATCH_DEFAULT``): ``PatchEmbed.forward_tokens`` is ``mk_patchify`` to bf16 patch rows and the
+token GEMM with the convolution's bias and the position add in its epilogue (bf16 images, or bf16 autocast; an fp32 run keeps
+``nn.Conv2d``), ``forward_head`` ends in one ``mk_unpatchify`` pass (fp32 and bf16).  ``MK_PATCH=torch`` and CPU tensors take the
+convolution and torch's permuted copy.
 
 Out of scope: ``DistributedAttention`` / ``DistributedMLP`` / ``DistributedMatmul`` -- matmul group sizes (``fin``, ``fout``) above 1
 raise ``NotImplementedError``; data parallelism works as for any module.
@@ -166,15 +171,14 @@ class VisionTransformer(nn.Module):
             nn.init.constant_(m.weight, 1.0)
 
     def prepare_tokens(self, x):
-        x = self.patch_embed(x).transpose(1, 2)          # [B, N, embed_dim]
-        return self.pos_drop(x + self.pos_embed)
+        return self.pos_drop(self.patch_embed.forward_tokens(x, self.pos_embed))          # [B, N, embed_dim]
 
     def forward_head(self, x):
         B = x.shape[0]
         h, w = self.patch_embed.red_img_size
         ph, pw = self.patch_size
-        x = self.head(x.reshape(B, h, w, self.embed_dim)).reshape(B, h, w, ph, pw, self.out_ch)
-        return torch.einsum("nhwpqc->nchpwq", x).reshape(B, self.out_ch, self.img_size[0], self.img_size[1])
+        x = self.head(x.reshape(B, h, w, self.embed_dim))           # features (p, q, c): "nhwpqc->nchpwq" is order 1
+        return ops.unpatchify(x, self.patch_size, self.out_ch, self.img_size, order=1)
 
     def forward(self, x):
         x = self.prepare_tokens(x)
