@@ -716,6 +716,41 @@ long long mk_token_linear_wgrad_workspace(long long R, int O, int I, int slabs);
 int mk_token_linear_wgrad(const void* dy, long long lddy, const void* x, long long ldx, float* dw, long long lddw, float* db,
                           void* workspace, long long R, int O, int I, int slabs, void* stream);
 
+/* ---- token-major linear layers on fp32 rows (csrc/x3_toklinear.hip): the same nn.Linear products outside autocast -- the
+ * reference's fp32 run (`amp_mode none`): qkv / proj / fc1 / fc2 / head of the ViT (models/networks/vit.py:14-104), the Mlp of
+ * AFNOv1 (models/networks/afnonet.py:26-44) and the "traditional" MLP / EncoderDecoder (layers.py:86-216) -- fp32-accurate on the bf16x3
+ * engine (csrc/x3_engine.h) instead of a vendor fp32 GEMM.  Every matrix is fp32, a 16-byte-aligned base pointer and a row
+ * stride in elements (a multiple of 4, at least the row length); the feature axis is contiguous.  I and O are multiples of 4,
+ * R >= 1.  The 32-bit offsets of a tile need 129 ld 4 < 2^31 for operands read row-major over the contraction (x, and w with
+ * w_kmajor 0) and 33 ld 4 < 2^31 for k-major ones (w with w_kmajor 1, dy and x of the weight gradient).  A ragged last tile
+ * loads zeros and stores nothing; columns past a row's length are neither read nor written.  Each entry point validates
+ * and returns nonzero with a message before any launch; all launches go on `stream`, nothing is allocated or synchronised, so
+ * it can be captured.  No atomics: the same inputs give the same bits.
+ * mk_token_linear_x3_info: t[3] = tile rows, tile columns, k-step.  Needs no device.
+ * mk_token_linear_x3_fwd (F.linear, and F.linear's data gradient): I is the contraction length, O the output's row length,
+ *     w_kmajor 0:  acc[r][o] = sum_k x[r][k] w[o w_ld + k]      w [O][I]
+ *     w_kmajor 1:  acc[r][o] = sum_k x[r][k] w[k w_ld + o]      w [I][O]: with x = the output's gradient the data gradient,
+ *                                                               from the weight as it is stored
+ *   then, in this order, whatever is given:  v = acc + bias[o];  pre = v;  v = gelu(v) if act (exact erf form);  v += addend[r][o];
+ *   v *= gelu'(aux[r][o]);  y = v.  bias fp32 [O] (16-byte aligned); y, pre, addend, aux [R][O].  Accepted combinations
+ *   (bias optional unless stated): y alone;  act = 1 with or without pre (fc1);  addend with act = 0 (fc2 with the block's
+ *   residual, the patch embedding with pos_embed);  aux with act = 0 and without bias, pre or addend (with w_kmajor 1: fc2's
+ *   data gradient times gelu'(pre) = the gradient of fc1's pre-activation).  pre needs act = 1.  Anything else is refused.
+ * mk_token_linear_x3_wgrad (the weight / bias gradient of F.linear): dw[o][i] = sum_r dy[r][o] x[r][i], dy [R][O], x [R][I],
+ *   dw [O][I].  The tokens are cut into `slabs` (1 ... 64; fewer where R has fewer 32-row steps) ranges of whole steps, each
+ *   into an fp32 panel in `ws`; a second launch adds the panels in slab order.  One slab stores dw directly.  slabs = 0 chooses:
+ *   about three workgroups per compute unit, no slab shorter than 4 steps.  db (fp32 [O], 16-byte aligned, or NULL):
+ *   db[o] = sum_r dy[r][o], float64 partials of 128 rows (one more launch) added in row order by the finishing launch.
+ *   mk_token_linear_x3_wgrad_workspace: the bytes `ws` must hold (16-byte aligned, no need to clear it; NULL is accepted when
+ *   there is one slab and no db), -1 for sizes the kernels refuse. */
+int mk_token_linear_x3_info(int* t);
+int mk_token_linear_x3_fwd(const float* x, long long x_ld, const float* w, long long w_ld, int w_kmajor, const float* bias,
+                           float* y, long long y_ld, float* pre, long long pre_ld, const float* addend, long long addend_ld,
+                           const float* aux, long long aux_ld, int act, long long R, int O, int I, void* stream);
+long long mk_token_linear_x3_wgrad_workspace(long long R, int O, int I, int slabs);
+int mk_token_linear_x3_wgrad(const float* dy, long long dy_ld, const float* x, long long x_ld, float* dw, long long dw_ld,
+                             float* db, void* ws, long long R, int O, int I, int slabs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -727,12 +727,16 @@ class InstanceNorm2d(nn.InstanceNorm2d):
 
 class Linear(nn.Linear):
     """``nn.Linear`` (same constructor, parameters and ``state_dict`` entries) on the ``mk_token_linear_*`` kernels under
-    ``MK_TOKEN_LINEAR=hip`` (read and validated on every call).  On the CPU, on inputs that ``ops.token_linear_supported`` declines
-    and with ``MK_TOKEN_LINEAR=torch`` it is exactly ``nn.Linear.forward``."""
+    ``MK_TOKEN_LINEAR=hip`` and, for fp32 rows outside autocast, on the ``mk_token_linear_x3_*`` kernels under
+    ``MK_TOKEN_LINEAR_FP32=hip`` (both read and validated on every call).  On the CPU, on inputs that ``ops.token_linear_supported``
+    and ``ops.token_linear_x3_supported`` decline and with both knobs at ``torch`` it is exactly ``nn.Linear.forward``."""
 
     def forward(self, x):
         from . import ops
+        fp32_hip = ops.token_linear_fp32_hip()
         if ops.token_linear_hip() and ops.token_linear_supported(x, self.weight, self.bias):
+            return ops.token_linear(x, self.weight, self.bias)
+        if fp32_hip and ops.token_linear_x3_supported(x, self.weight, self.bias):
             return ops.token_linear(x, self.weight, self.bias)
         return super().forward(x)
 
@@ -810,12 +814,15 @@ class PatchEmbed(nn.Module):
         """The tokens ``[B, patches, embed_dim]`` (``+ pos_embed``): ``forward(x).transpose(1, 2)`` as both patch networks use it.
         Under ``MK_PATCH=hip`` (read and validated on every call), for what ``ops.patch_embed_supported`` takes -- an fp32 or bf16
         image under bf16 autocast, or bf16 image and parameters without it -- one ``ops.patch_embed`` node: ``mk_patchify`` and the token GEMM with the bias and
-        the position add in its epilogue.  Everything else is the convolution."""
+        the position add in its epilogue; an fp32 image outside autocast takes the same node on the fp32 kernels when
+        ``MK_TOKEN_LINEAR_FP32=hip`` is set as well (``ops.patch_embed_x3_supported``).  Everything else is the convolution."""
         H, W = x.shape[-2], x.shape[-1]
         assert H == self.img_size[0] and W == self.img_size[1], \
             f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
         from . import ops
-        if ops.patch_hip() and ops.patch_embed_supported(x, self.proj.weight, self.proj.bias):
+        patch, fp32_hip = ops.patch_hip(), ops.token_linear_fp32_hip()
+        if patch and (ops.patch_embed_supported(x, self.proj.weight, self.proj.bias)
+                      or (fp32_hip and ops.patch_embed_x3_supported(x, self.proj.weight, self.proj.bias))):
             return ops.patch_embed(x, self.proj.weight, self.proj.bias, pos_embed)
         x = self.proj(x).flatten(2).transpose(1, 2)
         return x if pos_embed is None else x + pos_embed

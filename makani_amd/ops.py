@@ -2674,12 +2674,215 @@ def _toklin_addend_fused(addend, x, O):
             and tuple(addend.shape) == tuple(x.shape[:-1]) + (O,))
 
 
+# ----------------------------------------------------------------------------
+# the same linears on fp32 rows outside autocast (csrc/x3_toklinear.hip): fp32-accurate on the bf16x3 engine
+# ----------------------------------------------------------------------------
+# Opt-in by the rule of DESIGN section 19 until every row of tools/toklinear_fp32_bench.py has been measured faster than the
+# torch path.
+TOKEN_LINEAR_FP32_DEFAULT = "torch"
+
+
+def token_linear_fp32_hip():
+    """``MK_TOKEN_LINEAR_FP32=hip|torch`` (read at call time): fp32 token-major linears outside autocast on the
+    ``mk_token_linear_x3_*`` kernels, or ``F.linear``.  Independent of ``MK_TOKEN_LINEAR``."""
+    return _hip_or_torch("MK_TOKEN_LINEAR_FP32", TOKEN_LINEAR_FP32_DEFAULT)
+
+
+def token_linear_x3_info():
+    """The tile of the kernels (no device needed): ``tr`` rows, ``tc`` columns, ``tk`` contraction step."""
+    t = (ctypes.c_int * 3)()
+    _lib.check(_lib.load().mk_token_linear_x3_info(ctypes.addressof(t)), "mk_token_linear_x3_info")
+    return dict(zip(("tr", "tc", "tk"), t))
+
+
+def _toklin_x3_rows(t):
+    """``t`` ``[..., L]`` fp32 as the x3 kernels take it, and its row stride: itself where its layout fits, else a contiguous copy."""
+    ld = _row_stride(t)
+    if ld is None or ld % 4 or ld < t.shape[-1] or t.data_ptr() % 16:
+        return t.contiguous(), t.shape[-1]
+    return t, ld
+
+
+def _toklin_x3_param_ok(p, shape, device):
+    return torch.is_tensor(p) and p.device == device and p.dtype == torch.float32 and tuple(p.shape) == shape
+
+
+def token_linear_x3_supported(x, weight, bias=None):
+    """True for what the ``mk_token_linear_x3_*`` kernels take as it is: ``x`` ``[..., I]`` fp32 on the device with bf16 device
+    autocast NOT active, its last axis contiguous, its rows at one common stride that is a multiple of 4 and at least ``I``,
+    16-byte aligned; ``I`` and ``O`` multiples of 4; ``weight`` ``[O, I]`` and ``bias`` ``[O]`` (or None) fp32 on the same device;
+    and the engine selected (``MK_SPECTRAL_GEMM=bf16x3``, the default: with ``f32`` the torch path is taken)."""
+    if SPECTRAL_GEMM != "bf16x3":
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.numel() > 0 and x.dtype == torch.float32
+            and torch.is_tensor(weight) and weight.dim() == 2):
+        return False
+    O, I = weight.shape
+    if x.shape[-1] != I or I % 4 or O % 4 or I < 4 or O < 4:
+        return False
+    if _autocast_dtype() == torch.bfloat16:
+        return False
+    if not _toklin_x3_param_ok(weight, (O, I), x.device) or (bias is not None and not _toklin_x3_param_ok(bias, (O,), x.device)):
+        return False
+    ld = _row_stride(x)
+    return ld is not None and ld % 4 == 0 and ld >= I and x.data_ptr() % 16 == 0
+
+
+def _toklin_x3_weight(weight):
+    """The weight as the kernels read it (no image is packed): itself, or a contiguous copy of a strided or misaligned one."""
+    w = weight.detach()
+    return w if (w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0) else w.contiguous()
+
+
+def token_linear_x3_fwd_raw(x, x_ld, w, bias, R, O, I, kmajor=False, y=None, pre=None, addend=None, addend_ld=0, aux=None, aux_ld=0,
+                            gelu=False):
+    """One launch of ``mk_token_linear_x3_fwd`` into the contiguous fp32 ``y`` ``[R, O]``: ``x`` ``R`` rows of ``I`` at stride
+    ``x_ld``; ``w`` ``[O, I]``, or with ``kmajor`` ``[I, O]`` (the data gradient from the stored weight)."""
+    _lib.check(_lib.load().mk_token_linear_x3_fwd(x.data_ptr(), x_ld, w.data_ptr(), w.stride(0), int(bool(kmajor)), _ptr(bias),
+                                                  y.data_ptr(), O, *_pl(pre, O), *_pl(addend, addend_ld), *_pl(aux, aux_ld),
+                                                  int(bool(gelu)), R, O, I, _stream()), "mk_token_linear_x3_fwd")
+    return y
+
+
+def token_linear_x3_wgrad_raw(dy, dy_ld, x, x_ld, R, O, I, want_db, slabs=0):
+    """``dW`` fp32 ``[O, I]`` and ``db`` fp32 ``[O]`` (None unless ``want_db``) from fp32 ``dy`` ``[R, O]`` and ``x`` ``[R, I]``."""
+    lib = _lib.load()
+    dw = torch.empty(O, I, dtype=torch.float32, device=x.device)
+    db = torch.empty(O, dtype=torch.float32, device=x.device) if want_db else None
+    nbytes = lib.mk_token_linear_x3_wgrad_workspace(R, O, I, slabs)
+    if nbytes < 0:
+        raise RuntimeError(f"makani_amd mk_token_linear_x3_wgrad: sizes R = {R}, O = {O}, I = {I}, slabs = {slabs} are refused")
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    _lib.check(lib.mk_token_linear_x3_wgrad(dy.data_ptr(), dy_ld, x.data_ptr(), x_ld, dw.data_ptr(), I, _ptr(db), ws.data_ptr(), R, O, I,
+                                            slabs, _stream()), "mk_token_linear_x3_wgrad")
+    return dw, db
+
+
+def _toklin_x3_grad_rows(g, O):
+    g = g.reshape(-1, O)
+    return _toklin_x3_rows(g if g.dtype == torch.float32 else g.float())
+
+
+class _TokenLinearX3(torch.autograd.Function):
+    """``y = x W^T + b`` on fp32 rows, optionally through the exact GELU or added to an fp32 ``addend``: one GEMM on the bf16x3
+    engine.  Saves ``x``, the weight itself and, with ``gelu``, the pre-activation.  Backward: ``g gelu'(pre)`` first with
+    ``gelu``, the k-major GEMM on the stored weight for ``dx``, the slab kernel for ``dW`` and ``db``.  All fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gelu, addend):
+        O, I = weight.shape
+        shape = x.shape[:-1] + (O,)
+        xr, x_ld = _toklin_x3_rows(x)
+        R = x.numel() // I
+        w = _toklin_x3_weight(weight)
+        bf = None if bias is None else bias.detach().contiguous()
+        need = any(ctx.needs_input_grad[:3])
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        pre = None
+        if addend is not None:
+            ar, a_ld = _toklin_x3_rows(addend.detach().reshape(-1, O))
+            token_linear_x3_fwd_raw(xr, x_ld, w, bf, R, O, I, y=out, addend=ar, addend_ld=a_ld)
+        else:
+            pre = torch.empty(R, O, dtype=torch.float32, device=x.device) if (gelu and need) else None
+            token_linear_x3_fwd_raw(xr, x_ld, w, bf, R, O, I, y=out, pre=pre, gelu=gelu)
+        if need:
+            ctx.save_for_backward(xr, w, pre)
+        ctx.cfg = (x_ld, R, tuple(x.shape), bias is not None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.saved_tensors:               # only the addend asks for a gradient: the incoming one
+            return None, None, None, None, g
+        xr, w, pre = ctx.saved_tensors
+        x_ld, R, x_shape, has_bias = ctx.cfg
+        O, I = w.shape
+        g_in = g
+        g, g_ld = _toklin_x3_grad_rows(g, O)
+        if pre is not None:                     # through the GELU: g gelu'(pre), one pointwise pass (mk_bias_gelu_bwd)
+            gc = g if g_ld == O else g.contiguous()
+            g, g_ld = gelu_backward(pre.view(1, 1, R * O), gc.view(1, 1, R * O))[0].view(R, O), O
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(x_shape, dtype=torch.float32, device=g.device)
+            token_linear_x3_fwd_raw(g, g_ld, w, None, R, I, O, kmajor=True, y=dx)
+        want_db = has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_db:
+            dw, db = token_linear_x3_wgrad_raw(g, g_ld, xr, x_ld, R, O, I, want_db)
+            dw = dw if ctx.needs_input_grad[1] else None
+        return dx, dw, db, None, (g_in if ctx.needs_input_grad[4] else None)
+
+
+class _TokenMLPX3(torch.autograd.Function):
+    """``fc2(gelu(fc1(x)))`` (+ an fp32 ``addend``) on fp32 rows: two GEMMs on the bf16x3 engine, ``fc1``'s with the GELU epilogue
+    (and ``pre`` stored in grad mode only), ``fc2``'s with the addend.  Saves ``x``, the two weights themselves, ``pre`` and
+    ``act``.  Backward, in the order of ``_TokenMLP``: ``fc2``'s weight gradient on ``act``; ``fc2``'s data gradient from the
+    stored weight with the GELU' epilogue on ``pre``, which is ``dpre``; ``fc1``'s weight gradient and data gradient from ``dpre``;
+    the addend's gradient is the incoming gradient.  All fp32."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, addend):
+        H, I = w1.shape
+        O = w2.shape[0]
+        shape = x.shape[:-1] + (O,)
+        xr, x_ld = _toklin_x3_rows(x)
+        R = x.numel() // I
+        w1c, w2c = _toklin_x3_weight(w1), _toklin_x3_weight(w2)
+        b1c = None if b1 is None else b1.detach().contiguous()
+        b2c = None if b2 is None else b2.detach().contiguous()
+        need = any(ctx.needs_input_grad[:5])
+        act = torch.empty(R, H, dtype=torch.float32, device=x.device)
+        pre = torch.empty(R, H, dtype=torch.float32, device=x.device) if need else None
+        token_linear_x3_fwd_raw(xr, x_ld, w1c, b1c, R, H, I, y=act, pre=pre, gelu=True)
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        if addend is not None:
+            ar, a_ld = _toklin_x3_rows(addend.detach().reshape(-1, O))
+            token_linear_x3_fwd_raw(act, H, w2c, b2c, R, O, H, y=out, addend=ar, addend_ld=a_ld)
+        else:
+            token_linear_x3_fwd_raw(act, H, w2c, b2c, R, O, H, y=out)
+        if need:
+            ctx.save_for_backward(xr, w1c, w2c, pre, act)
+        ctx.cfg = (x_ld, R, tuple(x.shape), b1 is not None, b2 is not None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.saved_tensors:               # only the addend asks for a gradient: the incoming one
+            return None, None, None, None, None, g
+        xr, w1, w2, pre, act = ctx.saved_tensors
+        x_ld, R, x_shape, has_b1, has_b2 = ctx.cfg
+        H, I = w1.shape
+        O = w2.shape[0]
+        need = ctx.needs_input_grad
+        g_in = g
+        g, g_ld = _toklin_x3_grad_rows(g, O)
+        dw2 = db2 = dw1 = db1 = dx = None
+        if need[3] or (has_b2 and need[4]):
+            dw2, db2 = token_linear_x3_wgrad_raw(g, g_ld, act, H, R, O, H, has_b2 and need[4])
+            dw2 = dw2 if need[3] else None
+        if need[0] or need[1] or (has_b1 and need[2]):
+            dpre = torch.empty(R, H, dtype=torch.float32, device=g.device)
+            token_linear_x3_fwd_raw(g, g_ld, w2, None, R, H, O, kmajor=True, y=dpre, aux=pre, aux_ld=H)
+            if need[1] or (has_b1 and need[2]):
+                dw1, db1 = token_linear_x3_wgrad_raw(dpre, H, xr, x_ld, R, H, I, has_b1 and need[2])
+                dw1 = dw1 if need[1] else None
+            if need[0]:
+                dx = torch.empty(x_shape, dtype=torch.float32, device=g.device)
+                token_linear_x3_fwd_raw(dpre, H, w1, None, R, I, H, kmajor=True, y=dx)
+        return dx, dw1, db1, dw2, db2, (g_in if need[5] else None)
+
+
 def token_linear(x, weight, bias=None, gelu=False, addend=None):
     """``F.linear(x, weight, bias)`` over any leading axes -- ``F.gelu`` of it with ``gelu``, ``addend +`` it with ``addend`` (not
     both) -- as one autograd function on the ``mk_token_linear_*`` kernels: bf16 result, or the fp32 sum with an fp32 ``addend``.
-    What ``token_linear_supported`` declines, CPU tensors and ``MK_TOKEN_LINEAR=torch`` take ``F.linear`` / ``F.gelu``."""
+    fp32 rows outside bf16 autocast take, under ``MK_TOKEN_LINEAR_FP32=hip`` and for what ``token_linear_x3_supported`` accepts, the
+    same node on the ``mk_token_linear_x3_*`` kernels (fp32 results).  What both decline, CPU tensors and the knobs at ``torch``
+    take ``F.linear`` / ``F.gelu``."""
     if gelu and addend is not None:
         raise ValueError("token_linear: gelu and addend cannot be combined")
+    fp32_hip = token_linear_fp32_hip()
     if token_linear_hip() and token_linear_supported(x, weight, bias):
         xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
         if addend is None:
@@ -2687,6 +2890,14 @@ def token_linear(x, weight, bias=None, gelu=False, addend=None):
         if _toklin_addend_fused(addend, x, weight.shape[0]):
             return _TokenLinear.apply(xb, weight, bias, False, addend)
         return addend + _TokenLinear.apply(xb, weight, bias, False, None)
+    if fp32_hip and token_linear_x3_supported(x, weight, bias):
+        if addend is None:
+            if gelu and (x.numel() // x.shape[-1] * weight.shape[0]) % 8:      # the GELU-gradient pass takes whole 8-element groups
+                return torch.nn.functional.gelu(_TokenLinearX3.apply(x, weight, bias, False, None))
+            return _TokenLinearX3.apply(x, weight, bias, bool(gelu), None)
+        if _toklin_addend_fused(addend, x, weight.shape[0]):
+            return _TokenLinearX3.apply(x, weight, bias, False, addend)
+        return addend + _TokenLinearX3.apply(x, weight, bias, False, None)
     y = torch.nn.functional.linear(x, weight, bias)
     if gelu:
         y = torch.nn.functional.gelu(y)
@@ -2696,7 +2907,8 @@ def token_linear(x, weight, bias=None, gelu=False, addend=None):
 def token_mlp(x, w1, b1, w2, b2, addend=None):
     """``F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)`` (``addend +`` it with ``addend``) as one autograd function on the
     ``mk_token_linear_*`` kernels, with the GELU in ``fc1``'s epilogue, the addend in ``fc2``'s and the GELU gradient in the
-    epilogue of ``fc2``'s data gradient.  Same dispatch as ``token_linear``."""
+    epilogue of ``fc2``'s data gradient.  Same dispatch as ``token_linear``: the bf16 branch, then the fp32 one, then torch."""
+    fp32_hip = token_linear_fp32_hip()
     if (token_linear_hip() and token_linear_supported(x, w1, b1) and torch.is_tensor(w2) and w2.dim() == 2
             and w2.shape[1] == w1.shape[0] and w2.shape[0] % 8 == 0 and _toklin_param_ok(w2, tuple(w2.shape), x.device)
             and (b2 is None or _toklin_param_ok(b2, (w2.shape[0],), x.device))):
@@ -2704,6 +2916,12 @@ def token_mlp(x, w1, b1, w2, b2, addend=None):
         if addend is None or _toklin_addend_fused(addend, x, w2.shape[0]):
             return _TokenMLP.apply(xb, w1, b1, w2, b2, addend)
         return addend + _TokenMLP.apply(xb, w1, b1, w2, b2, None)
+    if (fp32_hip and token_linear_x3_supported(x, w1, b1) and torch.is_tensor(w2) and w2.dim() == 2
+            and w2.shape[1] == w1.shape[0] and w2.shape[0] % 4 == 0 and _toklin_x3_param_ok(w2, tuple(w2.shape), x.device)
+            and (b2 is None or _toklin_x3_param_ok(b2, (w2.shape[0],), x.device))):
+        if addend is None or _toklin_addend_fused(addend, x, w2.shape[0]):
+            return _TokenMLPX3.apply(x, w1, b1, w2, b2, addend)
+        return addend + _TokenMLPX3.apply(x, w1, b1, w2, b2, None)
     F = torch.nn.functional
     y = F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
     return y if addend is None else addend + y
@@ -2925,17 +3143,95 @@ def _patch_pos_fused(pos, img, N, E):
             and tuple(pos.shape) in ((1, N, E), (N, E)))
 
 
+def patch_embed_x3_supported(img, weight, bias=None):
+    """True for what ``_PatchEmbedX3`` takes: ``img`` ``[B, C, H, W]`` fp32 on the device with bf16 device autocast NOT active,
+    ``weight`` ``[E, C, p0, p1]`` with a patch that divides the grid, ``C p0 p1`` and ``E`` multiples of 4, ``weight`` and ``bias``
+    ``[E]`` (or None) fp32 on the same device, and the bf16x3 engine selected (``MK_SPECTRAL_GEMM``)."""
+    if SPECTRAL_GEMM != "bf16x3":
+        return False
+    if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.numel() > 0 and img.dtype == torch.float32
+            and torch.is_tensor(weight) and weight.dim() == 4):
+        return False
+    E, C, p0, p1 = weight.shape
+    F = C * p0 * p1
+    if img.shape[1] != C or img.shape[2] % p0 or img.shape[3] % p1 or F % 4 or E % 4:
+        return False
+    if _autocast_dtype() == torch.bfloat16:
+        return False
+    return _toklin_x3_param_ok(weight, (E, C, p0, p1), img.device) and (bias is None or _toklin_x3_param_ok(bias, (E,), img.device))
+
+
+class _PatchEmbedX3(torch.autograd.Function):
+    """``_PatchEmbed`` on fp32 images outside autocast: ``mk_patchify`` (order 0) to fp32 rows, then ``mk_token_linear_x3_fwd`` on
+    the weight's ``[E, F]`` view with the bias; with ``pos`` (fp32 ``[N, E]``) one GEMM launch per sample with ``pos`` as its
+    addend.  Saves the patch rows and the weight view.  Backward: the x3 slab kernel for ``dW`` / ``db``; the batch sum of the
+    gradient for ``pos``; for the image, where it asks, the k-major GEMM on the stored weight and ``mk_unpatchify``.  All fp32."""
+
+    @staticmethod
+    def forward(ctx, img, weight, bias, pos):
+        B, C, H, W = img.shape
+        E, _, p0, p1 = weight.shape
+        _, _, hp, wp, F = _patch_geometry(C, H, W, (p0, p1))
+        N = hp * wp
+        rows = patchify_raw(img.detach().contiguous(), torch.empty(B * N, F, dtype=torch.float32, device=img.device), (p0, p1), 0)
+        w = _toklin_x3_weight(weight.detach().reshape(E, F))
+        bf = None if bias is None else bias.detach().contiguous()
+        out = torch.empty(B, N, E, dtype=torch.float32, device=img.device)
+        if pos is not None:
+            pr, p_ld = _toklin_x3_rows(pos.detach().reshape(N, E))
+            for b in range(B):
+                token_linear_x3_fwd_raw(rows[b * N:(b + 1) * N], F, w, bf, N, E, F, y=out[b], addend=pr, addend_ld=p_ld)
+        else:
+            token_linear_x3_fwd_raw(rows, F, w, bf, B * N, E, F, y=out)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(rows, w)
+        ctx.cfg = (tuple(img.shape), tuple(weight.shape), bias is not None, None if pos is None else tuple(pos.shape))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        img_shape, w_shape, has_bias, pos_shape = ctx.cfg
+        need = ctx.needs_input_grad
+        dpos = g.sum(0).reshape(pos_shape) if (pos_shape is not None and need[3]) else None
+        if not ctx.saved_tensors:
+            return None, None, None, dpos
+        rows, w = ctx.saved_tensors
+        E, F = w.shape
+        R = rows.shape[0]
+        gr, g_ld = _toklin_x3_grad_rows(g, E)
+        dx = dw = db = None
+        want_db = has_bias and need[2]
+        if need[1] or want_db:
+            dw, db = token_linear_x3_wgrad_raw(gr, g_ld, rows, F, R, E, F, want_db)
+            dw = dw.view(w_shape) if need[1] else None
+        if need[0]:
+            dxr = torch.empty(R, F, dtype=torch.float32, device=g.device)
+            token_linear_x3_fwd_raw(gr, g_ld, w, None, R, F, E, kmajor=True, y=dxr)
+            dx = unpatchify_raw(dxr, torch.empty(img_shape, dtype=torch.float32, device=g.device), w_shape[2:], 0)
+        return dx, dw, db, dpos
+
+
 def patch_embed(img, weight, bias=None, pos=None):
     """``F.conv2d(img, weight, bias, stride=patch).flatten(2).transpose(1, 2)`` (``+ pos``): ``[B, C, H, W]`` -> ``[B, N, E]`` for
     ``weight`` ``[E, C, p0, p1]``.  Under ``MK_PATCH=hip``, for what ``patch_embed_supported`` takes, one autograd function on
     ``mk_patchify`` and the ``mk_token_linear_*`` kernels: a bf16 result, or with an fp32 ``pos`` (``[1, N, E]`` or ``[N, E]``) the
     fp32 sum ``pos + float(bf16(conv))`` from the GEMM's epilogue -- the rounding points of the torch expression under bf16
-    autocast.  Everything else takes the torch expression."""
-    if patch_hip() and patch_embed_supported(img, weight, bias):
+    autocast.  An fp32 image outside autocast, under ``MK_PATCH=hip`` AND ``MK_TOKEN_LINEAR_FP32=hip`` and for what
+    ``patch_embed_x3_supported`` takes, is the same node on fp32 rows and the ``mk_token_linear_x3_*`` kernels: an fp32 result.
+    Everything else takes the torch expression."""
+    patch, fp32_hip = patch_hip(), token_linear_fp32_hip()
+    if patch and patch_embed_supported(img, weight, bias):
         E, _, p0, p1 = weight.shape
         N = (img.shape[2] // p0) * (img.shape[3] // p1)
         if pos is None or _patch_pos_fused(pos, img, N, E):
             return _PatchEmbed.apply(img, weight, bias, pos)
         return _PatchEmbed.apply(img, weight, bias, None) + pos
+    if patch and fp32_hip and patch_embed_x3_supported(img, weight, bias):
+        E, _, p0, p1 = weight.shape
+        N = (img.shape[2] // p0) * (img.shape[3] // p1)
+        if pos is None or _patch_pos_fused(pos, img, N, E):
+            return _PatchEmbedX3.apply(img, weight, bias, pos)
+        return _PatchEmbedX3.apply(img, weight, bias, None) + pos
     y = torch.nn.functional.conv2d(img, weight, bias, stride=tuple(weight.shape[2:])).flatten(2).transpose(1, 2)
     return y if pos is None else y + pos
