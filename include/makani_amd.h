@@ -642,6 +642,33 @@ int mk_attn_bwd_dkv(const void* q, const void* k, const void* v, const void* dO,
 int mk_attn_bwd_dq(const void* q, const void* k, const void* v, const void* dO, const float* lse, const float* delta, void* dq,
                    int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream);
 
+/* ---- the same attention with fp32 operands on the bf16x3 arithmetic (csrc/x3_attn.hip): F.scaled_dot_product_attention of the
+ * ViT attention module (makani/models/networks/vit.py:44-55) when the model runs in plain fp32 (amp_mode none).  fp32 q, k, v,
+ * dO in, fp32 o, lse, delta, dq, dk, dv out; the formulas and the argument shape of mk_attn_*: a base pointer (16-byte aligned)
+ * and three element strides (batch, head, token) per tensor, each a non-negative multiple of 4, the token stride at least D, the D
+ * axis contiguous; `strides` in the order of the pointer arguments, read on the host during the call.  q, k, v may be the three
+ * views of one fp32 [B][N][3][H][D] projection output, o a [B][N][H D] buffer, dq, dk, dv the views of one [B][N][3][H][D] gradient.
+ * D a multiple of 16 in 16 ... 64 (zero-padded on chip to 64; a padded element is never read or written); any Nq, Nk >= 1,
+ * independent.  lse, delta [B][H][Nq] fp32 contiguous; mk_attn_x3_fwd takes lse == NULL (nothing stored).
+ * Every operand of the two forward and the five backward matrix products is split exactly into three bf16 pieces by truncation
+ * (x = h + m + l) and a product is the six piece products of weight >= 2^-16 on v_mfma_f32_32x32x16_bf16, accumulated in fp32;
+ * P and dS = P o (dO V^T - delta) are fp32 and are split in registers before their second products; scores, online softmax, row
+ * sums, lse and delta = rowsum(dO o O) (from the stored fp32 o) are fp32.
+ * One workgroup per (batch, head, tile of 128 queries) in fwd and dq, per (batch, head, tile of 128 keys) in dkv; nothing is
+ * summed across workgroups: no atomics, no waiting on another workgroup, the same inputs give the same bits.  Each call is
+ * one launch on `stream`, allocates nothing, does not synchronise and can be captured.  Unsupported D, strides, alignment or
+ * sizes past the 32-bit row range return code 1 before any launch.
+ * mk_attn_x3_info (no device needed): tiles[6] = (query tile, key tile) of fwd, of dkv and of dq for head size D. */
+int mk_attn_x3_info(int D, int* tiles);
+int mk_attn_x3_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int H, int Nq, int Nk, int D,
+                   const long long* strides, float scale, void* stream);
+int mk_attn_x3_bwd_delta(const float* o, const float* dO, float* delta, int B, int H, int Nq, int D, const long long* strides,
+                         void* stream);
+int mk_attn_x3_bwd_dkv(const float* q, const float* k, const float* v, const float* dO, const float* lse, const float* delta,
+                       float* dk, float* dv, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream);
+int mk_attn_x3_bwd_dq(const float* q, const float* k, const float* v, const float* dO, const float* lse, const float* delta,
+                      float* dq, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream);
+
 /* ---- layer norm over the TRAILING axis with the residual add fused in (csrc/toknorm.hip): nn.LayerNorm of the ViT blocks
  * (makani/models/networks/vit.py:86-118) and nn.LayerNorm((h, w)) of AFNO (afnonet.py:249-250).  `rows` rows of L >= 1
  * contiguous elements; every tensor has its own dtype (0 = fp32, 1 = bf16) and element row stride ld >= L.  Per row

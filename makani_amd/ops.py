@@ -2227,6 +2227,142 @@ def _attn_scale(scale, D):
     return float(scale) if scale is not None else 1.0 / math.sqrt(D)
 
 
+# ----------------------------------------------------------------------------
+# the same attention on fp32 operands outside autocast (csrc/x3_attn.hip): fp32-accurate on the bf16x3 arithmetic
+# ----------------------------------------------------------------------------
+# Opt-in by the rule of DESIGN section 19 (DESIGN section 31 has the rows of tools/attn_fp32_bench.py).
+ATTN_FP32_DEFAULT = "torch"
+ATTN_X3_MAX_HEAD = 64
+
+
+def attn_fp32_hip():
+    """``MK_ATTN_FP32=hip|torch`` (read at call time): fp32 attention outside autocast on the ``mk_attn_x3_*`` kernels, or
+    ``F.scaled_dot_product_attention``.  Independent of ``MK_ATTN``."""
+    return _hip_or_torch("MK_ATTN_FP32", ATTN_FP32_DEFAULT)
+
+
+def attn_x3_info(head_dim):
+    """(query tile, key tile) of the fp32 forward, dK / dV and dQ kernels at this head size: three pairs (no device needed)."""
+    t = (ctypes.c_int * 6)()
+    _lib.check(_lib.load().mk_attn_x3_info(int(head_dim), ctypes.addressof(t)), "mk_attn_x3_info")
+    return (t[0], t[1]), (t[2], t[3]), (t[4], t[5])
+
+
+def _attn_x3_operand_ok(t):
+    if t.dim() != 4 or not t.is_cuda or t.dtype != torch.float32 or t.stride(3) != 1 or t.data_ptr() % 16:
+        return False
+    sb, sh, sn = _attn_strides(t)
+    return min(sb, sh) >= 0 and sb % 4 == 0 and sh % 4 == 0 and sn % 4 == 0 and sn >= t.shape[3]
+
+
+def attention_x3_supported(q, k, v):
+    """True when the ``mk_attn_x3_*`` kernels take these ``[B, H, N, D]`` views as they are: fp32 on the device with device
+    autocast NOT active, the engine selected (``MK_SPECTRAL_GEMM=bf16x3``, as ``token_linear_x3_supported`` requires), D a
+    multiple of 16 in 16 ... 64 and contiguous, 16-byte aligned, batch / head / token strides multiples of 4 elements."""
+    if SPECTRAL_GEMM != "bf16x3":
+        return False
+    if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)):
+        return False
+    if not (k.shape == v.shape and q.shape[:2] == k.shape[:2] and q.shape[3] == k.shape[3]):
+        return False
+    D = q.shape[3]
+    if D % 16 or not 16 <= D <= ATTN_X3_MAX_HEAD or min(q.shape[2], k.shape[2], q.shape[0], q.shape[1]) < 1:
+        return False
+    if not all(_attn_x3_operand_ok(t) for t in (q, k, v)):
+        return False
+    return _autocast_dtype() is None
+
+
+def attn_x3_fwd_raw(q, k, v, o, lse, scale):
+    """``attn_fwd_raw`` on fp32 views."""
+    B, H, Nq, D = q.shape
+    st = _attn_stride_array(q, k, v, o)
+    _lib.check(_lib.load().mk_attn_x3_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _ptr(lse), B, H, Nq, k.shape[2], D,
+                                          ctypes.addressof(st), float(scale), _stream()), "mk_attn_x3_fwd")
+
+
+def attn_x3_bwd_raw(q, k, v, o, go, lse, dq, dk, dv, scale):
+    """``attn_bwd_raw`` on fp32 views: delta, then dK / dV, then dQ."""
+    B, H, Nq, D = q.shape
+    Nk = k.shape[2]
+    lib = _lib.load()
+    delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
+    st = _attn_stride_array(o, go)
+    _lib.check(lib.mk_attn_x3_bwd_delta(o.data_ptr(), go.data_ptr(), delta.data_ptr(), B, H, Nq, D, ctypes.addressof(st), _stream()),
+               "mk_attn_x3_bwd_delta")
+    st = _attn_stride_array(q, k, v, go, dk, dv)
+    _lib.check(lib.mk_attn_x3_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                      dk.data_ptr(), dv.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()),
+               "mk_attn_x3_bwd_dkv")
+    st = _attn_stride_array(q, k, v, go, dq)
+    _lib.check(lib.mk_attn_x3_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                     dq.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()), "mk_attn_x3_bwd_dq")
+
+
+def _attn_x3_grad_out(go):
+    return go if _attn_x3_operand_ok(go) else go.contiguous()
+
+
+class _AttentionX3(torch.autograd.Function):
+    """``_Attention`` on fp32 views and the ``mk_attn_x3_*`` kernels: the same saved set, the same permuted-view outputs."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale):
+        B, H, Nq, D = q.shape
+        o = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        need = any(ctx.needs_input_grad[:3])
+        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if need else None
+        attn_x3_fwd_raw(q, k, v, o, lse, scale)
+        if need:
+            ctx.save_for_backward(q, k, v, o, lse)
+            ctx.scale = scale
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        q, k, v, o, lse = ctx.saved_tensors
+        B, H, Nq, D = q.shape
+        Nk = k.shape[2]
+        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+        attn_x3_bwd_raw(q, k, v, o, _attn_x3_grad_out(go), lse, dq, dk, dv, ctx.scale)
+        return dq, dk, dv, None
+
+
+class _AttentionPackedX3(torch.autograd.Function):
+    """``_AttentionPacked`` on an fp32 projection output ``[B, N, 3 H D]``: one gradient tensor, written in place."""
+
+    @staticmethod
+    def forward(ctx, qkv, H, scale):
+        B, N, C3 = qkv.shape
+        D = C3 // (3 * H)
+        q, k, v = _qkv_views(qkv, B, N, H, D)
+        o = torch.empty(B, N, H * D, dtype=qkv.dtype, device=qkv.device)
+        need = ctx.needs_input_grad[0]
+        lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device) if need else None
+        attn_x3_fwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), lse, scale)
+        if need:
+            ctx.save_for_backward(qkv, o, lse)
+            ctx.args = (H, scale)
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        qkv, o, lse = ctx.saved_tensors
+        H, scale = ctx.args
+        B, N, C3 = qkv.shape
+        D = C3 // (3 * H)
+        q, k, v = _qkv_views(qkv, B, N, H, D)
+        dqkv = torch.empty(B, N, C3, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = _qkv_views(dqkv, B, N, H, D)
+        go = _attn_x3_grad_out(go.reshape(B, N, H, D).permute(0, 2, 1, 3))
+        attn_x3_bwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), go, lse, dq, dk, dv, scale)
+        return dqkv, None, None
+
+
 def _attn_autocast(*tensors):
     """Under device autocast ``F.scaled_dot_product_attention`` takes its operands in the autocast dtype; so do these ops (the
     fp32 output of a ``qk_norm`` LayerNorm reaches the product as bf16 either way)."""
@@ -2236,12 +2372,15 @@ def _attn_autocast(*tensors):
 
 def attention(q, k, v, scale=None, dropout_p=0.0):
     """``F.scaled_dot_product_attention(q, k, v)`` (no mask, not causal) for ``[B, H, N, D]`` views; returns ``[B, H, Nq, D]``.
-    bf16 device tensors that ``attention_supported`` accepts run on the ``mk_attn_*`` kernels under ``MK_ATTN=hip``; fp32 / fp16
-    inputs, CPU tensors, other head sizes or strides, ``dropout_p > 0`` and ``MK_ATTN=torch`` take the torch formulation."""
-    hip = attn_hip()
+    bf16 device tensors that ``attention_supported`` accepts run on the ``mk_attn_*`` kernels under ``MK_ATTN=hip``; fp32 device
+    tensors outside autocast that ``attention_x3_supported`` accepts run on the ``mk_attn_x3_*`` kernels under ``MK_ATTN_FP32=hip``;
+    fp16 inputs, CPU tensors, other head sizes or strides, ``dropout_p > 0`` and the knobs at ``torch`` take the torch formulation."""
+    hip, fp32_hip = attn_hip(), attn_fp32_hip()
     q, k, v = _attn_autocast(q, k, v)
     if hip and dropout_p == 0.0 and attention_supported(q, k, v):
         return _Attention.apply(q, k, v, _attn_scale(scale, q.shape[-1]))
+    if fp32_hip and dropout_p == 0.0 and attention_x3_supported(q, k, v):
+        return _AttentionX3.apply(q, k, v, _attn_scale(scale, q.shape[-1]))
     return torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
 
 
@@ -2253,12 +2392,16 @@ def attention_packed(qkv, num_heads, scale=None, dropout_p=0.0):
     B, N, C3 = qkv.shape
     H = int(num_heads)
     D = C3 // (3 * H)
-    hip = attn_hip()
+    hip, fp32_hip = attn_hip(), attn_fp32_hip()
     (qkv,) = _attn_autocast(qkv)
     if hip and dropout_p == 0.0 and qkv.is_cuda and qkv.dtype == torch.bfloat16:
         x = qkv if (qkv.stride(2) == 1 and qkv.data_ptr() % 16 == 0) else qkv.contiguous()
         if attention_supported(*_qkv_views(x.detach(), B, N, H, D)):
             return _AttentionPacked.apply(x, H, _attn_scale(scale, D))
+    if fp32_hip and dropout_p == 0.0 and qkv.is_cuda and qkv.dtype == torch.float32:
+        x = qkv if (qkv.stride(2) == 1 and qkv.data_ptr() % 16 == 0) else qkv.contiguous()
+        if attention_x3_supported(*_qkv_views(x.detach(), B, N, H, D)):
+            return _AttentionPackedX3.apply(x, H, _attn_scale(scale, D))
     q, k, v = (t.permute(0, 2, 1, 3) for t in qkv.reshape(B, N, 3, H, D).unbind(2))
     o = torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
     return o.transpose(1, 2).reshape(B, N, H * D)

@@ -8,8 +8,13 @@ The attention product -- at the 18 540 tokens of ``config/vit.yaml`` nearly all 
   writes the output token-major ``[B, N, H D]`` and returns one gradient tensor for the projection: no permuted copy, no cat;
 * ``qk_norm`` on: ``ops.attention`` on the normalised ``[B, H, N, D]`` views.
 
-fp32 / fp16 activations (no bf16 autocast), CPU tensors, head sizes that are no multiple of 16 in 16 ... 128, attention dropout in
-training and ``MK_ATTN=torch`` take ``F.scaled_dot_product_attention``, the reference's call.
+fp32 activations without autocast (the reference's ``amp_mode none``) reach, through the same two functions, the ``mk_attn_x3_*``
+kernels (csrc/x3_attn.hip) under ``MK_ATTN_FP32=hip`` (read and validated on every call; default ``ops.ATTN_FP32_DEFAULT``): fp32
+operands, output and lse, every matrix product on the bf16x3 arithmetic of the spectral engine, head sizes that are multiples of
+16 up to 64, and ``MK_SPECTRAL_GEMM=bf16x3``.
+
+fp16 activations, fp32 ones with ``MK_ATTN_FP32=torch``, CPU tensors, head sizes that are no multiple of 16 in 16 ... 128 (bf16) or
+16 ... 64 (fp32), attention dropout in training and ``MK_ATTN=torch`` take ``F.scaled_dot_product_attention``, the reference's call.
 
 The norms of the blocks (``norm1``, ``norm2``) and the final ``norm`` are ``layers.LayerNorm``: under ``MK_TOKEN_NORM=hip`` (read
 and validated on every call; default ``ops.TOKEN_NORM_DEFAULT``) they run on the ``mk_token_layernorm_*`` kernels
@@ -53,7 +58,9 @@ def _matmul_parallel(comm_inp_name, comm_hidden_name):
 
 
 class Attention(nn.Module):
-    """vit.py:14-55: multi-head self-attention on ``[B, N, C]`` tokens; ``qkv`` and ``proj`` are ``layers.Linear``."""
+    """vit.py:14-55: multi-head self-attention on ``[B, N, C]`` tokens; ``qkv`` and ``proj`` are ``layers.Linear``.  The product is
+    ``ops.attention_packed`` (``qk_norm`` off) or ``ops.attention`` (on): bf16 operands on the ``mk_attn_*`` kernels under
+    ``MK_ATTN=hip``, fp32 operands outside autocast on the ``mk_attn_x3_*`` kernels under ``MK_ATTN_FP32=hip``, else torch's call."""
 
     def __init__(self, dim, input_format="traditional", num_heads=8, qkv_bias=False, qk_norm=False, attn_drop_rate=0.0,
                  proj_drop_rate=0.0, norm_layer=nn.LayerNorm):
