@@ -21,12 +21,11 @@
 // rows + 2 elements.  Head sizes are zero-padded in LDS and registers to DP = 64 (D <= 64) or 128: a padded d is never
 // read from or written to memory.  A ragged last key tile is masked in the score; rows past the end load as zeros and
 // are not stored.
-#include "common.h"
+#include "attn_host.h"
 #include "mfma_tile.h"
 #include "../../include/makani_amd.h"
 
 #include <hip/hip_bf16.h>
-#include <cstdint>
 
 namespace {
 
@@ -39,17 +38,16 @@ using mk::mfma::read_row_frag;
 using mk::mfma::RowStage;
 using mk::mfma::tile_row;
 using mk::mfma::zero;
+using mk::attn::kLog2e;
+using mk::attn::kOwn;
 typedef __hip_bfloat16 bf16;
 
 constexpr int kT = 256;                 // 4 waves
-constexpr int kOwn = 128;               // tokens a workgroup owns (32 per wave)
 constexpr int kSweepK = 64;             // key tile of fwd and dq
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+constexpr float kLn2 = 0.6931471805599453f;
 
 constexpr int padded_d(int D) { return D <= 64 ? 64 : 128; }
 constexpr int dkv_sweep(int DP) { return 4096 / DP; }      // query tile of dkv: 64 (DP 64) or 32 (DP 128)
-
-struct Str { long long b, h, n; };      // element strides of batch, head, token; the D axis is contiguous
 
 // ---- staging of a [ROWS][D] tile through registers: the row-major image of RowStage, and the transposed one -------------------
 template <int ROWS, int DP>
@@ -110,15 +108,8 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[DP / 32], bf16* row,
         }
 }
 
-struct Params {
-    const bf16 *q, *k, *v, *dO;
-    bf16 *o, *dq, *dk, *dv;
-    float* lse_out;                 // fwd: may be null
-    const float *lse, *delta;       // bwd
-    int B, H, Nq, Nk, D, ntile;     // ntile: owned tiles per (batch, head)
-    Str sq, sk, sv, so, sdo, sdq, sdk, sdv;
-    float scale, c;                 // c = scale log2(e)
-};
+struct Params : mk::attn::ParamsOf<bf16> {};
+constexpr mk::attn::Family kFamily{128, 8};      // head sizes to 128; strides in units of 8 bf16
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 template <int DP>
@@ -370,35 +361,10 @@ __global__ __launch_bounds__(kT) void attn_bwd_dkv_kernel(Params p) {
     store_t<DP>(dk, p.dk + b * p.sdk.b + h * p.sdk.h + key * p.sdk.n, kv, p.D, fh, p.scale);
 }
 
-// ---- validation ------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-bool head_ok(int D) { return D >= 16 && D <= 128 && D % 16 == 0; }
-
-int check_sizes(const char* who, int B, int H, int Nq, int Nk, int D) {
-    MK_REQUIRE_AS(who, B >= 1 && H >= 1 && Nq >= 1 && Nk >= 1, "bad sizes");
-    MK_REQUIRE_AS(who, head_ok(D), "head size must be a multiple of 16 in 16 ... 128");
-    MK_REQUIRE_AS(who, (double)B * H * (Nq > Nk ? Nq : Nk) < 2147483647.0, "too many rows");
-    return 0;
-}
-// n tensors, each a base pointer and (batch, head, token) element strides: multiples of 8 elements, rows do not overlap
-int check_operands(const char* who, int n, const void* const* ptr, const long long* st, int D) {
-    MK_REQUIRE_AS(who, st != nullptr, "null strides");
-    for (int i = 0; i < n; ++i) {
-        MK_REQUIRE_AS(who, ptr[i] != nullptr, "null pointer");
-        MK_REQUIRE_AS(who, aligned16(ptr[i]), "operand not 16-byte aligned");
-        for (int j = 0; j < 3; ++j)
-            MK_REQUIRE_AS(who, st[3 * i + j] >= 0 && st[3 * i + j] % 8 == 0, "strides must be non-negative multiples of 8 elements");
-        MK_REQUIRE_AS(who, st[3 * i + 2] >= D, "token stride smaller than the head size");
-    }
-    return 0;
-}
-Str str_at(const long long* st, int i) { return Str{st[3 * i], st[3 * i + 1], st[3 * i + 2]}; }
-
 }  // namespace
 
 extern "C" int mk_attn_info(int D, int* tiles) {
-    MK_REQUIRE(head_ok(D), "head size must be a multiple of 16 in 16 ... 128");
+    if (int rc = mk::attn::check_head(__func__, kFamily, D)) return rc;
     MK_REQUIRE(tiles != nullptr, "null pointer");
     tiles[0] = kOwn, tiles[1] = kSweepK;                       // fwd: query tile, key tile
     tiles[2] = dkv_sweep(padded_d(D)), tiles[3] = kOwn;        // dkv
@@ -408,16 +374,11 @@ extern "C" int mk_attn_info(int D, int* tiles) {
 
 extern "C" int mk_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int H, int Nq, int Nk, int D,
                            const long long* strides, float scale, void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, Nk, D)) return rc;
-    const void* ptr[4] = {q, k, v, o};
-    if (int rc = check_operands(__func__, 4, ptr, strides, D)) return rc;
-    MK_REQUIRE(aligned4(lse), "lse not 4-byte aligned");
     Params p{};
-    p.q = (const bf16*)q, p.k = (const bf16*)k, p.v = (const bf16*)v, p.o = (bf16*)o, p.lse_out = lse;
-    p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.D = D, p.ntile = mk::ceil_div(Nq, kOwn);
-    p.sq = str_at(strides, 0), p.sk = str_at(strides, 1), p.sv = str_at(strides, 2), p.so = str_at(strides, 3);
-    p.scale = scale, p.c = scale * kLog2e;
-    const dim3 grid((unsigned)((long long)p.ntile * H * B));
+    if (int rc = mk::attn::fwd_params(__func__, kFamily, p, (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, B, H, Nq, Nk,
+                                      D, strides, scale))
+        return rc;
+    const dim3 grid = mk::attn::tile_grid(p);
     if (padded_d(D) == 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(kT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attn_fwd_kernel<128>, grid, dim3(kT), 0, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
@@ -426,14 +387,8 @@ extern "C" int mk_attn_fwd(const void* q, const void* k, const void* v, void* o,
 
 extern "C" int mk_attn_bwd_delta(const void* o, const void* dO, float* delta, int B, int H, int Nq, int D, const long long* strides,
                                  void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, 1, D)) return rc;
-    const void* ptr[2] = {o, dO};
-    if (int rc = check_operands(__func__, 2, ptr, strides, D)) return rc;
-    MK_REQUIRE(delta != nullptr && aligned4(delta), "delta null or not 4-byte aligned");
     Params p{};
-    p.o = (bf16*)const_cast<void*>(o), p.dO = (const bf16*)dO, p.lse_out = delta;
-    p.B = B, p.H = H, p.Nq = Nq, p.D = D;
-    p.so = str_at(strides, 0), p.sdo = str_at(strides, 1);
+    if (int rc = mk::attn::delta_params(__func__, kFamily, p, (const bf16*)o, (const bf16*)dO, delta, B, H, Nq, D, strides)) return rc;
     const long long total = (long long)B * H * Nq;
     hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)mk::ceil_div_ll(total, kT)), dim3(kT), 0, (hipStream_t)stream, p, total);
     MK_LAUNCH_CHECK();
@@ -443,18 +398,11 @@ extern "C" int mk_attn_bwd_delta(const void* o, const void* dO, float* delta, in
 extern "C" int mk_attn_bwd_dkv(const void* q, const void* k, const void* v, const void* dO, const float* lse, const float* delta,
                                void* dk, void* dv, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale,
                                void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, Nk, D)) return rc;
-    const void* ptr[6] = {q, k, v, dO, dk, dv};
-    if (int rc = check_operands(__func__, 6, ptr, strides, D)) return rc;
-    MK_REQUIRE(lse && delta && aligned4(lse) && aligned4(delta), "lse / delta null or not 4-byte aligned");
     Params p{};
-    p.q = (const bf16*)q, p.k = (const bf16*)k, p.v = (const bf16*)v, p.dO = (const bf16*)dO, p.dk = (bf16*)dk, p.dv = (bf16*)dv;
-    p.lse = lse, p.delta = delta;
-    p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.D = D, p.ntile = mk::ceil_div(Nk, kOwn);
-    p.sq = str_at(strides, 0), p.sk = str_at(strides, 1), p.sv = str_at(strides, 2), p.sdo = str_at(strides, 3);
-    p.sdk = str_at(strides, 4), p.sdv = str_at(strides, 5);
-    p.scale = scale, p.c = scale * kLog2e;
-    const dim3 grid((unsigned)((long long)p.ntile * H * B));
+    if (int rc = mk::attn::dkv_params(__func__, kFamily, p, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dO, lse, delta,
+                                      (bf16*)dk, (bf16*)dv, B, H, Nq, Nk, D, strides, scale))
+        return rc;
+    const dim3 grid = mk::attn::tile_grid(p);
     if (padded_d(D) == 64) hipLaunchKernelGGL(attn_bwd_dkv_kernel<64>, grid, dim3(kT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attn_bwd_dkv_kernel<128>, grid, dim3(kT), 0, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
@@ -463,18 +411,11 @@ extern "C" int mk_attn_bwd_dkv(const void* q, const void* k, const void* v, cons
 
 extern "C" int mk_attn_bwd_dq(const void* q, const void* k, const void* v, const void* dO, const float* lse, const float* delta,
                               void* dq, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, Nk, D)) return rc;
-    const void* ptr[5] = {q, k, v, dO, dq};
-    if (int rc = check_operands(__func__, 5, ptr, strides, D)) return rc;
-    MK_REQUIRE(lse && delta && aligned4(lse) && aligned4(delta), "lse / delta null or not 4-byte aligned");
     Params p{};
-    p.q = (const bf16*)q, p.k = (const bf16*)k, p.v = (const bf16*)v, p.dO = (const bf16*)dO, p.dq = (bf16*)dq;
-    p.lse = lse, p.delta = delta;
-    p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.D = D, p.ntile = mk::ceil_div(Nq, kOwn);
-    p.sq = str_at(strides, 0), p.sk = str_at(strides, 1), p.sv = str_at(strides, 2), p.sdo = str_at(strides, 3);
-    p.sdq = str_at(strides, 4);
-    p.scale = scale, p.c = scale * kLog2e;
-    const dim3 grid((unsigned)((long long)p.ntile * H * B));
+    if (int rc = mk::attn::dq_params(__func__, kFamily, p, (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dO, lse, delta,
+                                     (bf16*)dq, B, H, Nq, Nk, D, strides, scale))
+        return rc;
+    const dim3 grid = mk::attn::tile_grid(p);
     if (padded_d(D) == 64) hipLaunchKernelGGL(attn_bwd_dq_kernel<64>, grid, dim3(kT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attn_bwd_dq_kernel<128>, grid, dim3(kT), 0, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();

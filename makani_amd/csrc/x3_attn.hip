@@ -20,22 +20,22 @@
 // Head sizes are zero-padded on chip to 64; the 16-wide k-steps and the 32-wide output tiles that lie wholly in the padding get
 // no MFMA work (a wave-uniform test).  D > 64 is refused: the pieces of two owned operands at DP = 128 are 192 registers next
 // to 128 of accumulators in the dK / dV kernel.
+#include "attn_host.h"
 #include "x3_engine.h"
 
 namespace {
 
+using mk::attn::kLog2e;
+using mk::attn::kOwn;
 using mk::mfma::tile_row;
 using mk::mfma::zero;
 
 constexpr int kT = 256;                 // 4 waves
-constexpr int kOwn = 128;               // tokens a workgroup owns (32 per wave)
 constexpr int kDP = 64;                 // padded head size
 constexpr int kFwdTK = 64;              // key tile of fwd
 constexpr int kBwdT = 32;               // key tile of dq, query tile of dkv
 constexpr int KS = kDP / 16, DT = kDP / 32;
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-
-struct Str { long long b, h, n; };      // element strides of batch, head, token; the D axis is contiguous
+constexpr float kLn2 = 0.6931471805599453f;
 
 struct Frag3 { bf16x8 p[3]; };          // the h, m, l pieces of 8 operand elements
 
@@ -174,15 +174,8 @@ __device__ __forceinline__ void store_t(const f32x16 (&acc)[DT], float* row, boo
         }
 }
 
-struct Params {
-    const float *q, *k, *v, *dO;
-    float *o, *dq, *dk, *dv;
-    float* lse_out;                 // fwd: may be null;  delta kernel: the delta buffer
-    const float *lse, *delta;       // bwd
-    int B, H, Nq, Nk, D, ntile;     // ntile: owned tiles per (batch, head)
-    Str sq, sk, sv, so, sdo, sdq, sdk, sdv;
-    float scale, c;                 // c = scale log2(e)
-};
+struct Params : mk::attn::ParamsOf<float> {};
+constexpr mk::attn::Family kFamily{kDP, 4};       // head sizes to 64; strides in units of 4 floats
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kT) void x3_attn_fwd_kernel(Params p) {
@@ -409,37 +402,10 @@ __global__ __launch_bounds__(kT) void x3_attn_bwd_dkv_kernel(Params p) {
     store_t(dk, p.dk + b * p.sdk.b + h * p.sdk.h + key * p.sdk.n, kv, p.D, fh, p.scale);
 }
 
-// ---- validation ------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-bool head_ok(int D) { return D >= 16 && D <= kDP && D % 16 == 0; }
-constexpr const char* kHeadMsg = "head size must be a multiple of 16 in 16 ... 64";
-
-int check_sizes(const char* who, int B, int H, int Nq, int Nk, int D) {
-    MK_REQUIRE_AS(who, B >= 1 && H >= 1 && Nq >= 1 && Nk >= 1, "bad sizes");
-    MK_REQUIRE_AS(who, head_ok(D), kHeadMsg);
-    MK_REQUIRE_AS(who, (double)B * H * (Nq > Nk ? Nq : Nk) < 2147483647.0, "too many rows");
-    MK_REQUIRE_AS(who, (double)B * H * mk::ceil_div(Nq > Nk ? Nq : Nk, kOwn) < 2147483647.0, "grid too large");
-    return 0;
-}
-// n tensors, each a base pointer and (batch, head, token) element strides: multiples of 4 elements, rows do not overlap
-int check_operands(const char* who, int n, const void* const* ptr, const long long* st, int D) {
-    MK_REQUIRE_AS(who, st != nullptr, "null strides");
-    for (int i = 0; i < n; ++i) {
-        MK_REQUIRE_AS(who, ptr[i] != nullptr, "null pointer");
-        MK_REQUIRE_AS(who, aligned16(ptr[i]), "operand not 16-byte aligned");
-        for (int j = 0; j < 3; ++j)
-            MK_REQUIRE_AS(who, st[3 * i + j] >= 0 && st[3 * i + j] % 4 == 0, "strides must be non-negative multiples of 4 elements");
-        MK_REQUIRE_AS(who, st[3 * i + 2] >= D, "token stride smaller than the head size");
-    }
-    return 0;
-}
-Str str_at(const long long* st, int i) { return Str{st[3 * i], st[3 * i + 1], st[3 * i + 2]}; }
-
 }  // namespace
 
 extern "C" int mk_attn_x3_info(int D, int* tiles) {
-    MK_REQUIRE(head_ok(D), kHeadMsg);
+    if (int rc = mk::attn::check_head(__func__, kFamily, D)) return rc;
     MK_REQUIRE(tiles != nullptr, "null pointer");
     tiles[0] = kOwn, tiles[1] = kFwdTK;        // fwd: query tile, key tile
     tiles[2] = kBwdT, tiles[3] = kOwn;         // dkv
@@ -449,31 +415,17 @@ extern "C" int mk_attn_x3_info(int D, int* tiles) {
 
 extern "C" int mk_attn_x3_fwd(const float* q, const float* k, const float* v, float* o, float* lse, int B, int H, int Nq, int Nk, int D,
                               const long long* strides, float scale, void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, Nk, D)) return rc;
-    const void* ptr[4] = {q, k, v, o};
-    if (int rc = check_operands(__func__, 4, ptr, strides, D)) return rc;
-    MK_REQUIRE(aligned4(lse), "lse not 4-byte aligned");
     Params p{};
-    p.q = q, p.k = k, p.v = v, p.o = o, p.lse_out = lse;
-    p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.D = D, p.ntile = mk::ceil_div(Nq, kOwn);
-    p.sq = str_at(strides, 0), p.sk = str_at(strides, 1), p.sv = str_at(strides, 2), p.so = str_at(strides, 3);
-    p.scale = scale, p.c = scale * kLog2e;
-    const dim3 grid((unsigned)((long long)p.ntile * H * B));
-    hipLaunchKernelGGL(x3_attn_fwd_kernel, grid, dim3(kT), 0, (hipStream_t)stream, p);
+    if (int rc = mk::attn::fwd_params(__func__, kFamily, p, q, k, v, o, lse, B, H, Nq, Nk, D, strides, scale)) return rc;
+    hipLaunchKernelGGL(x3_attn_fwd_kernel, mk::attn::tile_grid(p), dim3(kT), 0, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int mk_attn_x3_bwd_delta(const float* o, const float* dO, float* delta, int B, int H, int Nq, int D, const long long* strides,
                                     void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, 1, D)) return rc;
-    const void* ptr[2] = {o, dO};
-    if (int rc = check_operands(__func__, 2, ptr, strides, D)) return rc;
-    MK_REQUIRE(delta != nullptr && aligned4(delta), "delta null or not 4-byte aligned");
     Params p{};
-    p.o = const_cast<float*>(o), p.dO = dO, p.lse_out = delta;
-    p.B = B, p.H = H, p.Nq = Nq, p.D = D;
-    p.so = str_at(strides, 0), p.sdo = str_at(strides, 1);
+    if (int rc = mk::attn::delta_params(__func__, kFamily, p, o, dO, delta, B, H, Nq, D, strides)) return rc;
     const long long total = (long long)B * H * Nq;
     hipLaunchKernelGGL(x3_attn_delta_kernel, dim3((unsigned)mk::ceil_div_ll(total, kT)), dim3(kT), 0, (hipStream_t)stream, p, total);
     MK_LAUNCH_CHECK();
@@ -483,38 +435,18 @@ extern "C" int mk_attn_x3_bwd_delta(const float* o, const float* dO, float* delt
 extern "C" int mk_attn_x3_bwd_dkv(const float* q, const float* k, const float* v, const float* dO, const float* lse, const float* delta,
                                   float* dk, float* dv, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale,
                                   void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, Nk, D)) return rc;
-    const void* ptr[6] = {q, k, v, dO, dk, dv};
-    if (int rc = check_operands(__func__, 6, ptr, strides, D)) return rc;
-    MK_REQUIRE(lse && delta && aligned4(lse) && aligned4(delta), "lse / delta null or not 4-byte aligned");
     Params p{};
-    p.q = q, p.k = k, p.v = v, p.dO = dO, p.dk = dk, p.dv = dv;
-    p.lse = lse, p.delta = delta;
-    p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.D = D, p.ntile = mk::ceil_div(Nk, kOwn);
-    p.sq = str_at(strides, 0), p.sk = str_at(strides, 1), p.sv = str_at(strides, 2), p.sdo = str_at(strides, 3);
-    p.sdk = str_at(strides, 4), p.sdv = str_at(strides, 5);
-    p.scale = scale, p.c = scale * kLog2e;
-    const dim3 grid((unsigned)((long long)p.ntile * H * B));
-    hipLaunchKernelGGL(x3_attn_bwd_dkv_kernel, grid, dim3(kT), 0, (hipStream_t)stream, p);
+    if (int rc = mk::attn::dkv_params(__func__, kFamily, p, q, k, v, dO, lse, delta, dk, dv, B, H, Nq, Nk, D, strides, scale)) return rc;
+    hipLaunchKernelGGL(x3_attn_bwd_dkv_kernel, mk::attn::tile_grid(p), dim3(kT), 0, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
     return 0;
 }
 
 extern "C" int mk_attn_x3_bwd_dq(const float* q, const float* k, const float* v, const float* dO, const float* lse, const float* delta,
                                  float* dq, int B, int H, int Nq, int Nk, int D, const long long* strides, float scale, void* stream) {
-    if (int rc = check_sizes(__func__, B, H, Nq, Nk, D)) return rc;
-    const void* ptr[5] = {q, k, v, dO, dq};
-    if (int rc = check_operands(__func__, 5, ptr, strides, D)) return rc;
-    MK_REQUIRE(lse && delta && aligned4(lse) && aligned4(delta), "lse / delta null or not 4-byte aligned");
     Params p{};
-    p.q = q, p.k = k, p.v = v, p.dO = dO, p.dq = dq;
-    p.lse = lse, p.delta = delta;
-    p.B = B, p.H = H, p.Nq = Nq, p.Nk = Nk, p.D = D, p.ntile = mk::ceil_div(Nq, kOwn);
-    p.sq = str_at(strides, 0), p.sk = str_at(strides, 1), p.sv = str_at(strides, 2), p.sdo = str_at(strides, 3);
-    p.sdq = str_at(strides, 4);
-    p.scale = scale, p.c = scale * kLog2e;
-    const dim3 grid((unsigned)((long long)p.ntile * H * B));
-    hipLaunchKernelGGL(x3_attn_bwd_dq_kernel, grid, dim3(kT), 0, (hipStream_t)stream, p);
+    if (int rc = mk::attn::dq_params(__func__, kFamily, p, q, k, v, dO, lse, delta, dq, B, H, Nq, Nk, D, strides, scale)) return rc;
+    hipLaunchKernelGGL(x3_attn_bwd_dq_kernel, mk::attn::tile_grid(p), dim3(kT), 0, (hipStream_t)stream, p);
     MK_LAUNCH_CHECK();
     return 0;
 }

@@ -11,6 +11,7 @@ complex64 ``[L, M, BC]`` (channels last), dhconv weight = complex64 ``[L, I, O]`
 import ctypes
 import math
 import os
+import typing
 
 import numpy as np
 import torch
@@ -2090,147 +2091,8 @@ def attn_hip():
     return _hip_or_torch("MK_ATTN", ATTN_DEFAULT)
 
 
-def attn_info(head_dim):
-    """(query tile, key tile) of the forward, the dK / dV and the dQ kernel at this head size: three pairs."""
-    t = (ctypes.c_int * 6)()
-    _lib.check(_lib.load().mk_attn_info(int(head_dim), ctypes.addressof(t)), "mk_attn_info")
-    return (t[0], t[1]), (t[2], t[3]), (t[4], t[5])
-
-
-def _attn_strides(t):
-    """(batch, head, token) element strides of a ``[B, H, N, D]`` view; an axis of size 1 has no stride of its own."""
-    sb, sh, sn = t.stride(0), t.stride(1), t.stride(2)
-    return (sb if t.shape[0] > 1 else 0, sh if t.shape[1] > 1 else 0, sn if t.shape[2] > 1 else t.shape[3])
-
-
-def _attn_operand_ok(t):
-    if t.dim() != 4 or not t.is_cuda or t.dtype != torch.bfloat16 or t.stride(3) != 1 or t.data_ptr() % 16:
-        return False
-    sb, sh, sn = _attn_strides(t)
-    return min(sb, sh) >= 0 and sb % 8 == 0 and sh % 8 == 0 and sn % 8 == 0 and sn >= t.shape[3]
-
-
-def attention_supported(q, k, v):
-    """True when the kernels take these ``[B, H, N, D]`` views as they are: bf16 on the device, D a multiple of 16 in 16 ... 128 and
-    contiguous, 16-byte aligned, batch / head / token strides multiples of 8 elements."""
-    if not (q.dim() == k.dim() == v.dim() == 4 and k.shape == v.shape and q.shape[:2] == k.shape[:2] and q.shape[3] == k.shape[3]):
-        return False
-    D = q.shape[3]
-    if D % 16 or not 16 <= D <= 128 or min(q.shape[2], k.shape[2], q.shape[0], q.shape[1]) < 1:
-        return False
-    return all(_attn_operand_ok(t) for t in (q, k, v))
-
-
-def _attn_stride_array(*tensors):
-    flat = [s for t in tensors for s in _attn_strides(t)]
-    return (ctypes.c_longlong * len(flat))(*flat)
-
-
-def attn_fwd_raw(q, k, v, o, lse, scale):
-    """``o`` (a ``[B, H, Nq, D]`` view, written in place) and, unless None, ``lse`` ``[B, H, Nq]`` fp32 from ``[B, H, N, D]`` views."""
-    B, H, Nq, D = q.shape
-    st = _attn_stride_array(q, k, v, o)
-    _lib.check(_lib.load().mk_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _ptr(lse), B, H, Nq, k.shape[2], D,
-                                       ctypes.addressof(st), float(scale), _stream()), "mk_attn_fwd")
-
-
-def attn_bwd_raw(q, k, v, o, go, lse, dq, dk, dv, scale):
-    """The three gradients, written in place into the ``[B, H, N, D]`` views ``dq``, ``dk``, ``dv``: delta, then dK / dV, then dQ."""
-    B, H, Nq, D = q.shape
-    Nk = k.shape[2]
-    lib = _lib.load()
-    delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
-    st = _attn_stride_array(o, go)
-    _lib.check(lib.mk_attn_bwd_delta(o.data_ptr(), go.data_ptr(), delta.data_ptr(), B, H, Nq, D, ctypes.addressof(st), _stream()),
-               "mk_attn_bwd_delta")
-    st = _attn_stride_array(q, k, v, go, dk, dv)
-    _lib.check(lib.mk_attn_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                   dk.data_ptr(), dv.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()),
-               "mk_attn_bwd_dkv")
-    st = _attn_stride_array(q, k, v, go, dq)
-    _lib.check(lib.mk_attn_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                  dq.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()), "mk_attn_bwd_dq")
-
-
-def _attn_grad_out(go):
-    """The upstream gradient as a view the kernels take (a token-major ``[B, N, H D]`` gradient already is one)."""
-    return go if _attn_operand_ok(go) else go.contiguous()
-
-
-class _Attention(torch.autograd.Function):
-    """``softmax(scale q k^T) v`` on ``[B, H, N, D]`` views.  The output and the gradients are token-major buffers ``[B, N, H, D]``
-    seen through a permutation, so the ``transpose(1, 2).reshape(B, N, C)`` behind the op is a view."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, scale):
-        B, H, Nq, D = q.shape
-        o = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        need = any(ctx.needs_input_grad[:3])
-        lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if need else None
-        attn_fwd_raw(q, k, v, o, lse, scale)
-        if need:
-            ctx.save_for_backward(q, k, v, o, lse)
-            ctx.scale = scale
-        return o
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, go):
-        q, k, v, o, lse = ctx.saved_tensors
-        B, H, Nq, D = q.shape
-        Nk = k.shape[2]
-        dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        attn_bwd_raw(q, k, v, o, _attn_grad_out(go), lse, dq, dk, dv, ctx.scale)
-        return dq, dk, dv, None
-
-
-def _qkv_views(qkv, B, N, H, D):
-    return tuple(t.permute(0, 2, 1, 3) for t in qkv.view(B, N, 3, H, D).unbind(2))
-
-
-class _AttentionPacked(torch.autograd.Function):
-    """The same on the projection output ``qkv`` ``[B, N, 3 H D]`` as it stands: q, k, v are three strided views of it, the output
-    is ``[B, N, H D]`` and the gradient one ``[B, N, 3 H D]`` buffer the kernels write in place.  No permuted copy, no cat."""
-
-    @staticmethod
-    def forward(ctx, qkv, H, scale):
-        B, N, C3 = qkv.shape
-        D = C3 // (3 * H)
-        q, k, v = _qkv_views(qkv, B, N, H, D)
-        o = torch.empty(B, N, H * D, dtype=qkv.dtype, device=qkv.device)
-        need = ctx.needs_input_grad[0]
-        lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device) if need else None
-        attn_fwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), lse, scale)
-        if need:
-            ctx.save_for_backward(qkv, o, lse)
-            ctx.args = (H, scale)
-        return o
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, go):
-        qkv, o, lse = ctx.saved_tensors
-        H, scale = ctx.args
-        B, N, C3 = qkv.shape
-        D = C3 // (3 * H)
-        q, k, v = _qkv_views(qkv, B, N, H, D)
-        dqkv = torch.empty(B, N, C3, dtype=qkv.dtype, device=qkv.device)
-        dq, dk, dv = _qkv_views(dqkv, B, N, H, D)
-        go = _attn_grad_out(go.reshape(B, N, H, D).permute(0, 2, 1, 3))
-        attn_bwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), go, lse, dq, dk, dv, scale)
-        return dqkv, None, None
-
-
-def _attn_scale(scale, D):
-    return float(scale) if scale is not None else 1.0 / math.sqrt(D)
-
-
-# ----------------------------------------------------------------------------
-# the same attention on fp32 operands outside autocast (csrc/x3_attn.hip): fp32-accurate on the bf16x3 arithmetic
-# ----------------------------------------------------------------------------
-# Opt-in by the rule of DESIGN section 19 (DESIGN section 31 has the rows of tools/attn_fp32_bench.py).
+# The same attention on fp32 operands outside autocast (csrc/x3_attn.hip), fp32-accurate on the bf16x3 arithmetic, is opt-in by
+# the rule of DESIGN section 19 (DESIGN section 31 has the rows of tools/attn_fp32_bench.py).
 ATTN_FP32_DEFAULT = "torch"
 ATTN_X3_MAX_HEAD = 64
 
@@ -2241,85 +2103,153 @@ def attn_fp32_hip():
     return _hip_or_torch("MK_ATTN_FP32", ATTN_FP32_DEFAULT)
 
 
-def attn_x3_info(head_dim):
-    """(query tile, key tile) of the fp32 forward, dK / dV and dQ kernels at this head size: three pairs (no device needed)."""
+class _AttnArith(typing.NamedTuple):
+    """What differs between the two attention arithmetics; everything below is written once over it."""
+    prefix: str                 # the entry points are <prefix>_info / _fwd / _bwd_delta / _bwd_dkv / _bwd_dq
+    dtype: torch.dtype          # of every operand, the output and the gradients; strides are multiples of 16 bytes of it
+    max_head: int               # head sizes are the multiples of 16 in 16 ... max_head
+    x3: bool                    # runs on the bf16x3 engine: needs it selected (SPECTRAL_GEMM) and no device autocast
+    fwd: typing.Callable        # the raw wrappers, looked up in the module when called
+    bwd: typing.Callable
+
+
+_ATTN_BF16 = _AttnArith("mk_attn", torch.bfloat16, 128, False, lambda *a: attn_fwd_raw(*a), lambda *a: attn_bwd_raw(*a))
+_ATTN_X3 = _AttnArith("mk_attn_x3", torch.float32, ATTN_X3_MAX_HEAD, True, lambda *a: attn_x3_fwd_raw(*a), lambda *a: attn_x3_bwd_raw(*a))
+
+
+def _attn_info(a, head_dim):
     t = (ctypes.c_int * 6)()
-    _lib.check(_lib.load().mk_attn_x3_info(int(head_dim), ctypes.addressof(t)), "mk_attn_x3_info")
+    _lib.check(getattr(_lib.load(), a.prefix + "_info")(int(head_dim), ctypes.addressof(t)), a.prefix + "_info")
     return (t[0], t[1]), (t[2], t[3]), (t[4], t[5])
 
 
-def _attn_x3_operand_ok(t):
-    if t.dim() != 4 or not t.is_cuda or t.dtype != torch.float32 or t.stride(3) != 1 or t.data_ptr() % 16:
+def attn_info(head_dim):
+    """(query tile, key tile) of the forward, the dK / dV and the dQ kernel at this head size: three pairs."""
+    return _attn_info(_ATTN_BF16, head_dim)
+
+
+def attn_x3_info(head_dim):
+    """(query tile, key tile) of the fp32 forward, dK / dV and dQ kernels at this head size: three pairs (no device needed)."""
+    return _attn_info(_ATTN_X3, head_dim)
+
+
+def _attn_strides(t):
+    """(batch, head, token) element strides of a ``[B, H, N, D]`` view; an axis of size 1 has no stride of its own."""
+    sb, sh, sn = t.stride(0), t.stride(1), t.stride(2)
+    return (sb if t.shape[0] > 1 else 0, sh if t.shape[1] > 1 else 0, sn if t.shape[2] > 1 else t.shape[3])
+
+
+def _attn_operand_ok(t, dtype):
+    """A ``[B, H, N, D]`` device view of this dtype, D contiguous, 16-byte aligned, every stride a multiple of 16 bytes."""
+    if t.dim() != 4 or not t.is_cuda or t.dtype != dtype or t.stride(3) != 1 or t.data_ptr() % 16:
         return False
+    unit = 16 // t.element_size()
     sb, sh, sn = _attn_strides(t)
-    return min(sb, sh) >= 0 and sb % 4 == 0 and sh % 4 == 0 and sn % 4 == 0 and sn >= t.shape[3]
+    return min(sb, sh) >= 0 and sb % unit == 0 and sh % unit == 0 and sn % unit == 0 and sn >= t.shape[3]
 
 
-def attention_x3_supported(q, k, v):
-    """True when the ``mk_attn_x3_*`` kernels take these ``[B, H, N, D]`` views as they are: fp32 on the device with device
-    autocast NOT active, the engine selected (``MK_SPECTRAL_GEMM=bf16x3``, as ``token_linear_x3_supported`` requires), D a
-    multiple of 16 in 16 ... 64 and contiguous, 16-byte aligned, batch / head / token strides multiples of 4 elements."""
-    if SPECTRAL_GEMM != "bf16x3":
+def _attn_supported(a, q, k, v):
+    if a.x3 and SPECTRAL_GEMM != "bf16x3":
         return False
     if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)):
         return False
     if not (k.shape == v.shape and q.shape[:2] == k.shape[:2] and q.shape[3] == k.shape[3]):
         return False
     D = q.shape[3]
-    if D % 16 or not 16 <= D <= ATTN_X3_MAX_HEAD or min(q.shape[2], k.shape[2], q.shape[0], q.shape[1]) < 1:
+    if D % 16 or not 16 <= D <= a.max_head or min(q.shape[2], k.shape[2], q.shape[0], q.shape[1]) < 1:
         return False
-    if not all(_attn_x3_operand_ok(t) for t in (q, k, v)):
+    if not all(_attn_operand_ok(t, a.dtype) for t in (q, k, v)):
         return False
-    return _autocast_dtype() is None
+    return not a.x3 or _autocast_dtype() is None
 
 
-def attn_x3_fwd_raw(q, k, v, o, lse, scale):
-    """``attn_fwd_raw`` on fp32 views."""
+def attention_supported(q, k, v):
+    """True when the kernels take these ``[B, H, N, D]`` views as they are: bf16 on the device, D a multiple of 16 in 16 ... 128 and
+    contiguous, 16-byte aligned, batch / head / token strides multiples of 8 elements."""
+    return _attn_supported(_ATTN_BF16, q, k, v)
+
+
+def attention_x3_supported(q, k, v):
+    """True when the ``mk_attn_x3_*`` kernels take these ``[B, H, N, D]`` views as they are: fp32 on the device with device
+    autocast NOT active, the engine selected (``MK_SPECTRAL_GEMM=bf16x3``, as ``token_linear_x3_supported`` requires), D a
+    multiple of 16 in 16 ... 64 and contiguous, 16-byte aligned, batch / head / token strides multiples of 4 elements."""
+    return _attn_supported(_ATTN_X3, q, k, v)
+
+
+def _attn_stride_array(*tensors):
+    flat = [s for t in tensors for s in _attn_strides(t)]
+    return (ctypes.c_longlong * len(flat))(*flat)
+
+
+def _attn_fwd(a, q, k, v, o, lse, scale):
     B, H, Nq, D = q.shape
     st = _attn_stride_array(q, k, v, o)
-    _lib.check(_lib.load().mk_attn_x3_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _ptr(lse), B, H, Nq, k.shape[2], D,
-                                          ctypes.addressof(st), float(scale), _stream()), "mk_attn_x3_fwd")
+    _lib.check(getattr(_lib.load(), a.prefix + "_fwd")(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), _ptr(lse), B, H, Nq,
+                                                       k.shape[2], D, ctypes.addressof(st), float(scale), _stream()), a.prefix + "_fwd")
 
 
-def attn_x3_bwd_raw(q, k, v, o, go, lse, dq, dk, dv, scale):
-    """``attn_bwd_raw`` on fp32 views: delta, then dK / dV, then dQ."""
+def _attn_bwd(a, q, k, v, o, go, lse, dq, dk, dv, scale):
     B, H, Nq, D = q.shape
     Nk = k.shape[2]
     lib = _lib.load()
     delta = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device)
     st = _attn_stride_array(o, go)
-    _lib.check(lib.mk_attn_x3_bwd_delta(o.data_ptr(), go.data_ptr(), delta.data_ptr(), B, H, Nq, D, ctypes.addressof(st), _stream()),
-               "mk_attn_x3_bwd_delta")
+    _lib.check(getattr(lib, a.prefix + "_bwd_delta")(o.data_ptr(), go.data_ptr(), delta.data_ptr(), B, H, Nq, D, ctypes.addressof(st),
+                                                     _stream()), a.prefix + "_bwd_delta")
     st = _attn_stride_array(q, k, v, go, dk, dv)
-    _lib.check(lib.mk_attn_x3_bwd_dkv(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                      dk.data_ptr(), dv.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()),
-               "mk_attn_x3_bwd_dkv")
+    _lib.check(getattr(lib, a.prefix + "_bwd_dkv")(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                                   dk.data_ptr(), dv.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale),
+                                                   _stream()), a.prefix + "_bwd_dkv")
     st = _attn_stride_array(q, k, v, go, dq)
-    _lib.check(lib.mk_attn_x3_bwd_dq(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                                     dq.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()), "mk_attn_x3_bwd_dq")
+    _lib.check(getattr(lib, a.prefix + "_bwd_dq")(q.data_ptr(), k.data_ptr(), v.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                                  dq.data_ptr(), B, H, Nq, Nk, D, ctypes.addressof(st), float(scale), _stream()),
+               a.prefix + "_bwd_dq")
 
 
-def _attn_x3_grad_out(go):
-    return go if _attn_x3_operand_ok(go) else go.contiguous()
+def attn_fwd_raw(q, k, v, o, lse, scale):
+    """``o`` (a ``[B, H, Nq, D]`` view, written in place) and, unless None, ``lse`` ``[B, H, Nq]`` fp32 from ``[B, H, N, D]`` views."""
+    _attn_fwd(_ATTN_BF16, q, k, v, o, lse, scale)
 
 
-class _AttentionX3(torch.autograd.Function):
-    """``_Attention`` on fp32 views and the ``mk_attn_x3_*`` kernels: the same saved set, the same permuted-view outputs."""
+def attn_bwd_raw(q, k, v, o, go, lse, dq, dk, dv, scale):
+    """The three gradients, written in place into the ``[B, H, N, D]`` views ``dq``, ``dk``, ``dv``: delta, then dK / dV, then dQ."""
+    _attn_bwd(_ATTN_BF16, q, k, v, o, go, lse, dq, dk, dv, scale)
 
-    @staticmethod
+
+def attn_x3_fwd_raw(q, k, v, o, lse, scale):
+    """``attn_fwd_raw`` on fp32 views."""
+    _attn_fwd(_ATTN_X3, q, k, v, o, lse, scale)
+
+
+def attn_x3_bwd_raw(q, k, v, o, go, lse, dq, dk, dv, scale):
+    """``attn_bwd_raw`` on fp32 views: delta, then dK / dV, then dQ."""
+    _attn_bwd(_ATTN_X3, q, k, v, o, go, lse, dq, dk, dv, scale)
+
+
+def _attn_grad_out(go):
+    """The upstream gradient as a view the kernels take (a token-major ``[B, N, H D]`` gradient already is one)."""
+    return go if _attn_operand_ok(go, go.dtype) else go.contiguous()
+
+
+def _node(name, doc, forward, backward):
+    """An autograd function of this name -- its graph nodes are ``<name>Backward`` -- from two plain functions."""
+    return type(name, (torch.autograd.Function,), dict(
+        __doc__=doc, __module__=__name__, forward=staticmethod(forward),
+        backward=staticmethod(torch.autograd.function.once_differentiable(backward))))
+
+
+def _attention_node(name, a, doc):
     def forward(ctx, q, k, v, scale):
         B, H, Nq, D = q.shape
         o = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
         need = any(ctx.needs_input_grad[:3])
         lse = torch.empty(B, H, Nq, dtype=torch.float32, device=q.device) if need else None
-        attn_x3_fwd_raw(q, k, v, o, lse, scale)
+        a.fwd(q, k, v, o, lse, scale)
         if need:
             ctx.save_for_backward(q, k, v, o, lse)
             ctx.scale = scale
         return o
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, go):
         q, k, v, o, lse = ctx.saved_tensors
         B, H, Nq, D = q.shape
@@ -2327,14 +2257,24 @@ class _AttentionX3(torch.autograd.Function):
         dq = torch.empty(B, Nq, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
         dk = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
         dv = torch.empty(B, Nk, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
-        attn_x3_bwd_raw(q, k, v, o, _attn_x3_grad_out(go), lse, dq, dk, dv, ctx.scale)
+        a.bwd(q, k, v, o, _attn_grad_out(go), lse, dq, dk, dv, ctx.scale)
         return dq, dk, dv, None
 
+    return _node(name, doc, forward, backward)
 
-class _AttentionPackedX3(torch.autograd.Function):
-    """``_AttentionPacked`` on an fp32 projection output ``[B, N, 3 H D]``: one gradient tensor, written in place."""
 
-    @staticmethod
+_Attention = _attention_node("_Attention", _ATTN_BF16, """``softmax(scale q k^T) v`` on ``[B, H, N, D]`` views.  The output and the
+    gradients are token-major buffers ``[B, N, H, D]`` seen through a permutation, so the ``transpose(1, 2).reshape(B, N, C)``
+    behind the op is a view.""")
+_AttentionX3 = _attention_node("_AttentionX3", _ATTN_X3, """``_Attention`` on fp32 views and the ``mk_attn_x3_*`` kernels: the same
+    saved set, the same permuted-view outputs.""")
+
+
+def _qkv_views(qkv, B, N, H, D):
+    return tuple(t.permute(0, 2, 1, 3) for t in qkv.view(B, N, 3, H, D).unbind(2))
+
+
+def _attention_packed_node(name, a, doc):
     def forward(ctx, qkv, H, scale):
         B, N, C3 = qkv.shape
         D = C3 // (3 * H)
@@ -2342,14 +2282,12 @@ class _AttentionPackedX3(torch.autograd.Function):
         o = torch.empty(B, N, H * D, dtype=qkv.dtype, device=qkv.device)
         need = ctx.needs_input_grad[0]
         lse = torch.empty(B, H, N, dtype=torch.float32, device=qkv.device) if need else None
-        attn_x3_fwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), lse, scale)
+        a.fwd(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), lse, scale)
         if need:
             ctx.save_for_backward(qkv, o, lse)
             ctx.args = (H, scale)
         return o
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, go):
         qkv, o, lse = ctx.saved_tensors
         H, scale = ctx.args
@@ -2358,9 +2296,22 @@ class _AttentionPackedX3(torch.autograd.Function):
         q, k, v = _qkv_views(qkv, B, N, H, D)
         dqkv = torch.empty(B, N, C3, dtype=qkv.dtype, device=qkv.device)
         dq, dk, dv = _qkv_views(dqkv, B, N, H, D)
-        go = _attn_x3_grad_out(go.reshape(B, N, H, D).permute(0, 2, 1, 3))
-        attn_x3_bwd_raw(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), go, lse, dq, dk, dv, scale)
+        go = _attn_grad_out(go.reshape(B, N, H, D).permute(0, 2, 1, 3))
+        a.bwd(q, k, v, o.view(B, N, H, D).permute(0, 2, 1, 3), go, lse, dq, dk, dv, scale)
         return dqkv, None, None
+
+    return _node(name, doc, forward, backward)
+
+
+_AttentionPacked = _attention_packed_node("_AttentionPacked", _ATTN_BF16, """The same on the projection output ``qkv``
+    ``[B, N, 3 H D]`` as it stands: q, k, v are three strided views of it, the output is ``[B, N, H D]`` and the gradient one
+    ``[B, N, 3 H D]`` buffer the kernels write in place.  No permuted copy, no cat.""")
+_AttentionPackedX3 = _attention_packed_node("_AttentionPackedX3", _ATTN_X3, """``_AttentionPacked`` on an fp32 projection output
+    ``[B, N, 3 H D]``: one gradient tensor, written in place.""")
+
+
+def _attn_scale(scale, D):
+    return float(scale) if scale is not None else 1.0 / math.sqrt(D)
 
 
 def _attn_autocast(*tensors):
@@ -2370,17 +2321,24 @@ def _attn_autocast(*tensors):
     return tensors if dt is None else tuple(t.to(dt) for t in tensors)
 
 
+def _attn_arith(knobs, t, dropout_p):
+    """The arithmetic of ``t``'s dtype when its knob is at ``hip`` and there is no dropout, else None: the torch call."""
+    for a, on in zip((_ATTN_BF16, _ATTN_X3), knobs):
+        if on and dropout_p == 0.0 and t.dtype == a.dtype:
+            return a
+    return None
+
+
 def attention(q, k, v, scale=None, dropout_p=0.0):
     """``F.scaled_dot_product_attention(q, k, v)`` (no mask, not causal) for ``[B, H, N, D]`` views; returns ``[B, H, Nq, D]``.
     bf16 device tensors that ``attention_supported`` accepts run on the ``mk_attn_*`` kernels under ``MK_ATTN=hip``; fp32 device
     tensors outside autocast that ``attention_x3_supported`` accepts run on the ``mk_attn_x3_*`` kernels under ``MK_ATTN_FP32=hip``;
     fp16 inputs, CPU tensors, other head sizes or strides, ``dropout_p > 0`` and the knobs at ``torch`` take the torch formulation."""
-    hip, fp32_hip = attn_hip(), attn_fp32_hip()
+    knobs = attn_hip(), attn_fp32_hip()
     q, k, v = _attn_autocast(q, k, v)
-    if hip and dropout_p == 0.0 and attention_supported(q, k, v):
-        return _Attention.apply(q, k, v, _attn_scale(scale, q.shape[-1]))
-    if fp32_hip and dropout_p == 0.0 and attention_x3_supported(q, k, v):
-        return _AttentionX3.apply(q, k, v, _attn_scale(scale, q.shape[-1]))
+    a = _attn_arith(knobs, q, dropout_p)
+    if a is not None and _attn_supported(a, q, k, v):
+        return (_AttentionX3 if a.x3 else _Attention).apply(q, k, v, _attn_scale(scale, q.shape[-1]))
     return torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
 
 
@@ -2392,16 +2350,13 @@ def attention_packed(qkv, num_heads, scale=None, dropout_p=0.0):
     B, N, C3 = qkv.shape
     H = int(num_heads)
     D = C3 // (3 * H)
-    hip, fp32_hip = attn_hip(), attn_fp32_hip()
+    knobs = attn_hip(), attn_fp32_hip()
     (qkv,) = _attn_autocast(qkv)
-    if hip and dropout_p == 0.0 and qkv.is_cuda and qkv.dtype == torch.bfloat16:
+    a = _attn_arith(knobs, qkv, dropout_p)
+    if a is not None and qkv.is_cuda:
         x = qkv if (qkv.stride(2) == 1 and qkv.data_ptr() % 16 == 0) else qkv.contiguous()
-        if attention_supported(*_qkv_views(x.detach(), B, N, H, D)):
-            return _AttentionPacked.apply(x, H, _attn_scale(scale, D))
-    if fp32_hip and dropout_p == 0.0 and qkv.is_cuda and qkv.dtype == torch.float32:
-        x = qkv if (qkv.stride(2) == 1 and qkv.data_ptr() % 16 == 0) else qkv.contiguous()
-        if attention_x3_supported(*_qkv_views(x.detach(), B, N, H, D)):
-            return _AttentionPackedX3.apply(x, H, _attn_scale(scale, D))
+        if _attn_supported(a, *_qkv_views(x.detach(), B, N, H, D)):
+            return (_AttentionPackedX3 if a.x3 else _AttentionPacked).apply(x, H, _attn_scale(scale, D))
     q, k, v = (t.permute(0, 2, 1, 3) for t in qkv.reshape(B, N, 3, H, D).unbind(2))
     o = torch.nn.functional.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, scale=scale)
     return o.transpose(1, 2).reshape(B, N, H * D)
@@ -2608,17 +2563,73 @@ def _row_stride(t):
     return L if ld is None else ld
 
 
-def _toklin_rows(t):
-    """``t`` ``[..., L]`` as the kernels take it, and its row stride: itself where ``token_linear_supported`` would accept its
-    layout, else a contiguous copy."""
+# The same linears on fp32 rows outside autocast (csrc/x3_toklinear.hip), fp32-accurate on the bf16x3 engine, are opt-in by the
+# rule of DESIGN section 19 until every row of tools/toklinear_fp32_bench.py has been measured faster than the torch path
+# (DESIGN section 30).
+TOKEN_LINEAR_FP32_DEFAULT = "torch"
+
+
+def token_linear_fp32_hip():
+    """``MK_TOKEN_LINEAR_FP32=hip|torch`` (read at call time): fp32 token-major linears outside autocast on the
+    ``mk_token_linear_x3_*`` kernels, or ``F.linear``.  Independent of ``MK_TOKEN_LINEAR``."""
+    return _hip_or_torch("MK_TOKEN_LINEAR_FP32", TOKEN_LINEAR_FP32_DEFAULT)
+
+
+def token_linear_x3_info():
+    """The tile of the kernels (no device needed): ``tr`` rows, ``tc`` columns, ``tk`` contraction step."""
+    t = (ctypes.c_int * 3)()
+    _lib.check(_lib.load().mk_token_linear_x3_info(ctypes.addressof(t)), "mk_token_linear_x3_info")
+    return dict(zip(("tr", "tc", "tk"), t))
+
+
+class _LinearArith(typing.NamedTuple):
+    """What differs between the two arithmetics of the token-major linears and the patch embedding.  The
+    nodes, the predicates and the dispatch below are written once over it.  The functions are looked up in the module when
+    they are called."""
+    dtype: torch.dtype          # of the rows, the results and the data gradients
+    unit: int                   # feature counts and every row stride (an fp32 addend's too) are multiples of it: 16 bytes of dtype
+    param_dtypes: tuple         # of weights and biases
+    x3: bool                    # runs on the bf16x3 engine: needs it selected (SPECTRAL_GEMM) and no bf16 device autocast
+    weight: typing.Callable     # (weight) -> what the forward GEMM reads, saved for the backward
+    gemm: typing.Callable       # (x, x_ld, w, bias, R, out, gelu, want_pre, addend, addend_ld) -> pre or None
+    dgrad: typing.Callable      # (g, g_ld, saved w, R, out, aux, aux_ld): the data gradient, times gelu'(aux) with aux
+    wgrad: typing.Callable      # the weight / bias gradient: the raw wrapper's signature
+    gelu_grad: typing.Callable  # (g, g_ld, pre, R, O) -> g gelu'(pre) as contiguous rows, where no GEMM epilogue takes it
+
+
+def _toklin_rows(t, unit):
+    """``t`` ``[..., L]`` as the kernels of the arithmetic with this stride unit take it, and its row stride: itself where its
+    layout fits, else a contiguous copy."""
     ld = _row_stride(t)
-    if ld is None or ld % 8 or ld < t.shape[-1] or t.data_ptr() % 16:
+    if ld is None or ld % unit or ld < t.shape[-1] or t.data_ptr() % 16:
         return t.contiguous(), t.shape[-1]
     return t, ld
 
 
-def _toklin_param_ok(p, shape, device):
-    return (torch.is_tensor(p) and p.device == device and p.dtype in (torch.float32, torch.bfloat16) and tuple(p.shape) == shape)
+def _toklin_param_ok(a, p, shape, device):
+    return torch.is_tensor(p) and p.device == device and p.dtype in a.param_dtypes and tuple(p.shape) == shape
+
+
+def _toklin_supported(a, x, weight, bias):
+    if a.x3 and SPECTRAL_GEMM != "bf16x3":
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.numel() > 0 and torch.is_tensor(weight) and weight.dim() == 2):
+        return False
+    O, I = weight.shape
+    if x.shape[-1] != I or I % a.unit or O % a.unit or I < a.unit or O < a.unit:
+        return False
+    lowp = _autocast_dtype() == torch.bfloat16      # F.linear would take x in bf16
+    if a.x3:
+        if x.dtype != torch.float32 or lowp:
+            return False
+    elif x.dtype != torch.bfloat16 and not (x.is_floating_point() and lowp):
+        return False
+    if not _toklin_param_ok(a, weight, (O, I), x.device) or (bias is not None and not _toklin_param_ok(a, bias, (O,), x.device)):
+        return False
+    ld = _row_stride(x)
+    if ld is None or ld % a.unit or ld < I:
+        return False
+    return x.dtype != a.dtype or x.data_ptr() % 16 == 0      # a cast under autocast makes a fresh, aligned tensor
 
 
 def token_linear_supported(x, weight, bias=None):
@@ -2626,19 +2637,15 @@ def token_linear_supported(x, weight, bias=None):
     floating-point dtype under bf16 device autocast, which takes it in bf16 as ``F.linear`` does --, its last axis contiguous, its
     rows at one common stride that is a multiple of 8, 16-byte aligned; ``I`` and ``O`` multiples of 8; ``weight`` ``[O, I]``
     and ``bias`` ``[O]`` (or None) fp32 or bf16 on the same device."""
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.numel() > 0 and torch.is_tensor(weight) and weight.dim() == 2):
-        return False
-    O, I = weight.shape
-    if x.shape[-1] != I or I % 8 or O % 8 or I < 8 or O < 8:
-        return False
-    if x.dtype != torch.bfloat16 and not (x.is_floating_point() and _autocast_dtype() == torch.bfloat16):
-        return False
-    if not _toklin_param_ok(weight, (O, I), x.device) or (bias is not None and not _toklin_param_ok(bias, (O,), x.device)):
-        return False
-    ld = _row_stride(x)
-    if ld is None or ld % 8 or ld < I:
-        return False
-    return x.dtype != torch.bfloat16 or x.data_ptr() % 16 == 0      # a cast under autocast makes a fresh, aligned tensor
+    return _toklin_supported(_TOKLIN_BF16, x, weight, bias)
+
+
+def token_linear_x3_supported(x, weight, bias=None):
+    """True for what the ``mk_token_linear_x3_*`` kernels take as it is: ``x`` ``[..., I]`` fp32 on the device with bf16 device
+    autocast NOT active, its last axis contiguous, its rows at one common stride that is a multiple of 4 and at least ``I``,
+    16-byte aligned; ``I`` and ``O`` multiples of 4; ``weight`` ``[O, I]`` and ``bias`` ``[O]`` (or None) fp32 on the same device;
+    and the engine selected (``MK_SPECTRAL_GEMM=bf16x3``, the default: with ``f32`` the torch path is taken)."""
+    return _toklin_supported(_TOKLIN_X3, x, weight, bias)
 
 
 def token_linear_pack_raw(weight, transpose=False):
@@ -2678,201 +2685,8 @@ def token_linear_wgrad_raw(dy, dy_ld, x, x_ld, R, O, I, want_db, slabs=0):
     return dw, db
 
 
-def _toklin_bias(bias):
-    return None if bias is None else bias.detach().float().contiguous()        # fp32 as it is; a bf16 bias exactly
-
-
-def _toklin_grad_rows(g, O):
-    """The incoming gradient as bf16 rows ``[R, O]`` (the gradient of the bf16 result that the fp32 sum was formed from)."""
-    g = g.reshape(-1, O)
-    return _toklin_rows(g if g.dtype == torch.bfloat16 else g.to(torch.bfloat16))
-
-
-def _toklin_param_grad(g, dtype):
-    return None if g is None else (g if g.dtype == dtype else g.to(dtype))
-
-
-class _TokenLinear(torch.autograd.Function):
-    """``y = x W^T + b`` on bf16 rows, optionally through the exact GELU or added to an fp32 ``addend``: one pack and one GEMM.
-    Saves ``x``, the bf16 weight image and, with ``gelu``, the pre-activation.  Backward: ``g gelu'(pre)`` first with ``gelu``, a
-    transposed pack and the GEMM again for ``dx``, the slab kernel for ``dW`` and ``db`` (fp32)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, gelu, addend):
-        O, I = weight.shape
-        shape = x.shape[:-1] + (O,)
-        xr, x_ld = _toklin_rows(x)
-        R = x.numel() // I
-        wimg = token_linear_pack_raw(weight)
-        bf = _toklin_bias(bias)
-        need = any(ctx.needs_input_grad[:3])
-        pre = None
-        if addend is not None:
-            ar, a_ld = _toklin_rows(addend.detach().reshape(-1, O))
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
-            token_linear_fwd_raw(xr, x_ld, wimg, bf, R, addend=ar, addend_ld=a_ld, out_f32=out)
-        else:
-            out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
-            if gelu:
-                pre = torch.empty(shape, dtype=torch.bfloat16, device=x.device) if need else None
-                token_linear_fwd_raw(xr, x_ld, wimg, bf, R, act=out, pre=pre)
-            else:
-                token_linear_fwd_raw(xr, x_ld, wimg, bf, R, y=out)
-        if need:
-            ctx.save_for_backward(xr, wimg, pre)
-        ctx.cfg = (x_ld, R, tuple(x.shape), weight.dtype, None if bias is None else bias.dtype)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        if not ctx.saved_tensors:               # only the addend asks for a gradient: the incoming one
-            return None, None, None, None, g
-        xr, wimg, pre = ctx.saved_tensors
-        x_ld, R, x_shape, w_dtype, b_dtype = ctx.cfg
-        has_bias = b_dtype is not None
-        O, I = wimg.shape
-        lib = _lib.load()
-        g_in = g
-        g, g_ld = _toklin_grad_rows(g, O)
-        if pre is not None:                     # through the GELU: g gelu'(pre), rounded to bf16 as torch's gelu backward rounds it
-            gp = torch.empty(R, O, dtype=torch.bfloat16, device=g.device)
-            _lib.check(lib.mk_token_linear_gelu_grad(g.data_ptr(), g_ld, pre.data_ptr(), O, gp.data_ptr(), O, R, O, _stream()),
-                       "mk_token_linear_gelu_grad")
-            g, g_ld = gp, O
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(x_shape, dtype=torch.bfloat16, device=g.device)
-            token_linear_fwd_raw(g, g_ld, token_linear_pack_raw(wimg, transpose=True), None, R, y=dx)
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            dw, db = token_linear_wgrad_raw(g, g_ld, xr, x_ld, R, O, I, has_bias and ctx.needs_input_grad[2])
-            dw = _toklin_param_grad(dw, w_dtype) if ctx.needs_input_grad[1] else None
-            db = _toklin_param_grad(db, b_dtype)
-        return dx, dw, db, None, (g_in if ctx.needs_input_grad[4] else None)
-
-
-class _TokenMLP(torch.autograd.Function):
-    """``fc2(gelu(fc1(x)))`` (+ an fp32 ``addend``) on bf16 rows: two packs and two GEMMs, ``fc1``'s with the GELU epilogue.  Saves
-    ``x``, the two weight images, ``pre`` and ``act``.  Backward, in order: ``fc2``'s weight gradient on ``act``; ``fc2``'s data
-    gradient with the GELU' epilogue on ``pre``, which is ``dpre``; ``fc1``'s weight gradient and data gradient from ``dpre``;
-    the addend's gradient is the incoming gradient."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, addend):
-        H, I = w1.shape
-        O = w2.shape[0]
-        shape = x.shape[:-1] + (O,)
-        xr, x_ld = _toklin_rows(x)
-        R = x.numel() // I
-        w1img, w2img = token_linear_pack_raw(w1), token_linear_pack_raw(w2)
-        need = any(ctx.needs_input_grad[:5])
-        act = torch.empty(R, H, dtype=torch.bfloat16, device=x.device)
-        pre = torch.empty(R, H, dtype=torch.bfloat16, device=x.device) if need else None
-        token_linear_fwd_raw(xr, x_ld, w1img, _toklin_bias(b1), R, act=act, pre=pre)
-        if addend is not None:
-            ar, a_ld = _toklin_rows(addend.detach().reshape(-1, O))
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
-            token_linear_fwd_raw(act, H, w2img, _toklin_bias(b2), R, addend=ar, addend_ld=a_ld, out_f32=out)
-        else:
-            out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
-            token_linear_fwd_raw(act, H, w2img, _toklin_bias(b2), R, y=out)
-        if need:
-            ctx.save_for_backward(xr, w1img, w2img, pre, act)
-        ctx.cfg = (x_ld, R, tuple(x.shape), w1.dtype, None if b1 is None else b1.dtype, w2.dtype, None if b2 is None else b2.dtype)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        if not ctx.saved_tensors:               # only the addend asks for a gradient: the incoming one
-            return None, None, None, None, None, g
-        xr, w1img, w2img, pre, act = ctx.saved_tensors
-        x_ld, R, x_shape, w1, b1, w2, b2 = ctx.cfg                 # the parameters' dtypes; None: no bias
-        H, I = w1img.shape
-        O = w2img.shape[0]
-        need = ctx.needs_input_grad
-        g_in = g
-        g, g_ld = _toklin_grad_rows(g, O)
-        dw2 = db2 = dw1 = db1 = dx = None
-        if need[3] or (b2 is not None and need[4]):
-            dw2, db2 = token_linear_wgrad_raw(g, g_ld, act, H, R, O, H, b2 is not None and need[4])
-            dw2 = _toklin_param_grad(dw2, w2) if need[3] else None
-            db2 = _toklin_param_grad(db2, b2)
-        if need[0] or need[1] or (b1 is not None and need[2]):
-            dpre = torch.empty(R, H, dtype=torch.bfloat16, device=g.device)
-            token_linear_fwd_raw(g, g_ld, token_linear_pack_raw(w2img, transpose=True), None, R, y=dpre, aux=pre, aux_ld=H)
-            if need[1] or (b1 is not None and need[2]):
-                dw1, db1 = token_linear_wgrad_raw(dpre, H, xr, x_ld, R, H, I, b1 is not None and need[2])
-                dw1 = _toklin_param_grad(dw1, w1) if need[1] else None
-                db1 = _toklin_param_grad(db1, b1)
-            if need[0]:
-                dx = torch.empty(x_shape, dtype=torch.bfloat16, device=g.device)
-                token_linear_fwd_raw(dpre, H, token_linear_pack_raw(w1img, transpose=True), None, R, y=dx)
-        return dx, dw1, db1, dw2, db2, (g_in if need[5] else None)
-
-
-def _toklin_addend_fused(addend, x, O):
-    """The kernels add an fp32 device addend of the output's shape in their epilogue; any other is added by torch."""
-    return (addend is not None and torch.is_tensor(addend) and addend.dtype == torch.float32 and addend.device == x.device
-            and tuple(addend.shape) == tuple(x.shape[:-1]) + (O,))
-
-
-# ----------------------------------------------------------------------------
-# the same linears on fp32 rows outside autocast (csrc/x3_toklinear.hip): fp32-accurate on the bf16x3 engine
-# ----------------------------------------------------------------------------
-# Opt-in by the rule of DESIGN section 19 until every row of tools/toklinear_fp32_bench.py has been measured faster than the
-# torch path (DESIGN section 30).
-TOKEN_LINEAR_FP32_DEFAULT = "torch"
-
-
-def token_linear_fp32_hip():
-    """``MK_TOKEN_LINEAR_FP32=hip|torch`` (read at call time): fp32 token-major linears outside autocast on the
-    ``mk_token_linear_x3_*`` kernels, or ``F.linear``.  Independent of ``MK_TOKEN_LINEAR``."""
-    return _hip_or_torch("MK_TOKEN_LINEAR_FP32", TOKEN_LINEAR_FP32_DEFAULT)
-
-
-def token_linear_x3_info():
-    """The tile of the kernels (no device needed): ``tr`` rows, ``tc`` columns, ``tk`` contraction step."""
-    t = (ctypes.c_int * 3)()
-    _lib.check(_lib.load().mk_token_linear_x3_info(ctypes.addressof(t)), "mk_token_linear_x3_info")
-    return dict(zip(("tr", "tc", "tk"), t))
-
-
-def _toklin_x3_rows(t):
-    """``t`` ``[..., L]`` fp32 as the x3 kernels take it, and its row stride: itself where its layout fits, else a contiguous copy."""
-    ld = _row_stride(t)
-    if ld is None or ld % 4 or ld < t.shape[-1] or t.data_ptr() % 16:
-        return t.contiguous(), t.shape[-1]
-    return t, ld
-
-
-def _toklin_x3_param_ok(p, shape, device):
-    return torch.is_tensor(p) and p.device == device and p.dtype == torch.float32 and tuple(p.shape) == shape
-
-
-def token_linear_x3_supported(x, weight, bias=None):
-    """True for what the ``mk_token_linear_x3_*`` kernels take as it is: ``x`` ``[..., I]`` fp32 on the device with bf16 device
-    autocast NOT active, its last axis contiguous, its rows at one common stride that is a multiple of 4 and at least ``I``,
-    16-byte aligned; ``I`` and ``O`` multiples of 4; ``weight`` ``[O, I]`` and ``bias`` ``[O]`` (or None) fp32 on the same device;
-    and the engine selected (``MK_SPECTRAL_GEMM=bf16x3``, the default: with ``f32`` the torch path is taken)."""
-    if SPECTRAL_GEMM != "bf16x3":
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() >= 1 and x.numel() > 0 and x.dtype == torch.float32
-            and torch.is_tensor(weight) and weight.dim() == 2):
-        return False
-    O, I = weight.shape
-    if x.shape[-1] != I or I % 4 or O % 4 or I < 4 or O < 4:
-        return False
-    if _autocast_dtype() == torch.bfloat16:
-        return False
-    if not _toklin_x3_param_ok(weight, (O, I), x.device) or (bias is not None and not _toklin_x3_param_ok(bias, (O,), x.device)):
-        return False
-    ld = _row_stride(x)
-    return ld is not None and ld % 4 == 0 and ld >= I and x.data_ptr() % 16 == 0
-
-
 def _toklin_x3_weight(weight):
-    """The weight as the kernels read it (no image is packed): itself, or a contiguous copy of a strided or misaligned one."""
+    """The weight as the x3 kernels read it (no image is packed): itself, or a contiguous copy of a strided or misaligned one."""
     w = weight.detach()
     return w if (w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.stride(0) >= w.shape[1] and w.data_ptr() % 16 == 0) else w.contiguous()
 
@@ -2901,120 +2715,208 @@ def token_linear_x3_wgrad_raw(dy, dy_ld, x, x_ld, R, O, I, want_db, slabs=0):
     return dw, db
 
 
-def _toklin_x3_grad_rows(g, O):
+# ---- the GEMM is where the arithmetics really differ: a packed bf16 image and one output per epilogue, against the fp32 weight as
+# ---- stored (k-major for the data gradient) and one output with a gelu flag.  Two short functions each, behind the description.
+def _toklin_bf16_gemm(x, x_ld, wimg, bias, R, out, gelu=False, want_pre=False, addend=None, addend_ld=0):
+    if addend is not None:
+        token_linear_fwd_raw(x, x_ld, wimg, bias, R, addend=addend, addend_ld=addend_ld, out_f32=out)
+    elif gelu:
+        pre = torch.empty(out.shape, dtype=torch.bfloat16, device=out.device) if want_pre else None
+        token_linear_fwd_raw(x, x_ld, wimg, bias, R, act=out, pre=pre)
+        return pre
+    else:
+        token_linear_fwd_raw(x, x_ld, wimg, bias, R, y=out)
+    return None
+
+
+def _toklin_x3_gemm(x, x_ld, w, bias, R, out, gelu=False, want_pre=False, addend=None, addend_ld=0):
+    O, I = w.shape
+    pre = torch.empty(R, O, dtype=torch.float32, device=out.device) if (gelu and want_pre) else None
+    token_linear_x3_fwd_raw(x, x_ld, w, bias, R, O, I, y=out, pre=pre, addend=addend, addend_ld=addend_ld, gelu=gelu)
+    return pre
+
+
+def _toklin_bf16_dgrad(g, g_ld, wimg, R, out, aux=None, aux_ld=0):
+    token_linear_fwd_raw(g, g_ld, token_linear_pack_raw(wimg, transpose=True), None, R, y=out, aux=aux, aux_ld=aux_ld)
+
+
+def _toklin_x3_dgrad(g, g_ld, w, R, out, aux=None, aux_ld=0):
+    O, I = w.shape
+    token_linear_x3_fwd_raw(g, g_ld, w, None, R, I, O, kmajor=True, y=out, aux=aux, aux_ld=aux_ld)
+
+
+def _toklin_bf16_gelu_grad(g, g_ld, pre, R, O):
+    """Rounded to bf16 as torch's gelu backward rounds it."""
+    gp = torch.empty(R, O, dtype=torch.bfloat16, device=g.device)
+    _lib.check(_lib.load().mk_token_linear_gelu_grad(g.data_ptr(), g_ld, pre.data_ptr(), O, gp.data_ptr(), O, R, O, _stream()),
+               "mk_token_linear_gelu_grad")
+    return gp
+
+
+def _toklin_x3_gelu_grad(g, g_ld, pre, R, O):
+    """One pointwise pass (``mk_bias_gelu_bwd``): it takes whole 8-element groups, which ``token_linear`` sees to."""
+    gc = g if g_ld == O else g.contiguous()
+    return gelu_backward(pre.view(1, 1, R * O), gc.view(1, 1, R * O))[0].view(R, O)
+
+
+_TOKLIN_BF16 = _LinearArith(torch.bfloat16, 8, (torch.float32, torch.bfloat16), False, lambda w: token_linear_pack_raw(w),
+                            _toklin_bf16_gemm, _toklin_bf16_dgrad, lambda *a: token_linear_wgrad_raw(*a), _toklin_bf16_gelu_grad)
+_TOKLIN_X3 = _LinearArith(torch.float32, 4, (torch.float32,), True, _toklin_x3_weight,
+                          _toklin_x3_gemm, _toklin_x3_dgrad, lambda *a: token_linear_x3_wgrad_raw(*a), _toklin_x3_gelu_grad)
+
+
+def _toklin_bias(bias):
+    return None if bias is None else bias.detach().float().contiguous()        # fp32 as it is; a bf16 bias exactly
+
+
+def _toklin_grad_rows(g, O, a):
+    """The incoming gradient as rows ``[R, O]`` in the arithmetic's dtype (for bf16: the gradient of the bf16 result that an fp32
+    sum was formed from)."""
     g = g.reshape(-1, O)
-    return _toklin_x3_rows(g if g.dtype == torch.float32 else g.float())
+    return _toklin_rows(g if g.dtype == a.dtype else g.to(a.dtype), a.unit)
 
 
-class _TokenLinearX3(torch.autograd.Function):
-    """``y = x W^T + b`` on fp32 rows, optionally through the exact GELU or added to an fp32 ``addend``: one GEMM on the bf16x3
-    engine.  Saves ``x``, the weight itself and, with ``gelu``, the pre-activation.  Backward: ``g gelu'(pre)`` first with
-    ``gelu``, the k-major GEMM on the stored weight for ``dx``, the slab kernel for ``dW`` and ``db``.  All fp32."""
+def _toklin_param_grad(g, dtype):
+    """The fp32 gradient in the parameter's dtype: a cast for a bf16 parameter, itself otherwise."""
+    return None if g is None else (g if g.dtype == dtype else g.to(dtype))
 
-    @staticmethod
+
+def _dtype_of(t):
+    return None if t is None else t.dtype
+
+
+def _token_linear_node(name, a, doc):
     def forward(ctx, x, weight, bias, gelu, addend):
         O, I = weight.shape
-        shape = x.shape[:-1] + (O,)
-        xr, x_ld = _toklin_x3_rows(x)
+        xr, x_ld = _toklin_rows(x, a.unit)
         R = x.numel() // I
-        w = _toklin_x3_weight(weight)
-        bf = None if bias is None else bias.detach().contiguous()
+        w = a.weight(weight)
+        bf = _toklin_bias(bias)
         need = any(ctx.needs_input_grad[:3])
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        pre = None
-        if addend is not None:
-            ar, a_ld = _toklin_x3_rows(addend.detach().reshape(-1, O))
-            token_linear_x3_fwd_raw(xr, x_ld, w, bf, R, O, I, y=out, addend=ar, addend_ld=a_ld)
-        else:
-            pre = torch.empty(R, O, dtype=torch.float32, device=x.device) if (gelu and need) else None
-            token_linear_x3_fwd_raw(xr, x_ld, w, bf, R, O, I, y=out, pre=pre, gelu=gelu)
+        ar, a_ld = (None, 0) if addend is None else _toklin_rows(addend.detach().reshape(-1, O), a.unit)
+        out = torch.empty(x.shape[:-1] + (O,), dtype=a.dtype if addend is None else torch.float32, device=x.device)
+        pre = a.gemm(xr, x_ld, w, bf, R, out, gelu, need, ar, a_ld)
         if need:
             ctx.save_for_backward(xr, w, pre)
-        ctx.cfg = (x_ld, R, tuple(x.shape), bias is not None)
+        ctx.cfg = (x_ld, R, tuple(x.shape), weight.dtype, _dtype_of(bias))
         return out
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         if not ctx.saved_tensors:               # only the addend asks for a gradient: the incoming one
             return None, None, None, None, g
         xr, w, pre = ctx.saved_tensors
-        x_ld, R, x_shape, has_bias = ctx.cfg
+        x_ld, R, x_shape, w_dtype, b_dtype = ctx.cfg
         O, I = w.shape
+        need = ctx.needs_input_grad
         g_in = g
-        g, g_ld = _toklin_x3_grad_rows(g, O)
-        if pre is not None:                     # through the GELU: g gelu'(pre), one pointwise pass (mk_bias_gelu_bwd)
-            gc = g if g_ld == O else g.contiguous()
-            g, g_ld = gelu_backward(pre.view(1, 1, R * O), gc.view(1, 1, R * O))[0].view(R, O), O
+        g, g_ld = _toklin_grad_rows(g, O, a)
+        if pre is not None:                     # through the GELU: g gelu'(pre)
+            g, g_ld = a.gelu_grad(g, g_ld, pre, R, O), O
         dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(x_shape, dtype=torch.float32, device=g.device)
-            token_linear_x3_fwd_raw(g, g_ld, w, None, R, I, O, kmajor=True, y=dx)
-        want_db = has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] or want_db:
-            dw, db = token_linear_x3_wgrad_raw(g, g_ld, xr, x_ld, R, O, I, want_db)
-            dw = dw if ctx.needs_input_grad[1] else None
-        return dx, dw, db, None, (g_in if ctx.needs_input_grad[4] else None)
+        if need[0]:
+            dx = torch.empty(x_shape, dtype=a.dtype, device=g.device)
+            a.dgrad(g, g_ld, w, R, dx)
+        want_db = b_dtype is not None and need[2]
+        if need[1] or want_db:
+            dw, db = a.wgrad(g, g_ld, xr, x_ld, R, O, I, want_db)
+            dw = _toklin_param_grad(dw, w_dtype) if need[1] else None
+            db = _toklin_param_grad(db, b_dtype)
+        return dx, dw, db, None, (g_in if need[4] else None)
+
+    return _node(name, doc, forward, backward)
 
 
-class _TokenMLPX3(torch.autograd.Function):
-    """``fc2(gelu(fc1(x)))`` (+ an fp32 ``addend``) on fp32 rows: two GEMMs on the bf16x3 engine, ``fc1``'s with the GELU epilogue
-    (and ``pre`` stored in grad mode only), ``fc2``'s with the addend.  Saves ``x``, the two weights themselves, ``pre`` and
-    ``act``.  Backward, in the order of ``_TokenMLP``: ``fc2``'s weight gradient on ``act``; ``fc2``'s data gradient from the
-    stored weight with the GELU' epilogue on ``pre``, which is ``dpre``; ``fc1``'s weight gradient and data gradient from ``dpre``;
-    the addend's gradient is the incoming gradient.  All fp32."""
+_TokenLinear = _token_linear_node("_TokenLinear", _TOKLIN_BF16, """``y = x W^T + b`` on bf16 rows, optionally through the exact GELU
+    or added to an fp32 ``addend``: one pack and one GEMM.  Saves ``x``, the bf16 weight image and, with ``gelu``, the
+    pre-activation.  Backward: ``g gelu'(pre)`` first with ``gelu``, a transposed pack and the GEMM again for ``dx``, the slab
+    kernel for ``dW`` and ``db`` (fp32, cast to a bf16 parameter's dtype).""")
+_TokenLinearX3 = _token_linear_node("_TokenLinearX3", _TOKLIN_X3, """The same on fp32 rows: one GEMM on the bf16x3 engine.  Saves
+    ``x``, the weight itself and, with ``gelu``, the pre-activation.  Backward: ``g gelu'(pre)`` first with ``gelu``, the k-major
+    GEMM on the stored weight for ``dx``, the slab kernel for ``dW`` and ``db``.  All fp32.""")
 
-    @staticmethod
+
+def _token_mlp_node(name, a, doc):
     def forward(ctx, x, w1, b1, w2, b2, addend):
         H, I = w1.shape
         O = w2.shape[0]
-        shape = x.shape[:-1] + (O,)
-        xr, x_ld = _toklin_x3_rows(x)
+        xr, x_ld = _toklin_rows(x, a.unit)
         R = x.numel() // I
-        w1c, w2c = _toklin_x3_weight(w1), _toklin_x3_weight(w2)
-        b1c = None if b1 is None else b1.detach().contiguous()
-        b2c = None if b2 is None else b2.detach().contiguous()
+        w1p, w2p = a.weight(w1), a.weight(w2)
         need = any(ctx.needs_input_grad[:5])
-        act = torch.empty(R, H, dtype=torch.float32, device=x.device)
-        pre = torch.empty(R, H, dtype=torch.float32, device=x.device) if need else None
-        token_linear_x3_fwd_raw(xr, x_ld, w1c, b1c, R, H, I, y=act, pre=pre, gelu=True)
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        if addend is not None:
-            ar, a_ld = _toklin_x3_rows(addend.detach().reshape(-1, O))
-            token_linear_x3_fwd_raw(act, H, w2c, b2c, R, O, H, y=out, addend=ar, addend_ld=a_ld)
-        else:
-            token_linear_x3_fwd_raw(act, H, w2c, b2c, R, O, H, y=out)
+        act = torch.empty(R, H, dtype=a.dtype, device=x.device)
+        pre = a.gemm(xr, x_ld, w1p, _toklin_bias(b1), R, act, True, need)
+        ar, a_ld = (None, 0) if addend is None else _toklin_rows(addend.detach().reshape(-1, O), a.unit)
+        out = torch.empty(x.shape[:-1] + (O,), dtype=a.dtype if addend is None else torch.float32, device=x.device)
+        a.gemm(act, H, w2p, _toklin_bias(b2), R, out, False, False, ar, a_ld)
         if need:
-            ctx.save_for_backward(xr, w1c, w2c, pre, act)
-        ctx.cfg = (x_ld, R, tuple(x.shape), b1 is not None, b2 is not None)
+            ctx.save_for_backward(xr, w1p, w2p, pre, act)
+        ctx.cfg = (x_ld, R, tuple(x.shape), w1.dtype, _dtype_of(b1), w2.dtype, _dtype_of(b2))
         return out
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         if not ctx.saved_tensors:               # only the addend asks for a gradient: the incoming one
             return None, None, None, None, None, g
-        xr, w1, w2, pre, act = ctx.saved_tensors
-        x_ld, R, x_shape, has_b1, has_b2 = ctx.cfg
-        H, I = w1.shape
-        O = w2.shape[0]
+        xr, w1p, w2p, pre, act = ctx.saved_tensors
+        x_ld, R, x_shape, w1, b1, w2, b2 = ctx.cfg                 # the parameters' dtypes; None: no bias
+        H, I = w1p.shape
+        O = w2p.shape[0]
         need = ctx.needs_input_grad
         g_in = g
-        g, g_ld = _toklin_x3_grad_rows(g, O)
+        g, g_ld = _toklin_grad_rows(g, O, a)
         dw2 = db2 = dw1 = db1 = dx = None
-        if need[3] or (has_b2 and need[4]):
-            dw2, db2 = token_linear_x3_wgrad_raw(g, g_ld, act, H, R, O, H, has_b2 and need[4])
-            dw2 = dw2 if need[3] else None
-        if need[0] or need[1] or (has_b1 and need[2]):
-            dpre = torch.empty(R, H, dtype=torch.float32, device=g.device)
-            token_linear_x3_fwd_raw(g, g_ld, w2, None, R, H, O, kmajor=True, y=dpre, aux=pre, aux_ld=H)
-            if need[1] or (has_b1 and need[2]):
-                dw1, db1 = token_linear_x3_wgrad_raw(dpre, H, xr, x_ld, R, H, I, has_b1 and need[2])
-                dw1 = dw1 if need[1] else None
+        if need[3] or (b2 is not None and need[4]):
+            dw2, db2 = a.wgrad(g, g_ld, act, H, R, O, H, b2 is not None and need[4])
+            dw2 = _toklin_param_grad(dw2, w2) if need[3] else None
+            db2 = _toklin_param_grad(db2, b2)
+        if need[0] or need[1] or (b1 is not None and need[2]):
+            dpre = torch.empty(R, H, dtype=a.dtype, device=g.device)
+            a.dgrad(g, g_ld, w2p, R, dpre, aux=pre, aux_ld=H)
+            if need[1] or (b1 is not None and need[2]):
+                dw1, db1 = a.wgrad(dpre, H, xr, x_ld, R, H, I, b1 is not None and need[2])
+                dw1 = _toklin_param_grad(dw1, w1) if need[1] else None
+                db1 = _toklin_param_grad(db1, b1)
             if need[0]:
-                dx = torch.empty(x_shape, dtype=torch.float32, device=g.device)
-                token_linear_x3_fwd_raw(dpre, H, w1, None, R, I, H, kmajor=True, y=dx)
+                dx = torch.empty(x_shape, dtype=a.dtype, device=g.device)
+                a.dgrad(dpre, H, w1p, R, dx)
         return dx, dw1, db1, dw2, db2, (g_in if need[5] else None)
+
+    return _node(name, doc, forward, backward)
+
+
+_TokenMLP = _token_mlp_node("_TokenMLP", _TOKLIN_BF16, """``fc2(gelu(fc1(x)))`` (+ an fp32 ``addend``) on bf16 rows: two packs and two
+    GEMMs, ``fc1``'s with the GELU epilogue (``pre`` stored in grad mode only), ``fc2``'s with the addend.  Saves ``x``, the two
+    weight images, ``pre`` and ``act``.  Backward, in order: ``fc2``'s weight gradient on ``act``; ``fc2``'s data gradient with the
+    GELU' epilogue on ``pre``, which is ``dpre``; ``fc1``'s weight gradient and data gradient from ``dpre``; the addend's gradient
+    is the incoming gradient.""")
+_TokenMLPX3 = _token_mlp_node("_TokenMLPX3", _TOKLIN_X3, """``_TokenMLP`` on fp32 rows: two GEMMs on the bf16x3 engine.  Saves ``x``,
+    the two weights themselves, ``pre`` and ``act``; the data gradients are k-major GEMMs on the stored weights.  All fp32.""")
+
+
+def _toklin_addend_fused(addend, x, O):
+    """The kernels add an fp32 device addend of the output's shape in their epilogue; any other is added by torch."""
+    return (addend is not None and torch.is_tensor(addend) and addend.dtype == torch.float32 and addend.device == x.device
+            and tuple(addend.shape) == tuple(x.shape[:-1]) + (O,))
+
+
+def _toklin_takes(a, x, weight, bias, second):
+    """The kernels of arithmetic ``a`` take this linear and, for the MLP, the ``second = (w2, b2)`` behind it."""
+    if not _toklin_supported(a, x, weight, bias):
+        return False
+    if second is None:
+        return True
+    w2, b2 = second
+    return (torch.is_tensor(w2) and w2.dim() == 2 and w2.shape[1] == weight.shape[0] and w2.shape[0] % a.unit == 0
+            and _toklin_param_ok(a, w2, tuple(w2.shape), x.device) and (b2 is None or _toklin_param_ok(a, b2, (w2.shape[0],), x.device)))
+
+
+def _toklin_arith(x, weight, bias, second=None):
+    """The arithmetic whose knob is at ``hip`` and whose kernels take this: bf16 first, then fp32; None is the torch path."""
+    fp32_hip = token_linear_fp32_hip()
+    if token_linear_hip() and _toklin_takes(_TOKLIN_BF16, x, weight, bias, second):
+        return _TOKLIN_BF16
+    if fp32_hip and _toklin_takes(_TOKLIN_X3, x, weight, bias, second):
+        return _TOKLIN_X3
+    return None
 
 
 def token_linear(x, weight, bias=None, gelu=False, addend=None):
@@ -3025,22 +2927,17 @@ def token_linear(x, weight, bias=None, gelu=False, addend=None):
     take ``F.linear`` / ``F.gelu``."""
     if gelu and addend is not None:
         raise ValueError("token_linear: gelu and addend cannot be combined")
-    fp32_hip = token_linear_fp32_hip()
-    if token_linear_hip() and token_linear_supported(x, weight, bias):
-        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+    a = _toklin_arith(x, weight, bias)
+    if a is not None:
+        node = _TokenLinearX3 if a.x3 else _TokenLinear
+        xa = x if x.dtype == a.dtype else x.to(a.dtype)
         if addend is None:
-            return _TokenLinear.apply(xb, weight, bias, bool(gelu), None)
+            if gelu and a.x3 and (x.numel() // x.shape[-1] * weight.shape[0]) % 8:     # the GELU-gradient pass takes whole 8-element groups
+                return torch.nn.functional.gelu(node.apply(xa, weight, bias, False, None))
+            return node.apply(xa, weight, bias, bool(gelu), None)
         if _toklin_addend_fused(addend, x, weight.shape[0]):
-            return _TokenLinear.apply(xb, weight, bias, False, addend)
-        return addend + _TokenLinear.apply(xb, weight, bias, False, None)
-    if fp32_hip and token_linear_x3_supported(x, weight, bias):
-        if addend is None:
-            if gelu and (x.numel() // x.shape[-1] * weight.shape[0]) % 8:      # the GELU-gradient pass takes whole 8-element groups
-                return torch.nn.functional.gelu(_TokenLinearX3.apply(x, weight, bias, False, None))
-            return _TokenLinearX3.apply(x, weight, bias, bool(gelu), None)
-        if _toklin_addend_fused(addend, x, weight.shape[0]):
-            return _TokenLinearX3.apply(x, weight, bias, False, addend)
-        return addend + _TokenLinearX3.apply(x, weight, bias, False, None)
+            return node.apply(xa, weight, bias, False, addend)
+        return addend + node.apply(xa, weight, bias, False, None)
     y = torch.nn.functional.linear(x, weight, bias)
     if gelu:
         y = torch.nn.functional.gelu(y)
@@ -3051,20 +2948,13 @@ def token_mlp(x, w1, b1, w2, b2, addend=None):
     """``F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)`` (``addend +`` it with ``addend``) as one autograd function on the
     ``mk_token_linear_*`` kernels, with the GELU in ``fc1``'s epilogue, the addend in ``fc2``'s and the GELU gradient in the
     epilogue of ``fc2``'s data gradient.  Same dispatch as ``token_linear``: the bf16 branch, then the fp32 one, then torch."""
-    fp32_hip = token_linear_fp32_hip()
-    if (token_linear_hip() and token_linear_supported(x, w1, b1) and torch.is_tensor(w2) and w2.dim() == 2
-            and w2.shape[1] == w1.shape[0] and w2.shape[0] % 8 == 0 and _toklin_param_ok(w2, tuple(w2.shape), x.device)
-            and (b2 is None or _toklin_param_ok(b2, (w2.shape[0],), x.device))):
-        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+    a = _toklin_arith(x, w1, b1, second=(w2, b2))
+    if a is not None:
+        node = _TokenMLPX3 if a.x3 else _TokenMLP
+        xa = x if x.dtype == a.dtype else x.to(a.dtype)
         if addend is None or _toklin_addend_fused(addend, x, w2.shape[0]):
-            return _TokenMLP.apply(xb, w1, b1, w2, b2, addend)
-        return addend + _TokenMLP.apply(xb, w1, b1, w2, b2, None)
-    if (fp32_hip and token_linear_x3_supported(x, w1, b1) and torch.is_tensor(w2) and w2.dim() == 2
-            and w2.shape[1] == w1.shape[0] and w2.shape[0] % 4 == 0 and _toklin_x3_param_ok(w2, tuple(w2.shape), x.device)
-            and (b2 is None or _toklin_x3_param_ok(b2, (w2.shape[0],), x.device))):
-        if addend is None or _toklin_addend_fused(addend, x, w2.shape[0]):
-            return _TokenMLPX3.apply(x, w1, b1, w2, b2, addend)
-        return addend + _TokenMLPX3.apply(x, w1, b1, w2, b2, None)
+            return node.apply(xa, w1, b1, w2, b2, addend)
+        return addend + node.apply(xa, w1, b1, w2, b2, None)
     F = torch.nn.functional
     y = F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
     return y if addend is None else addend + y
@@ -3208,133 +3098,62 @@ def unpatchify(tok, patch, out_chans, img_shape, order, dtype=None):
     return _unpatchify_torch(tok, patch, int(out_chans), H, W, order).to(dtype)
 
 
+def _patch_embed_supported(a, img, weight, bias):
+    if a.x3 and SPECTRAL_GEMM != "bf16x3":
+        return False
+    if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.numel() > 0 and torch.is_tensor(weight) and weight.dim() == 4):
+        return False
+    E, C, p0, p1 = weight.shape
+    F = C * p0 * p1
+    if img.shape[1] != C or img.shape[2] % p0 or img.shape[3] % p1 or F % a.unit or E % a.unit:
+        return False
+    lowp = _autocast_dtype() == torch.bfloat16      # the convolution would take the image in bf16
+    if a.x3:
+        if img.dtype != torch.float32 or lowp:
+            return False
+    elif img.dtype not in _PATCH_DTYPES or not (lowp or all(t.dtype == torch.bfloat16 for t in (img, weight, bias) if t is not None)):
+        return False
+    return _toklin_param_ok(a, weight, (E, C, p0, p1), img.device) and (bias is None or _toklin_param_ok(a, bias, (E,), img.device))
+
+
 def patch_embed_supported(img, weight, bias=None):
     """True for what ``_PatchEmbed`` takes: ``img`` ``[B, C, H, W]`` on the device, fp32 or bf16 under bf16 device autocast -- which
     takes it in bf16 as the convolution does -- or, without autocast, bf16 with bf16 parameters (``nn.Conv2d`` refuses mixed dtypes
     there, and so does this); ``weight`` ``[E, C, p0, p1]`` with a patch that divides the grid, ``C p0 p1`` and ``E`` multiples of 8,
     ``weight`` and ``bias`` ``[E]`` (or None) fp32 or bf16 on the same device.  Independent of ``MK_TOKEN_LINEAR``."""
-    if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.numel() > 0 and torch.is_tensor(weight) and weight.dim() == 4):
-        return False
-    E, C, p0, p1 = weight.shape
-    F = C * p0 * p1
-    if img.shape[1] != C or img.shape[2] % p0 or img.shape[3] % p1 or F % 8 or E % 8:
-        return False
-    if img.dtype not in _PATCH_DTYPES:
-        return False
-    if _autocast_dtype() != torch.bfloat16 and not all(t.dtype == torch.bfloat16 for t in (img, weight, bias) if t is not None):
-        return False
-    return _toklin_param_ok(weight, (E, C, p0, p1), img.device) and (bias is None or _toklin_param_ok(bias, (E,), img.device))
-
-
-class _PatchEmbed(torch.autograd.Function):
-    """A non-overlapping strided convolution as one GEMM on patch rows: ``mk_patchify`` (order 0, to bf16: the autocast cast of the
-    image in the same pass), the weight's bf16 image, ``mk_token_linear_fwd`` with the fp32 bias.  With ``pos`` (fp32 ``[N, E]``)
-    one GEMM launch per sample with ``pos`` as its addend: ``pos + float(bf16(acc + bias))``, fp32.  Saves the patch rows and the
-    weight image.  Backward: the slab kernel for ``dW`` / ``db``; the batch sum of the gradient for ``pos``; for the image, where it
-    asks, a transposed pack, the GEMM to bf16 rows and ``mk_unpatchify`` into the image's dtype."""
-
-    @staticmethod
-    def forward(ctx, img, weight, bias, pos):
-        B, C, H, W = img.shape
-        E, _, p0, p1 = weight.shape
-        _, _, hp, wp, F = _patch_geometry(C, H, W, (p0, p1))
-        N = hp * wp
-        rows = patchify_raw(img.detach().contiguous(), torch.empty(B * N, F, dtype=torch.bfloat16, device=img.device), (p0, p1), 0)
-        wimg = token_linear_pack_raw(weight.detach().reshape(E, F))
-        bf = _toklin_bias(bias)
-        if pos is not None:
-            pr, p_ld = _toklin_rows(pos.detach().reshape(N, E))
-            out = torch.empty(B, N, E, dtype=torch.float32, device=img.device)
-            for b in range(B):
-                token_linear_fwd_raw(rows[b * N:(b + 1) * N], F, wimg, bf, N, addend=pr, addend_ld=p_ld, out_f32=out[b])
-        else:
-            out = torch.empty(B, N, E, dtype=torch.bfloat16, device=img.device)
-            token_linear_fwd_raw(rows, F, wimg, bf, B * N, y=out)
-        if any(ctx.needs_input_grad[:3]):
-            ctx.save_for_backward(rows, wimg)
-        ctx.cfg = (tuple(img.shape), img.dtype, tuple(weight.shape), weight.dtype, None if bias is None else bias.dtype,
-                   None if pos is None else tuple(pos.shape))
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        img_shape, img_dtype, w_shape, w_dtype, b_dtype, pos_shape = ctx.cfg
-        need = ctx.needs_input_grad
-        dpos = g.sum(0).reshape(pos_shape) if (pos_shape is not None and need[3]) else None
-        if not ctx.saved_tensors:
-            return None, None, None, dpos
-        rows, wimg = ctx.saved_tensors
-        E, F = wimg.shape
-        R = rows.shape[0]
-        gr, g_ld = _toklin_grad_rows(g, E)
-        dx = dw = db = None
-        want_db = b_dtype is not None and need[2]
-        if need[1] or want_db:
-            dw, db = token_linear_wgrad_raw(gr, g_ld, rows, F, R, E, F, want_db)
-            dw = _toklin_param_grad(dw, w_dtype).view(w_shape) if need[1] else None
-            db = _toklin_param_grad(db, b_dtype)
-        if need[0]:
-            dxr = torch.empty(R, F, dtype=torch.bfloat16, device=g.device)
-            token_linear_fwd_raw(gr, g_ld, token_linear_pack_raw(wimg, transpose=True), None, R, y=dxr)
-            dx = unpatchify_raw(dxr, torch.empty(img_shape, dtype=img_dtype, device=g.device), w_shape[2:], 0)
-        return dx, dw, db, dpos
-
-
-def _patch_pos_fused(pos, img, N, E):
-    return (torch.is_tensor(pos) and pos.dtype == torch.float32 and pos.device == img.device
-            and tuple(pos.shape) in ((1, N, E), (N, E)))
+    return _patch_embed_supported(_TOKLIN_BF16, img, weight, bias)
 
 
 def patch_embed_x3_supported(img, weight, bias=None):
     """True for what ``_PatchEmbedX3`` takes: ``img`` ``[B, C, H, W]`` fp32 on the device with bf16 device autocast NOT active,
     ``weight`` ``[E, C, p0, p1]`` with a patch that divides the grid, ``C p0 p1`` and ``E`` multiples of 4, ``weight`` and ``bias``
     ``[E]`` (or None) fp32 on the same device, and the bf16x3 engine selected (``MK_SPECTRAL_GEMM``)."""
-    if SPECTRAL_GEMM != "bf16x3":
-        return False
-    if not (torch.is_tensor(img) and img.is_cuda and img.dim() == 4 and img.numel() > 0 and img.dtype == torch.float32
-            and torch.is_tensor(weight) and weight.dim() == 4):
-        return False
-    E, C, p0, p1 = weight.shape
-    F = C * p0 * p1
-    if img.shape[1] != C or img.shape[2] % p0 or img.shape[3] % p1 or F % 4 or E % 4:
-        return False
-    if _autocast_dtype() == torch.bfloat16:
-        return False
-    return _toklin_x3_param_ok(weight, (E, C, p0, p1), img.device) and (bias is None or _toklin_x3_param_ok(bias, (E,), img.device))
+    return _patch_embed_supported(_TOKLIN_X3, img, weight, bias)
 
 
-class _PatchEmbedX3(torch.autograd.Function):
-    """``_PatchEmbed`` on fp32 images outside autocast: ``mk_patchify`` (order 0) to fp32 rows, then ``mk_token_linear_x3_fwd`` on
-    the weight's ``[E, F]`` view with the bias; with ``pos`` (fp32 ``[N, E]``) one GEMM launch per sample with ``pos`` as its
-    addend.  Saves the patch rows and the weight view.  Backward: the x3 slab kernel for ``dW`` / ``db``; the batch sum of the
-    gradient for ``pos``; for the image, where it asks, the k-major GEMM on the stored weight and ``mk_unpatchify``.  All fp32."""
-
-    @staticmethod
+def _patch_embed_node(name, a, doc):
     def forward(ctx, img, weight, bias, pos):
         B, C, H, W = img.shape
         E, _, p0, p1 = weight.shape
         _, _, hp, wp, F = _patch_geometry(C, H, W, (p0, p1))
         N = hp * wp
-        rows = patchify_raw(img.detach().contiguous(), torch.empty(B * N, F, dtype=torch.float32, device=img.device), (p0, p1), 0)
-        w = _toklin_x3_weight(weight.detach().reshape(E, F))
-        bf = None if bias is None else bias.detach().contiguous()
-        out = torch.empty(B, N, E, dtype=torch.float32, device=img.device)
+        rows = patchify_raw(img.detach().contiguous(), torch.empty(B * N, F, dtype=a.dtype, device=img.device), (p0, p1), 0)
+        w = a.weight(weight.detach().reshape(E, F))
+        bf = _toklin_bias(bias)
+        out = torch.empty(B, N, E, dtype=a.dtype if pos is None else torch.float32, device=img.device)
         if pos is not None:
-            pr, p_ld = _toklin_x3_rows(pos.detach().reshape(N, E))
+            pr, p_ld = _toklin_rows(pos.detach().reshape(N, E), a.unit)
             for b in range(B):
-                token_linear_x3_fwd_raw(rows[b * N:(b + 1) * N], F, w, bf, N, E, F, y=out[b], addend=pr, addend_ld=p_ld)
+                a.gemm(rows[b * N:(b + 1) * N], F, w, bf, N, out[b], False, False, pr, p_ld)
         else:
-            token_linear_x3_fwd_raw(rows, F, w, bf, B * N, E, F, y=out)
+            a.gemm(rows, F, w, bf, B * N, out)
         if any(ctx.needs_input_grad[:3]):
             ctx.save_for_backward(rows, w)
-        ctx.cfg = (tuple(img.shape), tuple(weight.shape), bias is not None, None if pos is None else tuple(pos.shape))
+        ctx.cfg = (tuple(img.shape), img.dtype, tuple(weight.shape), weight.dtype, _dtype_of(bias), None if pos is None else tuple(pos.shape))
         return out
 
-    @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        img_shape, w_shape, has_bias, pos_shape = ctx.cfg
+        img_shape, img_dtype, w_shape, w_dtype, b_dtype, pos_shape = ctx.cfg
         need = ctx.needs_input_grad
         dpos = g.sum(0).reshape(pos_shape) if (pos_shape is not None and need[3]) else None
         if not ctx.saved_tensors:
@@ -3342,17 +3161,36 @@ class _PatchEmbedX3(torch.autograd.Function):
         rows, w = ctx.saved_tensors
         E, F = w.shape
         R = rows.shape[0]
-        gr, g_ld = _toklin_x3_grad_rows(g, E)
+        gr, g_ld = _toklin_grad_rows(g, E, a)
         dx = dw = db = None
-        want_db = has_bias and need[2]
+        want_db = b_dtype is not None and need[2]
         if need[1] or want_db:
-            dw, db = token_linear_x3_wgrad_raw(gr, g_ld, rows, F, R, E, F, want_db)
-            dw = dw.view(w_shape) if need[1] else None
+            dw, db = a.wgrad(gr, g_ld, rows, F, R, E, F, want_db)
+            dw = _toklin_param_grad(dw, w_dtype).view(w_shape) if need[1] else None
+            db = _toklin_param_grad(db, b_dtype)
         if need[0]:
-            dxr = torch.empty(R, F, dtype=torch.float32, device=g.device)
-            token_linear_x3_fwd_raw(gr, g_ld, w, None, R, F, E, kmajor=True, y=dxr)
-            dx = unpatchify_raw(dxr, torch.empty(img_shape, dtype=torch.float32, device=g.device), w_shape[2:], 0)
+            dxr = torch.empty(R, F, dtype=a.dtype, device=g.device)
+            a.dgrad(gr, g_ld, w, R, dxr)
+            dx = unpatchify_raw(dxr, torch.empty(img_shape, dtype=img_dtype, device=g.device), w_shape[2:], 0)
         return dx, dw, db, dpos
+
+    return _node(name, doc, forward, backward)
+
+
+_PatchEmbed = _patch_embed_node("_PatchEmbed", _TOKLIN_BF16, """A non-overlapping strided convolution as one GEMM on patch rows:
+    ``mk_patchify`` (order 0, to bf16: the autocast cast of the image in the same pass), the weight's bf16 image,
+    ``mk_token_linear_fwd`` with the fp32 bias.  With ``pos`` (fp32 ``[N, E]``) one GEMM launch per sample with ``pos`` as its
+    addend: ``pos + float(bf16(acc + bias))``, fp32.  Saves the patch rows and the weight image.  Backward: the slab kernel for
+    ``dW`` / ``db``; the batch sum of the gradient for ``pos``; for the image, where it asks, a transposed pack, the GEMM to bf16
+    rows and ``mk_unpatchify`` into the image's dtype.""")
+_PatchEmbedX3 = _patch_embed_node("_PatchEmbedX3", _TOKLIN_X3, """``_PatchEmbed`` on fp32 images outside autocast: fp32 patch rows,
+    then ``mk_token_linear_x3_fwd`` on the weight's ``[E, F]`` view with the bias.  Saves the patch rows and the weight view; the
+    image's gradient is the k-major GEMM on the stored weight and ``mk_unpatchify``.  All fp32.""")
+
+
+def _patch_pos_fused(pos, img, N, E):
+    return (torch.is_tensor(pos) and pos.dtype == torch.float32 and pos.device == img.device
+            and tuple(pos.shape) in ((1, N, E), (N, E)))
 
 
 def patch_embed(img, weight, bias=None, pos=None):
@@ -3364,17 +3202,16 @@ def patch_embed(img, weight, bias=None, pos=None):
     ``patch_embed_x3_supported`` takes, is the same node on fp32 rows and the ``mk_token_linear_x3_*`` kernels: an fp32 result.
     Everything else takes the torch expression."""
     patch, fp32_hip = patch_hip(), token_linear_fp32_hip()
-    if patch and patch_embed_supported(img, weight, bias):
+    node = None
+    if patch and _patch_embed_supported(_TOKLIN_BF16, img, weight, bias):
+        node = _PatchEmbed
+    elif patch and fp32_hip and _patch_embed_supported(_TOKLIN_X3, img, weight, bias):
+        node = _PatchEmbedX3
+    if node is not None:
         E, _, p0, p1 = weight.shape
         N = (img.shape[2] // p0) * (img.shape[3] // p1)
         if pos is None or _patch_pos_fused(pos, img, N, E):
-            return _PatchEmbed.apply(img, weight, bias, pos)
-        return _PatchEmbed.apply(img, weight, bias, None) + pos
-    if patch and fp32_hip and patch_embed_x3_supported(img, weight, bias):
-        E, _, p0, p1 = weight.shape
-        N = (img.shape[2] // p0) * (img.shape[3] // p1)
-        if pos is None or _patch_pos_fused(pos, img, N, E):
-            return _PatchEmbedX3.apply(img, weight, bias, pos)
-        return _PatchEmbedX3.apply(img, weight, bias, None) + pos
+            return node.apply(img, weight, bias, pos)
+        return node.apply(img, weight, bias, None) + pos
     y = torch.nn.functional.conv2d(img, weight, bias, stride=tuple(weight.shape[2:])).flatten(2).transpose(1, 2)
     return y if pos is None else y + pos

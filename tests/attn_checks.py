@@ -144,3 +144,44 @@ def make_inputs(N, D, in_scale=1.0, seed=0, lead=(), Nk=None):
     v = torch.randn(*lead, Nk, D, generator=g).bfloat16()
     go = torch.randn(*lead, N, D, generator=g).bfloat16()
     return q, k, v, go
+
+
+def check_refusal_texts(lib, prefix, max_head, unit):
+    """Every refusal of the four entry points ``<prefix>_fwd / _bwd_delta / _bwd_dkv / _bwd_dq`` (``mk_attn`` with head sizes to
+    128 and strides in units of 8, ``mk_attn_x3`` with 64 and 4): code 1 and the exact text of ``mk_last_error()``, before any
+    launch -- no device is touched.  Returns the number of refusals checked."""
+    import ctypes
+    P = 4096
+    good = [64 * 40, 40, 40 * 3] * 6
+
+    def call(entry, D=32, N=5, first=P, strides=good, lse=P, delta=P):
+        st = None if strides is None else (ctypes.c_longlong * len(strides))(*strides)
+        sp = None if st is None else ctypes.addressof(st)
+        fn = getattr(lib, f"{prefix}_{entry}")
+        if entry == "fwd":
+            rc = fn(first, P, P, P, lse, 1, 2, N, N, D, sp, 1.0, None)
+        elif entry == "bwd_delta":
+            rc = fn(first, P, delta, 1, 2, N, D, sp, None)
+        elif entry == "bwd_dkv":
+            rc = fn(first, P, P, P, lse, delta, P, P, 1, 2, N, N, D, sp, 1.0, None)
+        else:
+            rc = fn(first, P, P, P, lse, delta, P, 1, 2, N, N, D, sp, 1.0, None)
+        return rc, lib.mk_last_error().decode()
+
+    head = f"head size must be a multiple of 16 in 16 ... {max_head}"
+    shared = [(dict(D=24), head), (dict(D=max_head + 16), head), (dict(N=0), "bad sizes"), (dict(first=None), "null pointer"),
+              (dict(first=P + 8), "operand not 16-byte aligned"),
+              (dict(strides=[64 * 40, 40, 40 * 3 + unit // 2] + good[3:]), f"strides must be non-negative multiples of {unit} elements"),
+              (dict(strides=[64, 40, 16] + good[3:]), "token stride smaller than the head size"), (dict(strides=None), "null strides")]
+    both = "lse / delta null or not 4-byte aligned"
+    own = dict(fwd=[(dict(lse=P + 2), "lse not 4-byte aligned")],
+               bwd_delta=[(dict(delta=None), "delta null or not 4-byte aligned"), (dict(delta=P + 2), "delta null or not 4-byte aligned")],
+               bwd_dkv=[(dict(lse=None), both), (dict(delta=None), both), (dict(lse=P + 2), both), (dict(delta=P + 2), both)])
+    own["bwd_dq"] = own["bwd_dkv"]
+    n = 0
+    for entry, cases in own.items():
+        for kw, text in shared + cases:
+            rc, msg = call(entry, **kw)
+            assert (rc, msg) == (1, f"{prefix}_{entry}: {text}"), (entry, kw, rc, msg)
+            n += 1
+    return n

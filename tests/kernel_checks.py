@@ -309,3 +309,15 @@ def x3_elementwise(y, ref64, mag64, c=X3_C, slack64=None, what=""):
                              f"ref = {float(ref[idx])!r}, mag = {float(mag[idx]):.3e}; {int((ratio > c).sum())} of {ratio.numel()} "
                              f"elements exceed the limit")
     return worst
+
+
+def node_kinds(y):
+    """The class names of every autograd node behind ``y``: which of the package's functions, and which of torch's, a graph holds."""
+    seen, stack = set(), [y.grad_fn]
+    while stack:
+        fn = stack.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)
+        stack += [f for f, _ in fn.next_functions]
+    return [type(f).__name__ for f in seen]

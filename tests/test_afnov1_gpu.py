@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import kernel_checks as kc
+from kernel_checks import node_kinds as _graph_kinds
 from test_afno_gpu import CHAIN_CASES, EDGE, GRAD_TOL, TOL, _count_calls
 from test_afnov1_cpu import (LAM, block_chain64, build, check_against_fixture, make_filter, ref, window_chain64,  # noqa: F401
                              window_matrix)
@@ -278,17 +279,6 @@ def test_net_on_the_device_against_the_reference_run(dev, monkeypatch, ref):  # 
     calls = _count_calls(monkeypatch, "spec_block_mlp")
     check_against_fixture(ref, "net", net, dev, TOL, GRAD_TOL, "device fp32")
     assert len(calls) == 2, "one fused filter per block"
-
-
-def _graph_kinds(y):
-    seen, stack = set(), [y.grad_fn]
-    while stack:
-        fn = stack.pop()
-        if fn is None or fn in seen:
-            continue
-        seen.add(fn)
-        stack += [f for f, _ in fn.next_functions]
-    return [type(f).__name__ for f in seen]
 
 
 @pytest.mark.parametrize("token_kernels", [False, True], ids=["torch-norm-linear", "hip-norm-linear"])

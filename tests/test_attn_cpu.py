@@ -136,3 +136,8 @@ def test_info_and_refusals_without_a_device():
         assert lib.mk_attn_bwd_delta(ptr, P, P, 1, 2, 5, D, sp, None) == 1
         assert lib.mk_attn_bwd_dkv(ptr, P, P, P, P, P, P, P, 1, 2, 5, 5, D, sp, 1.0, None) == 1
         assert lib.mk_attn_bwd_dq(ptr, P, P, P, P, P, P, 1, 2, 5, 5, D, sp, 1.0, None) == 1
+
+
+def test_every_refusal_keeps_its_words_without_a_device():
+    from makani_amd import _lib
+    assert ac.check_refusal_texts(_lib.load(), "mk_attn", 128, 8) == 4 * 8 + 1 + 2 + 4 + 4

@@ -13,6 +13,8 @@ import pytest
 import torch
 import torch.nn as nn
 
+from kernel_checks import node_kinds
+
 pytestmark = pytest.mark.gpu
 
 C, HEADS, B, N = 64, 4, 2, 200
@@ -84,14 +86,7 @@ def test_hip_path_runs_the_kernels(dev, monkeypatch):
     mod = mod.to(dev)
     with torch.autocast("cuda", dtype=torch.bfloat16):
         y = mod(torch.randn(shape, device=dev))
-    seen, stack = set(), [y.grad_fn]
-    while stack:
-        fn = stack.pop()
-        if fn is None or fn in seen:
-            continue
-        seen.add(fn)
-        stack += [f for f, _ in fn.next_functions]
-    kinds = [type(f).__name__ for f in seen]
+    kinds = node_kinds(y)
     assert sum(k.startswith("_TokenLinear") for k in kinds) == 2 and sum(k.startswith("_TokenMLP") for k in kinds) == 1
     assert not any("Addmm" in k or "MmBackward" in k for k in kinds), kinds
 

@@ -113,6 +113,11 @@ def test_info_and_refusals_without_a_device():
     assert lib.mk_attn_x3_bwd_dq(P, P, P, P, None, P, P, 1, 2, 5, 5, 32, ctypes.addressof(st), 1.0, None) == 1     # null lse
 
 
+def test_every_refusal_keeps_its_words_without_a_device():
+    from makani_amd import _lib
+    assert ac.check_refusal_texts(_lib.load(), "mk_attn_x3", 64, 4) == 4 * 8 + 1 + 2 + 4 + 4
+
+
 @pytest.mark.parametrize("knob", ["hip", "torch"])
 def test_cpu_tensors_take_the_torch_call_bit_for_bit(knob, monkeypatch):
     from makani_amd import ops

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 import kernel_checks as kc
+from kernel_checks import node_kinds as _node_kinds
 
 pytestmark = pytest.mark.gpu
 
@@ -64,17 +65,6 @@ def _reference(mod, x, gen):
     g = torch.randn(y64.shape, generator=gen)
     want = [y64.detach()] + list(torch.autograd.grad(y64, [x64] + list(ref_mod.parameters()), g.double(), allow_unused=True))
     return g, want
-
-
-def _node_kinds(y):
-    seen, stack = set(), [y.grad_fn]
-    while stack:
-        fn = stack.pop()
-        if fn is None or fn in seen:
-            continue
-        seen.add(fn)
-        stack += [f for f, _ in fn.next_functions]
-    return [type(f).__name__ for f in seen]
 
 
 CASES = [("linear", "torch"), ("linear_nobias", "torch"), ("mlp", "torch"), ("afnov1_mlp", "torch"), ("block", "torch"), ("vit", "torch"),
