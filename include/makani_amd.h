@@ -296,6 +296,24 @@ int mk_diag_fwd(const float* x, const float* w, float* y, int batch, int cin, in
 int mk_diag_dgrad(const float* gy, const float* w, float* gx, int batch, int cin, int cout, long long P, void* stream);
 int mk_diag_wgrad(const float* x, const float* gy, float* gw, int batch, int cin, int cout, long long P, void* stream);
 
+/* ---- diagonal spectral filter on the private spectrum -------------------------------------------
+ * The same contraction without the layout round trip: x / y / gx / gy are the private spectrum [lloc][mloc][batch * chan]
+ * complex64 (channel contiguous, as for dhconv), w / gw the parameter as stored, [cin][cout][lloc][mloc] complex64.
+ * dense = 0: entries with global l_off + l < m_off + m hold no data -- x / gy / w there are never read, y / gx there are not
+ * written, gw there is an exact zero written by the kernel.  dense = 1 (the planar pair): every entry is data.
+ * Exact sequential fp32 fma chains in the order of mk_diag_*; one writer per element: the same bits every run and for every
+ * cut into shards.  Operands 8-byte aligned (16-byte weight accesses where mloc is even and w is 16-byte aligned);
+ * cin + cout <= 2500, batch <= 65536. */
+/* y[l][m][b][o] = sum_i x[l][m][b][i] * w[i][o][l][m]   (_contract_diagonal, contractions.py:121-127) */
+int mk_spec_diag_fwd(const float* x, const float* w, float* y, int lloc, int mloc, int batch,
+                     int cin, int cout, int l_off, int m_off, int dense, void* stream);
+/* gx[l][m][b][i] = sum_o gy[l][m][b][o] * conj(w[i][o][l][m])   (adjoint in x of contractions.py:121-127) */
+int mk_spec_diag_dgrad(const float* gy, const float* w, float* gx, int lloc, int mloc, int batch,
+                       int cin, int cout, int l_off, int m_off, int dense, void* stream);
+/* gw[i][o][l][m] = sum_b conj(x[l][m][b][i]) * gy[l][m][b][o]   (adjoint in w of contractions.py:121-127) */
+int mk_spec_diag_wgrad(const float* x, const float* gy, float* gw, int lloc, int mloc, int batch,
+                       int cin, int cout, int l_off, int m_off, int dense, void* stream);
+
 /* ---- layout conversion -------------------------------------------------- */
 /* torch [BC][L][M] complex64  <->  private [L][M][BC] complex64.  unpack writes
  * exact zeros where global l < m (what the reference's zero table entries give). */

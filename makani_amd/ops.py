@@ -449,6 +449,105 @@ def diag_contract(x, w):
 
 
 # ----------------------------------------------------------------------------
+# the diagonal filter on the private spectrum (mk_spec_diag_*): no layout round trip, the weight as the parameter stores it
+# ----------------------------------------------------------------------------
+# Opt-in: the default is flipped under the rule of DESIGN section 19 (no measured row of tools/specdiag_bench.py slower) in a
+# change of its own.
+SPEC_DIAG_DEFAULT = "public"
+
+
+def spec_diag_fused():
+    """``MK_SPEC_DIAG=fused|public`` (read at call time): the diagonal filter of ``SpectralConv`` on the private spectrum
+    (``mk_spec_diag_*`` between ``forward_packed`` and ``inverse_packed``), or through the public layout (``mk_diag_*``)."""
+    mode = os.environ.get("MK_SPEC_DIAG", SPEC_DIAG_DEFAULT)
+    if mode not in ("fused", "public"):
+        raise ValueError(f"unknown MK_SPEC_DIAG {mode!r} (fused | public)")
+    return mode == "fused"
+
+
+def spec_diag_supported(c, w):
+    """The ``mk_spec_diag_*`` kernels take these operands: contiguous complex64 tensors on a HIP device."""
+    return all(t.is_cuda and t.dtype == torch.complex64 and t.is_contiguous() for t in (c, w))
+
+
+def _spec_diag_args(s, batch, w_shape):
+    """(lloc, mloc, cin, cout) of a private spectrum ``[L, M, batch * C]`` next to a weight of shape ``[I, O, L, M]``."""
+    assert s.dim() == 3 and s.is_contiguous() and s.dtype == torch.complex64 and len(w_shape) == 4
+    cin, cout, lloc, mloc = (int(v) for v in w_shape)
+    assert (s.shape[0], s.shape[1]) == (lloc, mloc) and s.shape[2] % batch == 0, "spec_diag operand shapes do not match"
+    return lloc, mloc, cin, cout
+
+
+def _spec_diag_launch(name, a, b, out, lloc, mloc, batch, cin, cout, l_off, m_off, dense):
+    _lib.check(getattr(_lib.load(), name)(a.data_ptr(), b.data_ptr(), out.data_ptr(), lloc, mloc, batch, cin, cout, int(l_off),
+                                          int(m_off), int(bool(dense)), _stream()), name)
+    return out
+
+
+def spec_diag_fwd_raw(x, w, batch, l_off=0, m_off=0, dense=False, out=None):
+    """y[l, m, b, o] = sum_i x[l, m, b, i] w[i, o, l, m]; entries with global l < m (``dense`` False) are left unwritten."""
+    _need_cuda(x, w)
+    assert w.is_contiguous() and w.dtype == torch.complex64
+    lloc, mloc, cin, cout = _spec_diag_args(x, batch, w.shape)
+    assert x.shape[2] == batch * cin, "spec_diag operand shapes do not match"
+    y = torch.empty(lloc, mloc, batch * cout, dtype=torch.complex64, device=x.device) if out is None else out
+    return _spec_diag_launch("mk_spec_diag_fwd", x, w, y, lloc, mloc, batch, cin, cout, l_off, m_off, dense)
+
+
+def spec_diag_dgrad_raw(gy, w, batch, l_off=0, m_off=0, dense=False, out=None):
+    """gx[l, m, b, i] = sum_o gy[l, m, b, o] conj(w[i, o, l, m]); entries with global l < m are left unwritten."""
+    _need_cuda(gy, w)
+    assert w.is_contiguous() and w.dtype == torch.complex64
+    lloc, mloc, cin, cout = _spec_diag_args(gy, batch, w.shape)
+    assert gy.shape[2] == batch * cout, "spec_diag operand shapes do not match"
+    gx = torch.empty(lloc, mloc, batch * cin, dtype=torch.complex64, device=gy.device) if out is None else out
+    return _spec_diag_launch("mk_spec_diag_dgrad", gy, w, gx, lloc, mloc, batch, cin, cout, l_off, m_off, dense)
+
+
+def spec_diag_wgrad_raw(x, gy, batch, l_off=0, m_off=0, dense=False, out=None):
+    """gw[i, o, l, m] = sum_b conj(x[l, m, b, i]) gy[l, m, b, o] in the parameter's layout; exact zeros where global l < m."""
+    _need_cuda(x, gy)
+    cin, cout = x.shape[2] // batch, gy.shape[2] // batch
+    lloc, mloc, _, _ = _spec_diag_args(x, batch, (cin, cout, x.shape[0], x.shape[1]))
+    _spec_diag_args(gy, batch, (cin, cout, lloc, mloc))
+    assert x.shape[2] == batch * cin and gy.shape[2] == batch * cout, "spec_diag operand shapes do not match"
+    gw = torch.empty(cin, cout, lloc, mloc, dtype=torch.complex64, device=x.device) if out is None else out
+    return _spec_diag_launch("mk_spec_diag_wgrad", x, gy, gw, lloc, mloc, batch, cin, cout, l_off, m_off, dense)
+
+
+class _SpecDiag(torch.autograd.Function):
+    """y[l, m, b, o] = sum_i x[l, m, b, i] w[i, o, l, m] on the private layout (mk_spec_diag_*)."""
+
+    @staticmethod
+    def forward(ctx, x, w, batch, l_off, m_off, dense):
+        ctx.save_for_backward(x, w)
+        ctx.args = (batch, l_off, m_off, dense)
+        return spec_diag_fwd_raw(x, w, batch, l_off, m_off, dense)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = spec_diag_dgrad_raw(gy, w, *ctx.args)
+        if ctx.needs_input_grad[1]:
+            gw = spec_diag_wgrad_raw(x, gy, *ctx.args)
+        return gx, gw, None, None, None, None
+
+
+def spec_diag(c, w, batch, l_off=0, m_off=0, dense=False):
+    """The diagonal filter ``einsum("bixy,ioxy->boxy")`` on the private spectrum ``c`` ``[L, M, batch * I]`` with the parameter
+    ``w`` ``[I, O, L, M]`` as stored -> ``[L, M, batch * O]``.  The weight gradient comes back in the parameter's layout, the
+    spectrum gradient in the private layout.  ``l_off`` / ``m_off``: the global indices of a shard's first degree / order;
+    ``dense``: every entry is data (the planar pair), otherwise entries with global l < m are neither read nor written."""
+    _need_cuda(c, w)
+    if not spec_diag_supported(c, w):
+        raise TypeError("spec_diag expects contiguous complex64 operands (spec_diag_supported)")
+    return _SpecDiag.apply(c, w, batch, l_off, m_off, dense)
+
+
+# ----------------------------------------------------------------------------
 # 1x1 convolutions on fp32 fields: the bf16x3 engine of the spectral GEMMs (fp32-accurate, no vendor GEMM)
 # ----------------------------------------------------------------------------
 def _pad4(w):

@@ -9,7 +9,9 @@ the layer runs fused on the private channels-last spectrum: FFT -> Legendre (MFM
 -> dhconv (MFMA) -> Legendre -> FFT, five to seven launches, no layout round trip and no
 ``.contiguous()`` copies.  The planar pair (``RealFFT2`` / ``InverseRealFFT2`` on their HIP path) runs the
 same way: FFT -> latitude DFT (MFMA) -> dhconv (dense: no triangle) -> latitude DFT -> FFT.  Any other
-duck-typed transform pair takes the generic path through ``get_contract_fun``.
+duck-typed transform pair takes the generic path through ``get_contract_fun``.  ``operator_type="diagonal"`` takes the
+generic path too unless ``MK_SPEC_DIAG=fused``: then it runs on the same fused path with ``ops.spec_diag`` (``mk_spec_diag_*``,
+the weight ``[in, out, l, m]`` as stored) in place of dhconv.
 
 The dhconv weight keeps the reference's logical shape ``[in, out, l]`` (state-dict
 parity) but is *stored* ``[l, in, out]`` (a permuted view), so each degree's
@@ -107,6 +109,13 @@ class SpectralConv(nn.Module):
         # the planar pair on the same fused path where its HIP transforms apply (decided per call: MK_PLANAR_FFT, the device)
         self._planar = (isinstance(forward_transform, RealFFT2) and isinstance(inverse_transform, InverseRealFFT2)
                         and operator_type == "dhconv" and not separable)
+        # the diagonal filter on the same fused path (ops.spec_diag in place of ops.dhconv), decided per call: MK_SPEC_DIAG
+        self._diag_pair = None
+        if operator_type == "diagonal" and not separable:
+            if _is_hip_pair(forward_transform, inverse_transform):
+                self._diag_pair = "sht"
+            elif isinstance(forward_transform, RealFFT2) and isinstance(inverse_transform, InverseRealFFT2):
+                self._diag_pair = "planar"
 
         if bias == "constant":
             self.bias = nn.Parameter(torch.zeros(1, self.out_channels, 1, 1))
@@ -158,7 +167,11 @@ class SpectralConv(nn.Module):
         elif self.scale_residual:
             r = self.synthesise(c, B, odt)
             residual = r.view(B, C, r.shape[-2], r.shape[-1]).to(dtype)
-        y = ops.dhconv(c, self._weight_tensor(), B, l_off, self.m_off)
+        if self.operator_type == "diagonal":
+            # a weight per (l, m), as the parameter stores it (a shard: the local block); the planar spectrum is dense
+            y = ops.spec_diag(c, self._weight_tensor(), B, self.l_off, self.m_off, dense=isinstance(ft, RealFFT2))
+        else:
+            y = ops.dhconv(c, self._weight_tensor(), B, l_off, self.m_off)
         sums = None
         if want_row_sums:       # the inverse FFT hands over the row statistics of its output (mk_irfft_sums)
             out, sums = it.inverse_packed(y, B, odt, True) if self._distributed else it.inverse_packed(y, odt, True)
@@ -166,6 +179,21 @@ class SpectralConv(nn.Module):
             out = it.inverse_packed(y, B, odt) if self._distributed else it.inverse_packed(y, odt)
         out = out.view(B, self.out_channels, out.shape[-2], out.shape[-1])
         return out, residual, sums
+
+    def _takes_diag_fused(self, x):
+        """The diagonal filter stays on the private spectrum: ``MK_SPEC_DIAG=fused`` (validated on every call), one of this
+        package's HIP transform pairs for this input, fp32 / bf16 rows on the device, the weight as ``ops.spec_diag`` takes it."""
+        if self.operator_type != "diagonal" or not ops.spec_diag_fused():
+            return False
+        if self._diag_pair is None or not (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)):
+            return False
+        w = self._weight_tensor()
+        if not ops.spec_diag_supported(w, w):
+            return False
+        if self._diag_pair == "sht":
+            return True
+        ft = self.forward_transform
+        return tuple(x.shape[-2:]) == (ft.nlat, ft.nlon) and ft.hip_ready(x) and self.inverse_transform.hip_ready(x)
 
     def forward(self, x, want_row_sums=False, premix=None, spectrum_residual=False):
         """``want_row_sums`` (this package's blocks only): a third result, the fp64 ``[B*C, 2]`` sums / sums of squares of the rows
@@ -183,6 +211,7 @@ class SpectralConv(nn.Module):
         fused = self._fused or (self._planar and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16)
                                 and tuple(x.shape[-2:]) == (ft.nlat, ft.nlon)
                                 and ft.hip_ready(x) and self.inverse_transform.hip_ready(x))
+        fused = fused or self._takes_diag_fused(x)
         if fused and x.is_cuda and x.dim() == 4:
             with torch.autocast(device_type="cuda", enabled=False):
                 x, residual, sums = self._forward_fused(x, dtype, want_row_sums and not hasattr(self, "bias"), premix,
@@ -264,6 +293,7 @@ class FactorizedSpectralConv(SpectralConv):
                                           complex=complex_weight, operator_type=operator_type)
         self._fused = self._fused and complex_weight
         self._planar = self._planar and complex_weight
+        self._diag_pair = self._diag_pair if complex_weight else None
 
     def _weight_tensor(self):
         return self.weight.to_tensor()
