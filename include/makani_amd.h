@@ -581,6 +581,35 @@ long long mk_history_workspace(int B, int Cn, int H);
 int mk_history_sums(const void* x, int x_dtype, const float* u, const float* wt, double* workspace, double* sums, int B, int T,
                     int C, int Cu, int H, int W, void* stream);
 
+/* ---- the tail of an autoregressive rollout step (csrc/rollout.hip): everything makani/utils/inferencer.py and the step
+ * wrappers do behind the model call, in one pass over the model output.  Every optional part is switched off by a NULL
+ * pointer or a zero count.  Per point (b, c, h, w), in this order, every product and sum an fp32 rounding of its own (the
+ * file is compiled with fp contraction off):
+ *   v = yn[b][c][h][w]                           fp32 (dtype 0) or bf16 (1, widened exactly)
+ *   v = v * std[b][c] + mean[b][c]               mean, std [B][C] fp32, both or neither
+ *   v = v * mask[h][w]                           for c in mask_chans [n_mask] (int32, device); mask [H][W] fp32
+ *   v = x_last[b][c][h][w] + v * scale[c]        when residual == 1; scale [C] fp32 or NULL (v = x_last + v);
+ *                                                x_last fp32, sample b at x_last + b * x_bstride (elements), [C][H][W] there
+ *   v = x_last[b][c][h][w]                       for c in hold_chans [n_hold] (int32, device)
+ *   pred[b][c][h][w] = v                         fp32, each element written once
+ *   with tar [B][C][H][W] fp32:  d = v - tar (rounded to fp32);  sums [B][C][6] fp64 = the five sums of mk_geo_metric_sums
+ *     in its order (w = wrow[h], c = clim[c][h][w] or 0 when clim is NULL) and the unweighted sum d d;
+ *     err_map [C][H][W] fp32 (or NULL) = (..((err_map + d_0 d_0) + d_1 d_1) ..) over the samples in ascending b
+ *   emit[b][k][h][w] = v(c = emit_chans[k]) * emit_scale[k] + emit_shift[k],  k < K; emit_scale / emit_shift [K] fp32 or
+ *     NULL (the product / the sum is then not formed: the value is copied); an entry of emit_chans outside [0, C) leaves
+ *     its field unwritten, as an entry of mask_chans or hold_chans outside it matches no channel
+ * clim, err_map and sums need tar; tar needs wrow, workspace (mk_rollout_tail_workspace(B, C, H) doubles) and sums.
+ * pred, err_map and emit depend on their own point only: a launch on a slice of rows gives the slice bit for bit.  The
+ * sums are accumulated as in mk_geo_metric_sums (fp32 row partials, fp64 across rows, slabs added in a fixed order): no
+ * atomics, the same bits every run.  Any W and any element-aligned pointers.  No allocation, synchronisation or host
+ * copy. */
+long long mk_rollout_tail_workspace(int B, int C, int H);
+int mk_rollout_tail(const void* yn, int dtype, const float* mean, const float* std, const float* mask, const int* mask_chans,
+                    int n_mask, const float* x_last, long long x_bstride, int residual, const float* scale,
+                    const int* hold_chans, int n_hold, float* pred, const float* tar, const float* clim, const float* wrow,
+                    double* workspace, double* sums, float* err_map, float* emit, const int* emit_chans, const float* emit_scale,
+                    const float* emit_shift, int K, int B, int C, int H, int W, void* stream);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

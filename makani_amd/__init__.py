@@ -13,6 +13,7 @@ Mirrors the reference's interfaces for the hot path only:
 * ``makani_amd.comm``                 h / w / data process groups over torch.distributed (RCCL)
 * ``makani_amd.preprocessor``         Preprocessor2D / get_preprocessor (one-pass HIP input assembly: ``assemble``)
 * ``makani_amd.stepper``              SingleStepWrapper / MultiStepWrapper (the model wrappers of trainer and inferencer)
+* ``makani_amd.inference``            Rollout (the inferencer's autoregressive rollout on a one-pass HIP step tail)
 
 All arithmetic of the spectral path runs in libmakani_amd.so (include/makani_amd.h).
 """

@@ -1861,6 +1861,17 @@ def channel_layer_norm(x, weight, bias, eps=1e-5, fuse_gelu=False, out_dtype=Non
 GEO_METRIC_SUMS = ("l1", "sq", "cov", "var_p", "var_t")     # order of the last axis of geo_metric_sums
 
 
+def _geo_metric_sums_torch(prd, tar, clim, wrow):
+    """The five sums in torch float64 on the tensors' device (the CPU path of ``geo_metric_sums`` and of ``rollout_tail``)."""
+    B, C, H, W = prd.shape
+    p, t = prd.double(), tar.double()
+    w = wrow.double().reshape(1, 1, H, 1)
+    c = clim.double().reshape(1, C, H, W) if clim is not None else torch.zeros((), dtype=torch.float64, device=prd.device)
+    d, pa, ta = p - t, p - c, t - c
+    return torch.stack([(w * d.abs()).sum((-2, -1)), (w * d * d).sum((-2, -1)), (w * pa * ta).sum((-2, -1)),
+                        (w * pa * pa).sum((-2, -1)), (w * ta * ta).sum((-2, -1))], dim=-1)
+
+
 @torch.no_grad()
 def geo_metric_sums(prd, tar, clim, wrow):
     """Latitude-weighted integrals of the validation metrics, ``[B, C, 5]`` float64 in the order of ``GEO_METRIC_SUMS``:
@@ -1878,12 +1889,7 @@ def geo_metric_sums(prd, tar, clim, wrow):
     if clim is not None and tuple(clim.shape[-3:]) != (C, H, W):
         raise ValueError(f"geo_metric_sums: climatology {tuple(clim.shape)} does not match [C, H, W] = {(C, H, W)}")
     if not prd.is_cuda:
-        p, t = prd.double(), tar.double()
-        w = wrow.double().reshape(1, 1, H, 1)
-        c = clim.double().reshape(1, C, H, W) if clim is not None else torch.zeros((), dtype=torch.float64)
-        d, pa, ta = p - t, p - c, t - c
-        return torch.stack([(w * d.abs()).sum((-2, -1)), (w * d * d).sum((-2, -1)), (w * pa * ta).sum((-2, -1)),
-                            (w * pa * pa).sum((-2, -1)), (w * ta * ta).sum((-2, -1))], dim=-1)
+        return _geo_metric_sums_torch(prd, tar, clim, wrow)
     _need_cuda(prd, tar, wrow, *([clim] if clim is not None else []))
     if prd.dtype not in (torch.float32, torch.bfloat16):
         prd = prd.float()
@@ -2140,6 +2146,175 @@ def input_assemble(x, u=None, stat=None, mean=None, std=None, mask_chans=None, m
 
     return _InputAssemble.apply(x.contiguous(), f32(u), f32(stat), f32(mean), f32(std),
                                 mask_chans.contiguous() if mask_chans is not None else None, int(mask_src), out_dtype)
+
+
+# ----------------------------------------------------------------------------
+# the tail of an autoregressive rollout step (csrc/rollout.hip)
+# ----------------------------------------------------------------------------
+ROLLOUT_DEFAULT = "hip"         # MK_ROLLOUT: hip | torch.  No row of tools/rollout_bench.py is slower than torch
+ROLLOUT_SUMS = GEO_METRIC_SUMS + ("sq_unweighted",)     # order of the last axis of rollout_tail's sums
+
+
+def _chan_list(name, chans, C, device, allow_repeat=False):
+    """A channel list as an int32 tensor on ``device`` (None when empty).  A python list is range-checked here; a tensor is
+    taken as it is (the caller built it once: nothing is uploaded or read back, so the call stays capturable)."""
+    if chans is None:
+        return None
+    if torch.is_tensor(chans):
+        if chans.dtype != torch.int32 or chans.dim() != 1:
+            raise ValueError(f"rollout_tail: {name} must be a 1-D int32 tensor, got {chans.dtype} {tuple(chans.shape)}")
+        if chans.device != device:
+            raise ValueError(f"rollout_tail: {name} on {chans.device}, the model output on {device}")
+        return chans.contiguous() if chans.numel() else None
+    chans = [int(c) for c in chans]
+    if not chans:
+        return None
+    if min(chans) < 0 or max(chans) >= C:
+        raise ValueError(f"rollout_tail: {name} {chans} out of range for {C} channels")
+    if not allow_repeat and len(set(chans)) != len(chans):
+        raise ValueError(f"rollout_tail: {name} {chans} repeats a channel")
+    return torch.tensor(chans, dtype=torch.int32, device=device)
+
+
+def _rollout_tail_torch(yn, mean, std, mask, mask_chans, x_last, residual, scale, hold_chans, tar, clim, wrow, err_map,
+                        emit_chans, emit_scale, emit_shift):
+    """The steps of ``rollout_tail`` as torch ops on the tensors' device, one rounding per operation; the sums in torch
+    float64 (the sixth from ``d`` rounded to fp32).  Arguments as ``rollout_tail`` has normalised them."""
+    B, C, H, W = yn.shape
+    v = yn.float()
+    if mean is not None:
+        v = v * std.reshape(B, C, 1, 1)
+        v = v + mean.reshape(B, C, 1, 1)
+
+    def hit(chans):
+        h = torch.zeros(C, dtype=torch.bool, device=yn.device)
+        h[chans.long()] = True
+        return h.reshape(1, C, 1, 1)
+
+    if mask_chans is not None:
+        v = v * torch.where(hit(mask_chans), mask.reshape(1, 1, H, W), torch.ones((), dtype=torch.float32, device=yn.device))
+    if residual:
+        if scale is not None:
+            v = v * scale.reshape(1, C, 1, 1)
+        v = x_last + v
+    if hold_chans is not None:
+        v = torch.where(hit(hold_chans), x_last, v)
+    pred = v.contiguous() if v.data_ptr() != yn.data_ptr() else v.clone()
+    sums = emit = None
+    if tar is not None:
+        d = pred - tar
+        sums = torch.cat([_geo_metric_sums_torch(pred, tar, clim, wrow), d.double().square().sum((-2, -1)).unsqueeze(-1)], dim=-1)
+        if err_map is not None:
+            for b in range(B):
+                err_map += d[b] * d[b]
+    if emit_chans is not None:
+        emit = pred[:, emit_chans.long()]
+        if emit_scale is not None:
+            emit = emit * emit_scale.reshape(1, -1, 1, 1)
+        if emit_shift is not None:
+            emit = emit + emit_shift.reshape(1, -1, 1, 1)
+        emit = emit.contiguous()
+    return pred, sums, emit
+
+
+@torch.no_grad()
+def rollout_tail(yn, mean=None, std=None, mask=None, mask_chans=None, x_last=None, residual=False, scale=None, hold_chans=None,
+                 tar=None, clim=None, wrow=None, err_map=None, emit_chans=None, emit_scale=None, emit_shift=None):
+    """Everything a rollout step does behind the model call, in one pass over the model output ``yn`` ``[B, C, H, W]`` (fp32
+    or bf16): returns ``(pred, sums, emit)`` and updates ``err_map`` in place.  Per point, in this order, every product
+    and sum an fp32 rounding of its own:
+
+    * ``v = yn * std + mean`` with ``mean`` / ``std`` of ``B * C`` elements, both or neither (``history_denormalize``);
+    * ``v = v * mask`` for the channels ``mask_chans`` with ``mask`` ``[H, W]`` (``mask_output``);
+    * ``v = x_last + v * scale`` when ``residual`` (``scale`` ``[C]`` optional), ``x_last`` ``[B, C, H, W]`` fp32, which may
+      be the last history step of the step's input, a strided view read in place (``add_residual``);
+    * ``v = x_last`` for the channels ``hold_chans``;
+    * ``pred = v``, fp32 ``[B, C, H, W]``;
+    * with ``tar`` ``[B, C, H, W]`` and ``wrow`` ``[H]``: ``d = pred - tar`` and ``sums`` ``[B, C, 6]`` float64 in the order of
+      ``ROLLOUT_SUMS`` -- the five of ``geo_metric_sums`` (``clim`` ``[C, H, W]`` or None) and the unweighted sum of
+      ``d * d``; ``err_map`` ``[C, H, W]`` fp32 (contiguous) gets ``+= d[b] * d[b]`` for b = 0, 1, ... in that order;
+    * ``emit = pred[:, emit_chans] * emit_scale + emit_shift`` ``[B, K, H, W]`` fp32 (scale and shift ``[K]``, each optional).
+
+    Channel lists are python lists (checked against C) or 1-D int32 tensors on the device (taken as they are; an entry
+    outside ``[0, C)`` matches nothing in the kernel).  ``sums`` / ``emit`` are None without ``tar`` / ``emit_chans``.
+
+    ``MK_ROLLOUT=hip`` (read on every call): CUDA tensors take one HIP pass plus a fixed-order finalize
+    (``mk_rollout_tail``; bitwise repeatable, capturable).  CPU tensors, and ``MK_ROLLOUT=torch``, take
+    ``_rollout_tail_torch``, the same steps as torch ops.  No gradient flows through this op."""
+    hip = _hip_or_torch("MK_ROLLOUT", ROLLOUT_DEFAULT)
+    if yn.dim() != 4:
+        raise ValueError(f"rollout_tail: model output {tuple(yn.shape)} must be [B, C, H, W]")
+    B, C, H, W = yn.shape
+    dev = yn.device
+    if (mean is None) != (std is None) or (mean is not None and (mean.numel() != B * C or std.numel() != B * C)):
+        raise ValueError(f"rollout_tail: mean and std must both have B * C = {B * C} elements, got "
+                         f"{None if mean is None else tuple(mean.shape)} and {None if std is None else tuple(std.shape)}")
+    mask_chans = _chan_list("mask_chans", mask_chans, C, dev)
+    hold_chans = _chan_list("hold_chans", hold_chans, C, dev)
+    emit_chans = _chan_list("emit_chans", emit_chans, C, dev, allow_repeat=True)
+    if mask_chans is not None and (mask is None or tuple(mask.shape[-2:]) != (H, W) or mask.numel() != H * W):
+        raise ValueError(f"rollout_tail: masked channels need a mask [H, W] = {(H, W)}, got {None if mask is None else tuple(mask.shape)}")
+    if (residual or hold_chans is not None) and (x_last is None or tuple(x_last.shape) != (B, C, H, W)):
+        raise ValueError(f"rollout_tail: the residual and the held channels need x_last {(B, C, H, W)}, got "
+                         f"{None if x_last is None else tuple(x_last.shape)}")
+    if scale is not None and (not residual or scale.numel() != C):
+        raise ValueError(f"rollout_tail: scale {tuple(scale.shape)} needs residual=True and C = {C} elements")
+    if tar is None and (clim is not None or err_map is not None):
+        raise ValueError("rollout_tail: clim and err_map need a target")
+    if tar is not None:
+        if tuple(tar.shape) != (B, C, H, W):
+            raise ValueError(f"rollout_tail: target {tuple(tar.shape)} does not match the model output {(B, C, H, W)}")
+        if wrow is None or wrow.numel() != H:
+            raise ValueError(f"rollout_tail: wrow has {0 if wrow is None else wrow.numel()} weights for {H} latitude rows")
+        if clim is not None and tuple(clim.shape[-3:]) != (C, H, W):
+            raise ValueError(f"rollout_tail: climatology {tuple(clim.shape)} does not match [C, H, W] = {(C, H, W)}")
+        if err_map is not None and (tuple(err_map.shape) != (C, H, W) or err_map.dtype != torch.float32
+                                    or not err_map.is_contiguous() or err_map.device != dev):
+            raise ValueError(f"rollout_tail: err_map must be a contiguous fp32 [C, H, W] = {(C, H, W)} on {dev}, got "
+                             f"{err_map.dtype} {tuple(err_map.shape)} on {err_map.device}")
+    K = emit_chans.numel() if emit_chans is not None else 0
+    for name, t in (("emit_scale", emit_scale), ("emit_shift", emit_shift)):
+        if t is not None and (K == 0 or t.numel() != K):
+            raise ValueError(f"rollout_tail: {name} {tuple(t.shape)} needs K = {K} emitted channels")
+
+    def f32(t):
+        return t.detach().float().contiguous() if t is not None else None
+
+    if yn.dtype not in (torch.float32, torch.bfloat16):
+        yn = yn.float()
+    yn = yn.detach()
+    mean, std, mask, scale, tar, clim, wrow = (f32(t) for t in (mean, std, mask, scale, tar, clim, wrow))
+    emit_scale, emit_shift = f32(emit_scale), f32(emit_shift)
+    if not (residual or hold_chans is not None):
+        x_last = None
+    if x_last is not None:
+        x_last = x_last.detach().float()
+    if not (hip and yn.is_cuda):
+        return _rollout_tail_torch(yn, mean, std, mask, mask_chans, x_last, bool(residual), scale, hold_chans, tar, clim, wrow,
+                                   err_map, emit_chans, emit_scale, emit_shift)
+    _need_cuda(*[t for t in (mean, std, mask, x_last, scale, tar, clim, wrow, emit_scale, emit_shift) if t is not None])
+    yn = yn.contiguous()
+    x_bstride = 0
+    if x_last is not None:
+        # read in place when every sample is a contiguous [C, H, W] block (the last history step of the input is)
+        if tuple(x_last.stride()[1:]) != (H * W, W, 1) or (B > 1 and x_last.stride(0) < C * H * W):
+            x_last = x_last.contiguous()
+        x_bstride = x_last.stride(0) if B > 1 else C * H * W
+    lib = _lib.load()
+    pred = torch.empty(B, C, H, W, dtype=torch.float32, device=dev)
+    ws = sums = emit = None
+    if tar is not None:
+        ws = torch.empty(lib.mk_rollout_tail_workspace(B, C, H), dtype=torch.float64, device=dev)
+        sums = torch.empty(B, C, 6, dtype=torch.float64, device=dev)
+    if K:
+        emit = torch.empty(B, K, H, W, dtype=torch.float32, device=dev)
+    _lib.check(lib.mk_rollout_tail(yn.data_ptr(), _pw_dtype(yn), _ptr(mean), _ptr(std), _ptr(mask), _ptr(mask_chans),
+                                   mask_chans.numel() if mask_chans is not None else 0, _ptr(x_last), x_bstride, int(bool(residual)),
+                                   _ptr(scale), _ptr(hold_chans), hold_chans.numel() if hold_chans is not None else 0,
+                                   pred.data_ptr(), _ptr(tar), _ptr(clim), _ptr(wrow), _ptr(ws), _ptr(sums), _ptr(err_map),
+                                   _ptr(emit), _ptr(emit_chans), _ptr(emit_scale), _ptr(emit_shift), K, B, C, H, W, _stream()),
+               "mk_rollout_tail")
+    return pred, sums, emit
 
 
 # ----------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """What the ``*_bench.py`` tools that set a HIP path against its torch formulation share: windows of back-to-back calls between
 two device events, the alternating median over such windows, a relative error for the sanity bound before a row is timed, and a
 callable that sets a family's ``hip | torch`` variable.  Imported by specattn_bench, specdiag_bench, afno_bench, attn_bench, toknorm_bench,
-toklinear_bench, toklinear_fp32_bench, afnov1_bench and patch_bench; ``bench.py`` at the root has its own timing and does not use it."""
+toklinear_bench, toklinear_fp32_bench, afnov1_bench, patch_bench and rollout_bench; ``bench.py`` at the root has its own timing and does not use it."""
 import os
 
 import numpy as np
