@@ -1,9 +1,11 @@
 """CPU tests of the channel layer norm: the C ABI is exported and bound, and ``DistributedLayerNorm`` on the CPU is still the
-reference's formulation (transpose -> nn.LayerNorm -> transpose), bit for bit.  No kernel launches here."""
+reference's formulation (transpose -> nn.LayerNorm -> transpose), bit for bit; the constants of chnorm_checks.py against its
+emulation of the kernels' arithmetic.  No kernel launches here."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import chnorm_checks as cc
 from makani_amd import _lib, ops
 from makani_amd.layer_norm import DistributedLayerNorm
 
@@ -76,3 +78,42 @@ def test_optional_parameters_construct_and_run():
     assert list(m.state_dict().keys()) == ["norm.weight"]
     assert m.norm.weight.is_shared_mp == ["model"] and m.norm.bias is None
     assert torch.equal(m(x, fuse_gelu=True), F.gelu(_reference(m, x)))
+
+
+def test_emulation_stays_within_half_of_each_constant():
+    worst = cc.emulation_worst()
+    print("[chnorm] emulation worst ratios: " + ", ".join(f"{k} {v:.2f}" for k, v in worst.items()))
+    recorded = dict(y=cc.EMU_WORST_Y, gx=cc.EMU_WORST_GX, gw=cc.EMU_WORST_GW, gb=cc.EMU_WORST_GB, stat=cc.EMU_WORST_STAT)
+    limits = dict(y=cc.C_Y, gx=cc.C_GX, gw=cc.C_GW, gb=cc.C_GB, stat=cc.C_STAT)
+    for k, v in worst.items():
+        assert v <= limits[k] / 2, (k, v, limits[k])
+        assert v <= recorded[k] * 1.02 + 0.01, f"{k}: the emulation reaches {v:.3f}, the module records {recorded[k]}"
+    assert any(-(-P // 32) * B >= 3 * grid for B, _, P, grid in cc.EMU_SHAPES), "no shape with 3 tiles per workgroup"
+    for act in (cc.F32, cc.BF16):
+        d = cc.dgelu_abs_error(act)
+        assert d <= cc.EMU_DGELU[act] * 1.02 and cc.DGELU[act] >= 2 * cc.EMU_DGELU[act], (act, d)
+
+
+def test_a_defect_is_far_outside_the_bounds():
+    """What the constants are there to catch, each at least 20 times its limit: a workgroup that drops the channel sums of its
+    second tile, a pixel whose (mean, rstd) are its neighbour's, a one-pass variance at N(50, 0.1^2)."""
+    B, C, P, grid = 3, 4, 2250, 64                                        # 213 tiles of 32 pixels on 64 workgroups
+    for fuse in (False, True):
+        t = cc.make_inputs(B, C, P, "n53", 0)
+        ref = cc.reference(t["x"], t["w"], t["b"], 1e-6, t["gy"], fuse)
+        good = cc.ratios(cc.emulate(t["x"], t["w"], t["b"], 1e-6, t["gy"], fuse, grid=grid), ref)
+        assert good["gw"] <= cc.C_GW / 2 and good["gb"] <= cc.C_GB / 2 and good["y"] <= cc.C_Y / 2
+        bad = cc.ratios(cc.emulate(t["x"], t["w"], t["b"], 1e-6, t["gy"], fuse, grid=grid, defect="drop_tile"), ref)
+        assert bad["gw"] > 20 * cc.C_GW and bad["gb"] > 20 * cc.C_GB, bad
+        bad = cc.ratios(cc.emulate(t["x"], t["w"], t["b"], 1e-6, t["gy"], fuse, grid=grid, defect="neighbour_stats"), ref)
+        assert bad["y"] > 20 * cc.C_Y and bad["gx"] > 20 * cc.C_GX and bad["stat"] > 20 * cc.C_STAT, bad
+        t = cc.make_inputs(1, 73, 36, "n50", 0)
+        ref = cc.reference(t["x"], t["w"], t["b"], 1e-6, t["gy"], fuse)
+        bad = cc.ratios(cc.emulate(t["x"], t["w"], t["b"], 1e-6, t["gy"], fuse, defect="one_pass"), ref)
+        assert bad["y"] > 20 * cc.C_Y and bad["gx"] > 20 * cc.C_GX and bad["stat"] > 20 * cc.C_STAT, bad
+
+
+def test_rows_and_field_are_inverse():
+    x = torch.arange(2 * 3 * 5.0).view(2, 3, 5)
+    r = cc.rows(x)
+    assert r.shape == (10, 3) and torch.equal(r[7], x[1, :, 2]) and torch.equal(cc.field(r, 2), x)
