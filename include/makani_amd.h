@@ -610,6 +610,31 @@ int mk_rollout_tail(const void* yn, int dtype, const float* mean, const float* s
                     double* workspace, double* sums, float* err_map, float* emit, const int* emit_chans, const float* emit_scale,
                     const float* emit_shift, int K, int B, int C, int H, int W, void* stream);
 
+/* ---- dataset statistics (csrc/stats.hip): what data_process/get_stats.py derives its seven files from, in one pass
+ * over a batch x [T][C][H][W] of fp32 samples that are consecutive in time.  Every optional part is switched off by a
+ * NULL pointer or a zero count.  Per channel c, with d = x - pivot[c] (pivot [C] fp32; NULL: 0), e = x_t - x_{t-1}, both
+ * formed in fp64, and w = wrow[h] (wrow [H] fp32):
+ *   sums [C][4] fp64   = sum w d,  sum w d^2,  sum w e,  sum w e^2          written, not accumulated
+ *     e runs over t = 1 ... T-1, and over t = 0 too when prev [C][H][W] fp32 is given (the sample before the first);
+ *     with T = 1 and no prev the two difference sums are exact zeros
+ *   minmax [C][2] fp32 = min, max over the call; a NaN anywhere in a channel makes its min, max and four sums NaN
+ *   tsum [C][H][W] fp64, read-modify-write:  tsum = (..((tsum + x_0) + x_1) ..) in ascending t, one thread per point:
+ *     bit-equal to a sequential fp64 sum, and a launch on a slice of rows gives that slice bit for bit
+ *   wsums [n_wind][2] fp64 = sum m,  sum m^2 (unweighted) for the pairs (wind_u[k], wind_v[k]) (int32, device),
+ *     m = sqrtf(u u + v v) in fp32: each product rounded, the sum rounded, the root correctly rounded (no fma), then
+ *     widened.  The u channels must differ: a pair whose u repeats an earlier pair's, or with an index outside [0, C),
+ *     reads nothing and gets NaN sums.  The v channel of a pair is read a second time.
+ * All accumulation is fp64 (a lane adds the unweighted terms of a row and folds them with the row's weight at its end);
+ * every workgroup writes a workspace slot of its own and a finish adds the slots in a fixed order: no atomics, the same
+ * bits every run.  The sums add up over spatial shards and over calls with one pivot (the caller slices wrow to its
+ * shard).  Element offsets are 64-bit (T C H W may pass 2^31); C <= 65535 and C H W < 2^31.  Any W and any
+ * element-aligned pointers.  No allocation, synchronisation or host copy: `workspace` holds
+ * mk_field_stats_workspace(C, H, n_wind) doubles. */
+long long mk_field_stats_workspace(int C, int H, int n_wind);
+int mk_field_stats(const float* x, const float* prev, const float* pivot, const float* wrow, double* workspace, double* sums,
+                   float* minmax, double* tsum, const int* wind_u, const int* wind_v, int n_wind, double* wsums, int T, int C,
+                   int H, int W, void* stream);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

@@ -2155,24 +2155,24 @@ ROLLOUT_DEFAULT = "hip"         # MK_ROLLOUT: hip | torch.  No row of tools/roll
 ROLLOUT_SUMS = GEO_METRIC_SUMS + ("sq_unweighted",)     # order of the last axis of rollout_tail's sums
 
 
-def _chan_list(name, chans, C, device, allow_repeat=False):
+def _chan_list(name, chans, C, device, allow_repeat=False, who="rollout_tail"):
     """A channel list as an int32 tensor on ``device`` (None when empty).  A python list is range-checked here; a tensor is
     taken as it is (the caller built it once: nothing is uploaded or read back, so the call stays capturable)."""
     if chans is None:
         return None
     if torch.is_tensor(chans):
         if chans.dtype != torch.int32 or chans.dim() != 1:
-            raise ValueError(f"rollout_tail: {name} must be a 1-D int32 tensor, got {chans.dtype} {tuple(chans.shape)}")
+            raise ValueError(f"{who}: {name} must be a 1-D int32 tensor, got {chans.dtype} {tuple(chans.shape)}")
         if chans.device != device:
-            raise ValueError(f"rollout_tail: {name} on {chans.device}, the model output on {device}")
+            raise ValueError(f"{who}: {name} on {chans.device}, the model output on {device}")
         return chans.contiguous() if chans.numel() else None
     chans = [int(c) for c in chans]
     if not chans:
         return None
     if min(chans) < 0 or max(chans) >= C:
-        raise ValueError(f"rollout_tail: {name} {chans} out of range for {C} channels")
+        raise ValueError(f"{who}: {name} {chans} out of range for {C} channels")
     if not allow_repeat and len(set(chans)) != len(chans):
-        raise ValueError(f"rollout_tail: {name} {chans} repeats a channel")
+        raise ValueError(f"{who}: {name} {chans} repeats a channel")
     return torch.tensor(chans, dtype=torch.int32, device=device)
 
 
@@ -2315,6 +2315,100 @@ def rollout_tail(yn, mean=None, std=None, mask=None, mask_chans=None, x_last=Non
                                    _ptr(emit), _ptr(emit_chans), _ptr(emit_scale), _ptr(emit_shift), K, B, C, H, W, _stream()),
                "mk_rollout_tail")
     return pred, sums, emit
+
+
+# ----------------------------------------------------------------------------
+# dataset statistics (csrc/stats.hip)
+# ----------------------------------------------------------------------------
+STATS_DEFAULT = "hip"           # MK_STATS: hip | torch.  No row of tools/stats_bench.py is slower than torch
+FIELD_STATS_SUMS = ("d", "d_sq", "diff", "diff_sq")     # order of the last axis of field_stats' sums
+
+
+def _field_stats_torch(x, prev, pivot, wrow, tsum, wind_u, wind_v):
+    """The sums of ``field_stats`` as float64 torch ops on the tensors' device; ``tsum`` is added to sample by sample."""
+    T, C, H, W = x.shape
+    xd = x.double()
+    w = wrow.double().reshape(1, 1, H, 1)
+    d = xd - pivot.double().reshape(1, C, 1, 1) if pivot is not None else xd
+    if prev is not None:
+        e = xd - torch.cat([prev.double().reshape(1, C, H, W), xd[:-1]], dim=0)
+    else:
+        e = xd[1:] - xd[:-1]                     # empty for T = 1: the sums over it are exact zeros
+    sums = torch.stack([(w * d).sum((0, 2, 3)), (w * d * d).sum((0, 2, 3)), (w * e).sum((0, 2, 3)), (w * e * e).sum((0, 2, 3))], dim=-1)
+    minmax = torch.stack([x.amin((0, 2, 3)), x.amax((0, 2, 3))], dim=-1)        # amin / amax keep a NaN, as np.min does
+    sums = torch.where(torch.isnan(minmax[:, :1]), float("nan"), sums)
+    for t in range(T):
+        tsum += xd[t]
+    wsums = None
+    if wind_u is not None:
+        u, v = x[:, wind_u.long()], x[:, wind_v.long()]
+        # fp32, one rounding per operation, then widened.  The root is taken in float64 and rounded to fp32, which is the
+        # correctly rounded fp32 root (53 >= 2 * 24 + 2 bits); torch's own fp32 sqrt is not correctly rounded everywhere
+        m = torch.sqrt((u * u + v * v).double()).float().double()
+        wsums = torch.stack([m.sum((0, 2, 3)), (m * m).sum((0, 2, 3))], dim=-1)
+    return sums, minmax, wsums
+
+
+@torch.no_grad()
+def field_stats(x, wrow, tsum, prev=None, pivot=None, wind_u=None, wind_v=None):
+    """One pass over a batch ``x`` ``[T, C, H, W]`` (fp32, consecutive in time) for the dataset statistics: returns
+    ``(sums, minmax, wsums)`` and adds the samples to ``tsum`` in place.
+
+    * ``sums`` ``[C, 4]`` float64 in the order of ``FIELD_STATS_SUMS``: ``sum w d``, ``sum w d^2``, ``sum w e``, ``sum w e^2``
+      with ``d = x - pivot[c]`` (``pivot`` ``[C]`` fp32 or None: 0), ``e = x[t] - x[t - 1]``, both formed in float64, and
+      ``w = wrow[h]``.  ``e`` runs over ``t = 1 ... T - 1``, and over ``t = 0`` too when ``prev`` ``[C, H, W]`` (the sample
+      before the first) is given;
+    * ``minmax`` ``[C, 2]`` fp32; a NaN in a channel makes its min, max and sums NaN;
+    * ``tsum`` ``[C, H, W]`` float64 (contiguous): ``tsum += x[0]``, ``+= x[1]``, ... in that order;
+    * ``wsums`` ``[n_wind, 2]`` float64 (None without pairs): the unweighted ``sum m``, ``sum m^2`` of
+      ``m = sqrt(u * u + v * v)`` (fp32, one rounding per operation) for the channel pairs ``(wind_u[k], wind_v[k])``;
+      python lists (checked against C, the u channels distinct) or 1-D int32 tensors on the device (taken as they are).
+
+    ``MK_STATS=hip`` (read on every call): CUDA tensors take one HIP pass plus a fixed-order finish (``mk_field_stats``;
+    bitwise repeatable, capturable).  CPU tensors, and ``MK_STATS=torch``, take ``_field_stats_torch``, the same sums as
+    float64 torch ops.  No gradient flows through this op."""
+    hip = _hip_or_torch("MK_STATS", STATS_DEFAULT)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"field_stats: the batch must be fp32 [T, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    T, C, H, W = x.shape
+    dev = x.device
+    if T < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError(f"field_stats: empty batch {tuple(x.shape)}")
+    if wrow.numel() != H:
+        raise ValueError(f"field_stats: wrow has {wrow.numel()} weights for {H} latitude rows")
+    if tuple(tsum.shape) != (C, H, W) or tsum.dtype != torch.float64 or not tsum.is_contiguous() or tsum.device != dev:
+        raise ValueError(f"field_stats: tsum must be a contiguous float64 [C, H, W] = {(C, H, W)} on {dev}, got "
+                         f"{tsum.dtype} {tuple(tsum.shape)} on {tsum.device}")
+    if prev is not None and (tuple(prev.shape[-3:]) != (C, H, W) or prev.numel() != C * H * W):
+        raise ValueError(f"field_stats: prev {tuple(prev.shape)} does not match [C, H, W] = {(C, H, W)}")
+    if pivot is not None and pivot.numel() != C:
+        raise ValueError(f"field_stats: pivot has {pivot.numel()} elements for {C} channels")
+    if (wind_u is None) != (wind_v is None):
+        raise ValueError("field_stats: wind_u and wind_v come together")
+    wind_u = _chan_list("wind_u", wind_u, C, dev, who="field_stats")
+    wind_v = _chan_list("wind_v", wind_v, C, dev, allow_repeat=True, who="field_stats")
+    if (wind_u is None) != (wind_v is None) or (wind_u is not None and wind_u.numel() != wind_v.numel()):
+        raise ValueError("field_stats: wind_u and wind_v must name the same number of channels")
+
+    def f32(t):
+        return t.detach().float().contiguous() if t is not None else None
+
+    x = x.detach()
+    prev, pivot, wrow = f32(prev), f32(pivot), f32(wrow)
+    if not (hip and x.is_cuda):
+        return _field_stats_torch(x, prev, pivot, wrow, tsum, wind_u, wind_v)
+    _need_cuda(*[t for t in (prev, pivot, wrow) if t is not None])
+    x = x.contiguous()
+    n_wind = wind_u.numel() if wind_u is not None else 0
+    lib = _lib.load()
+    ws = torch.empty(lib.mk_field_stats_workspace(C, H, n_wind), dtype=torch.float64, device=dev)
+    sums = torch.empty(C, 4, dtype=torch.float64, device=dev)
+    minmax = torch.empty(C, 2, dtype=torch.float32, device=dev)
+    wsums = torch.empty(n_wind, 2, dtype=torch.float64, device=dev) if n_wind else None
+    _lib.check(lib.mk_field_stats(x.data_ptr(), _ptr(prev), _ptr(pivot), wrow.data_ptr(), ws.data_ptr(), sums.data_ptr(),
+                                  minmax.data_ptr(), tsum.data_ptr(), _ptr(wind_u), _ptr(wind_v), n_wind, _ptr(wsums), T, C, H, W,
+                                  _stream()), "mk_field_stats")
+    return sums, minmax, wsums
 
 
 # ----------------------------------------------------------------------------
