@@ -635,6 +635,28 @@ int mk_field_stats(const float* x, const float* prev, const float* pivot, const 
                    float* minmax, double* tsum, const int* wind_u, const int* wind_v, int n_wind, double* wsums, int T, int C,
                    int H, int W, void* stream);
 
+/* ---- dataset histograms (csrc/hist.hip): the second sweep of data_process/get_histograms.py, np.histogram per channel
+ * over a given range, in one pass over a batch x [T][C][H][W] of fp32 samples.
+ *   edges [C][nbins + 1] fp64: per channel a strictly increasing table (an fp32 table is widened by the caller, which
+ *     is exact).  Whether it increases cannot be checked through a device pointer: that is the caller's check
+ *   counts [C][nbins] int64, ADDED TO: the caller zeroes it once and batches accumulate.  The counts are the ones the
+ *     table defines, exactly: bin i holds edges[i] <= x < edges[i + 1], the last bin is closed on the right.  The bin of
+ *     a point is guessed by fp32 arithmetic and corrected against the table, so no rounding of the guess reaches a count
+ *   outside [C][3] int64, added to, or NULL: the points below edges[0] (-inf among them), above edges[nbins] (+inf) and
+ *     the NaNs, none of which is binned (np.histogram drops them silently)
+ * Workgroup (slab of 4 rows, channel) keeps the channel's table, as the exact fp32 thresholds up(edges[i]) (x >= e for
+ * an fp32 x is x >= the smallest fp32 not below e), and R replicas of a uint32 bin array in LDS (lane -> replica, runs
+ * of equal bins among a lane's 8 points merged into one add), folds the replicas and adds its non-zero bins
+ * to counts with device-scope 64-bit INTEGER atomics: integer addition commutes and does not round, so the result is
+ * the same every run and for every split of the rows or the samples -- which is why atomics are acceptable here, where
+ * the floating-point sums of this library avoid them.  nbins is 1 ... 4096: the table and one bin array then take 32,776
+ * bytes of LDS (plus 48 static) and four workgroups fit a CU of 160 KB; more bins would run on fewer.  C <= 65535, C H W < 2^31, and 4 W T < 2^32 (a
+ * workgroup's points fit a uint32 bin); element offsets are 64-bit.  Any W; x at any 4-byte aligned address, every
+ * (sample, row) vectorised from its own 16-byte boundary; edges, counts and outside 8-byte aligned.  Every refusal
+ * returns 1 before any launch.  No workspace, one launch, no allocation, synchronisation or host copy. */
+int mk_field_hist(const float* x, const double* edges, long long* counts, long long* outside, int nbins, int T, int C, int H,
+                  int W, void* stream);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

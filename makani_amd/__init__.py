@@ -14,6 +14,8 @@ Mirrors the reference's interfaces for the hot path only:
 * ``makani_amd.preprocessor``         Preprocessor2D / get_preprocessor (one-pass HIP input assembly: ``assemble``)
 * ``makani_amd.stepper``              SingleStepWrapper / MultiStepWrapper (the model wrappers of trainer and inferencer)
 * ``makani_amd.inference``            Rollout (the inferencer's autoregressive rollout on a one-pass HIP step tail)
+* ``makani_amd.stats``                DatasetStats (the statistics files of a dataset from one HIP pass per batch)
+* ``makani_amd.histograms``           DatasetHistograms (per-channel value histograms, equal to np.histogram's, on one HIP pass)
 
 All arithmetic of the spectral path runs in libmakani_amd.so (include/makani_amd.h).
 """

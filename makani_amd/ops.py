@@ -2412,6 +2412,107 @@ def field_stats(x, wrow, tsum, prev=None, pivot=None, wind_u=None, wind_v=None):
 
 
 # ----------------------------------------------------------------------------
+# dataset histograms (csrc/hist.hip)
+# ----------------------------------------------------------------------------
+HIST_DEFAULT = "hip"            # MK_HIST: hip | torch.  No row of tools/hist_bench.py is slower than torch
+HIST_MAX_BINS = 4096            # what mk_field_hist takes: the edge table and one bin array in 32,776 bytes of LDS
+FIELD_HIST_OUTSIDE = ("below", "above", "nan")          # order of the last axis of field_hist's outside
+
+
+def hist_edges(lo, hi, nbins, dtype=np.float32):
+    """The bin edges ``[C, nbins + 1]`` that ``np.histogram(a, bins=nbins, range=(lo[c], hi[c]))`` returns for data ``a`` of
+    ``dtype`` and Python-float bounds, bit for bit: ``np.linspace`` over the range in ``dtype`` (numpy computes it in float64
+    and rounds once).  ``lo`` and ``hi`` are scalars or ``[C]``; ``lo == hi`` widens the range by 0.5 each way, as numpy
+    does.  Raises ``ValueError`` for non-finite bounds, ``lo > hi``, ``nbins < 1`` and for a table that is not strictly
+    increasing in ``dtype`` ("Too many bins for data range", numpy's words)."""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"hist_edges: the edge dtype must be float32 or float64, got {dtype}")
+    if int(nbins) != nbins or nbins < 1:
+        raise ValueError(f"hist_edges: nbins must be a positive integer, got {nbins!r}")
+    nbins = int(nbins)
+    lo, hi = np.atleast_1d(np.asarray(lo, dtype=np.float64)), np.atleast_1d(np.asarray(hi, dtype=np.float64))
+    if lo.ndim != 1 or lo.shape != hi.shape or lo.size < 1:
+        raise ValueError(f"hist_edges: lo {lo.shape} and hi {hi.shape} must be scalars or [C]")
+    out = np.empty((lo.size, nbins + 1), dtype=dtype)
+    for c, (first, last) in enumerate(zip(lo.tolist(), hi.tolist())):
+        if not (np.isfinite(first) and np.isfinite(last)):
+            raise ValueError(f"hist_edges: channel {c}: the range [{first}, {last}] is not finite")
+        if first > last:
+            raise ValueError(f"hist_edges: channel {c}: max must be larger than min in the range [{first}, {last}]")
+        if first == last:
+            first, last = first - 0.5, last + 0.5
+        out[c] = np.linspace(first, last, nbins + 1, endpoint=True, dtype=dtype)
+        if np.any(out[c, :-1] >= out[c, 1:]):
+            raise ValueError(f"hist_edges: channel {c}: Too many bins for data range. Cannot create {nbins} finite-sized bins "
+                             f"in [{first}, {last}] in {dtype}.")
+    return out
+
+
+def _field_hist_torch(x, edges, counts, outside):
+    """``field_hist`` as torch ops on the tensors' device, exact by the same definition: ``bucketize`` of the float64 points
+    against the channel's table, the last edge sent to the last bin, ``bincount``."""
+    nbins = counts.shape[1]
+    for c in range(x.shape[1]):
+        v = x[:, c].reshape(-1).double()
+        e = edges[c]
+        nan, below, above = torch.isnan(v), v < e[0], v > e[-1]
+        idx = (torch.bucketize(v[~(nan | below | above)], e, right=True) - 1).clamp_(max=nbins - 1)
+        counts[c] += torch.bincount(idx, minlength=nbins)
+        if outside is not None:
+            outside[c] += torch.stack([below.sum(), above.sum(), nan.sum()])
+
+
+@torch.no_grad()
+def field_hist(x, edges, counts, outside=None):
+    """Adds the per-channel histograms of a batch ``x`` ``[T, C, H, W]`` (fp32) to ``counts`` in place; returns ``counts``.
+
+    * ``edges`` ``[C, nbins + 1]`` float64 (contiguous): per channel a strictly increasing table, as ``hist_edges`` builds
+      (an fp32 table widened, which is exact).  That it increases is the caller's to see to: ``hist_edges`` checks it;
+    * ``counts`` ``[C, nbins]`` int64 (contiguous), added to: bin ``i`` counts ``edges[i] <= x < edges[i + 1]``, the last bin
+      is closed on the right -- the counts of ``np.histogram`` with these edges, exactly, whatever path runs;
+    * ``outside`` ``[C, 3]`` int64 (contiguous) or None, added to, in the order of ``FIELD_HIST_OUTSIDE``: the points below
+      the first edge, above the last, and the NaNs, which no bin counts.
+
+    ``MK_HIST=hip`` (read on every call): CUDA tensors with up to ``HIST_MAX_BINS`` bins take one HIP pass
+    (``mk_field_hist``: bins in LDS, 64-bit integer atomics to ``counts``; the same result every run, capturable).  CPU
+    tensors, more bins, and ``MK_HIST=torch`` take ``_field_hist_torch``; the two are equal, not close.  No gradient flows
+    through this op.
+
+    Speed, not counts: the HIP pass guesses the bin as if the table were uniform and walks from the guess to the right bin
+    one edge at a time, so it is fast for near-uniform tables (``hist_edges``).  A strongly non-uniform table, such as
+    quantile edges, stays exact but can cost up to ``nbins`` dependent LDS reads per point; its time is not measured, and
+    ``MK_HIST=torch`` (a binary search) is the path to try there."""
+    hip = _hip_or_torch("MK_HIST", HIST_DEFAULT)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"field_hist: the batch must be fp32 [T, C, H, W], got {x.dtype} {tuple(x.shape)}")
+    T, C, H, W = x.shape
+    dev = x.device
+    if T < 1 or C < 1 or H < 1 or W < 1:
+        raise ValueError(f"field_hist: empty batch {tuple(x.shape)}")
+    if edges.dim() != 2 or edges.shape[0] != C or edges.shape[1] < 2 or edges.dtype != torch.float64 or not edges.is_contiguous() \
+            or edges.device != dev:
+        raise ValueError(f"field_hist: edges must be a contiguous float64 [C, nbins + 1] with C = {C} on {dev}, got "
+                         f"{edges.dtype} {tuple(edges.shape)} on {edges.device}")
+    nbins = edges.shape[1] - 1
+    if tuple(counts.shape) != (C, nbins) or counts.dtype != torch.int64 or not counts.is_contiguous() or counts.device != dev:
+        raise ValueError(f"field_hist: counts must be a contiguous int64 [C, nbins] = {(C, nbins)} on {dev}, got "
+                         f"{counts.dtype} {tuple(counts.shape)} on {counts.device}")
+    if outside is not None and (tuple(outside.shape) != (C, 3) or outside.dtype != torch.int64 or not outside.is_contiguous()
+                                or outside.device != dev):
+        raise ValueError(f"field_hist: outside must be a contiguous int64 [C, 3] = {(C, 3)} on {dev}, got "
+                         f"{outside.dtype} {tuple(outside.shape)} on {outside.device}")
+    x = x.detach()
+    if not (hip and x.is_cuda and nbins <= HIST_MAX_BINS):
+        _field_hist_torch(x, edges, counts, outside)
+        return counts
+    x = x.contiguous()
+    _lib.check(_lib.load().mk_field_hist(x.data_ptr(), edges.data_ptr(), counts.data_ptr(), _ptr(outside), nbins, T, C, H, W,
+                                         _stream()), "mk_field_hist")
+    return counts
+
+
+# ----------------------------------------------------------------------------
 # cosine of the solar zenith angle (csrc/zenith.hip)
 # ----------------------------------------------------------------------------
 @torch.no_grad()
