@@ -47,7 +47,7 @@ extern "C" int mk_adam_step(float* p, const float* g, float* m, float* v, long l
                             float eps, float weight_decay, int step, void* stream) {
     MK_REQUIRE(p && g && m && v, "null pointer");
     MK_REQUIRE(n > 0 && step >= 1, "bad sizes");
-    MK_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "buffers must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(p, g, m, v), "buffers must be 16-byte aligned");
     AdamArgs a;
     a.lr = lr;
     a.beta1 = beta1;

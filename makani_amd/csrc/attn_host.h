@@ -4,7 +4,6 @@
 #pragma once
 #include "common.h"
 
-#include <cstdint>
 #include <string>
 
 namespace mk::attn {
@@ -32,9 +31,6 @@ struct Family {
     int unit;                       // elements in 16 bytes: every stride is a multiple of it
 };
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 inline int check_head(const char* who, const Family& f, int D) {
     MK_REQUIRE_AS(who, D >= 16 && D <= f.max_head && D % 16 == 0,
                   "head size must be a multiple of 16 in 16 ... " + std::to_string(f.max_head));
@@ -52,7 +48,7 @@ inline int check_operands(const char* who, const Family& f, int n, const void* c
     MK_REQUIRE_AS(who, st != nullptr, "null strides");
     for (int i = 0; i < n; ++i) {
         MK_REQUIRE_AS(who, ptr[i] != nullptr, "null pointer");
-        MK_REQUIRE_AS(who, aligned16(ptr[i]), "operand not 16-byte aligned");
+        MK_REQUIRE_AS(who, mk::aligned<16>(ptr[i]), "operand not 16-byte aligned");
         for (int j = 0; j < 3; ++j)
             MK_REQUIRE_AS(who, st[3 * i + j] >= 0 && st[3 * i + j] % f.unit == 0,
                           "strides must be non-negative multiples of " + std::to_string(f.unit) + " elements");
@@ -82,7 +78,7 @@ int fwd_params(const char* who, const Family& f, ParamsOf<T>& p, const T* q, con
                int Nq, int Nk, int D, const long long* st, float scale) {
     const void* ptr[4] = {q, k, v, o};
     if (int rc = tiled_params(who, f, p, 4, ptr, B, H, Nq, Nk, D, Nq, st, scale)) return rc;
-    MK_REQUIRE_AS(who, aligned4(lse), "lse not 4-byte aligned");
+    MK_REQUIRE_AS(who, mk::aligned<4>(lse), "lse not 4-byte aligned");
     p.q = q, p.k = k, p.v = v, p.o = o, p.lse_out = lse, p.so = str_at(st, 3);
     return 0;
 }
@@ -93,7 +89,7 @@ int delta_params(const char* who, const Family& f, ParamsOf<T>& p, const T* o, c
     if (int rc = check_sizes(who, f, B, H, Nq, 1, D)) return rc;
     const void* ptr[2] = {o, dO};
     if (int rc = check_operands(who, f, 2, ptr, st, D)) return rc;
-    MK_REQUIRE_AS(who, delta != nullptr && aligned4(delta), "delta null or not 4-byte aligned");
+    MK_REQUIRE_AS(who, delta != nullptr && mk::aligned<4>(delta), "delta null or not 4-byte aligned");
     p.o = const_cast<T*>(o), p.dO = dO, p.lse_out = delta;
     p.B = B, p.H = H, p.Nq = Nq, p.D = D;
     p.so = str_at(st, 0), p.sdo = str_at(st, 1);
@@ -105,7 +101,7 @@ int dkv_params(const char* who, const Family& f, ParamsOf<T>& p, const T* q, con
                const float* delta, T* dk, T* dv, int B, int H, int Nq, int Nk, int D, const long long* st, float scale) {
     const void* ptr[6] = {q, k, v, dO, dk, dv};
     if (int rc = tiled_params(who, f, p, 6, ptr, B, H, Nq, Nk, D, Nk, st, scale)) return rc;
-    MK_REQUIRE_AS(who, lse && delta && aligned4(lse) && aligned4(delta), "lse / delta null or not 4-byte aligned");
+    MK_REQUIRE_AS(who, lse && delta && mk::aligned<4>(lse, delta), "lse / delta null or not 4-byte aligned");
     p.q = q, p.k = k, p.v = v, p.dO = dO, p.dk = dk, p.dv = dv, p.lse = lse, p.delta = delta;
     p.sdo = str_at(st, 3), p.sdk = str_at(st, 4), p.sdv = str_at(st, 5);
     return 0;
@@ -116,7 +112,7 @@ int dq_params(const char* who, const Family& f, ParamsOf<T>& p, const T* q, cons
               const float* delta, T* dq, int B, int H, int Nq, int Nk, int D, const long long* st, float scale) {
     const void* ptr[5] = {q, k, v, dO, dq};
     if (int rc = tiled_params(who, f, p, 5, ptr, B, H, Nq, Nk, D, Nq, st, scale)) return rc;
-    MK_REQUIRE_AS(who, lse && delta && aligned4(lse) && aligned4(delta), "lse / delta null or not 4-byte aligned");
+    MK_REQUIRE_AS(who, lse && delta && mk::aligned<4>(lse, delta), "lse / delta null or not 4-byte aligned");
     p.q = q, p.k = k, p.v = v, p.dO = dO, p.dq = dq, p.lse = lse, p.delta = delta;
     p.sdo = str_at(st, 3), p.sdq = str_at(st, 4);
     return 0;

@@ -368,8 +368,6 @@ __global__ __launch_bounds__(256) void chan_layernorm_finish(const float* __rest
     if (lane == 0) gwb[i] = (float)v;
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 long long bwd_grid(long long ntiles) { return ntiles < kBwdGrid ? ntiles : kBwdGrid; }
 
 template <typename TI, typename TO, bool GELU>
@@ -381,7 +379,7 @@ int launch_fwd(const void* x, const float* w, const float* b, void* y, float* st
     const long long grid = ntiles < kFwdGrid ? ntiles : kFwdGrid;
     const long long want = fwd_lds_fixed<TI>() + (long long)C * TP * (long long)sizeof(TI);
     const int use_lds = want <= kLdsMax;
-    const int aligned = P % (16 / (int)sizeof(TI)) == 0 && aligned_to(x, 16) && aligned_to(y, 16);
+    const int aligned = P % (16 / (int)sizeof(TI)) == 0 && mk::aligned<16>(x, y);
     hipLaunchKernelGGL((chan_layernorm_fwd_kernel<TI, TO, GELU>), dim3((unsigned)grid), dim3(kT),
                        (size_t)(use_lds ? want : fwd_lds_fixed<TI>()), st, (const TI*)x, w, b, (TO*)y, stats, C, P, tps, ntiles,
                        eps, use_lds, aligned);
@@ -398,7 +396,7 @@ int launch_bwd(const void* x, const void* gy, const float* stats, const float* w
     const long long fixed = bwd_lds_fixed(TP);
     const long long want = fixed + 4LL * acc_floats(C) + (long long)C * TP * (long long)(sizeof(TX) + sizeof(TG));
     const int use_lds = want <= kLdsMax;
-    const int aligned = P % V == 0 && aligned_to(x, 16) && aligned_to(gy, 16) && aligned_to(gx, 16);
+    const int aligned = P % V == 0 && mk::aligned<16>(x, gy, gx);
     const long long grid = bwd_grid(ntiles);
     hipLaunchKernelGGL((chan_layernorm_bwd_kernel<TX, TG, GELU>), dim3((unsigned)grid), dim3(kT),
                        (size_t)(use_lds ? want : fixed), st, (const TX*)x, (const TG*)gy, stats, w, b, (TX*)gx,
@@ -425,8 +423,8 @@ extern "C" int mk_chan_layernorm_fwd(const void* x, int x_dtype, const float* we
     MK_REQUIRE(B >= 1 && C >= 1 && P >= 1, "bad sizes");
     MK_REQUIRE(C <= (1 << 24) && (long long)B * C * P < (1LL << 40), "field too large");
     MK_REQUIRE((x_dtype == 0 || x_dtype == 1) && (y_dtype == 0 || y_dtype == 1), "dtype must be 0 (fp32) or 1 (bf16)");
-    MK_REQUIRE(aligned_to(x, x_dtype == 0 ? 4 : 2) && aligned_to(y, y_dtype == 0 ? 4 : 2), "field not aligned to its element");
-    MK_REQUIRE(aligned_to(weight, 4) && aligned_to(bias, 4) && aligned_to(stats, 8), "fp32 stream not aligned");
+    MK_REQUIRE(mk::aligned_to(x, x_dtype == 0 ? 4 : 2) && mk::aligned_to(y, y_dtype == 0 ? 4 : 2), "field not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(weight, bias) && mk::aligned<8>(stats), "fp32 stream not aligned");
     MK_REQUIRE(eps >= 0.f, "eps must not be negative");
     hipStream_t st = (hipStream_t)stream;
     const int k = x_dtype * 4 + y_dtype * 2 + (fuse_gelu ? 1 : 0);
@@ -450,10 +448,9 @@ extern "C" int mk_chan_layernorm_bwd(const void* x, int x_dtype, const void* gy,
     MK_REQUIRE(B >= 1 && C >= 1 && P >= 1, "bad sizes");
     MK_REQUIRE(C <= (1 << 24) && (long long)B * C * P < (1LL << 40), "field too large");
     MK_REQUIRE((x_dtype == 0 || x_dtype == 1) && (gy_dtype == 0 || gy_dtype == 1), "dtype must be 0 (fp32) or 1 (bf16)");
-    MK_REQUIRE(aligned_to(x, x_dtype == 0 ? 4 : 2) && aligned_to(gx, x_dtype == 0 ? 4 : 2) &&
-                   aligned_to(gy, gy_dtype == 0 ? 4 : 2), "field not aligned to its element");
-    MK_REQUIRE(aligned_to(weight, 4) && aligned_to(bias, 4) && aligned_to(stats, 8) && aligned_to(workspace, 4) &&
-                   aligned_to(gwb, 4), "fp32 stream not aligned");
+    MK_REQUIRE(mk::aligned_to(x, x_dtype == 0 ? 4 : 2) && mk::aligned_to(gx, x_dtype == 0 ? 4 : 2) &&
+                   mk::aligned_to(gy, gy_dtype == 0 ? 4 : 2), "field not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(weight, bias, workspace, gwb) && mk::aligned<8>(stats), "fp32 stream not aligned");
     hipStream_t st = (hipStream_t)stream;
     const int k = x_dtype * 4 + gy_dtype * 2 + (fuse_gelu ? 1 : 0);
     switch (k) {

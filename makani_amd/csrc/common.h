@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <string>
 
@@ -31,6 +32,14 @@ void set_error(const std::string& msg);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
+
+// Host-side pointer checks.  A null pointer counts as aligned: the checks of optional operands rely on that.
+template <uintptr_t BYTES, class... P> inline bool aligned(const P*... p) {
+    static_assert(BYTES && (BYTES & (BYTES - 1)) == 0, "a power of two");
+    return ((reinterpret_cast<uintptr_t>(p) | ... | uintptr_t{0}) & (BYTES - 1)) == 0;
+}
+// the run-time form, for sizes that depend on a dtype code (`bytes` a power of two); null counts as aligned here too
+inline bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 // Dynamic LDS above 64 KB has to be allowed per kernel AND per device: once for each (instantiation, device) pair, checked.
 // `bytes` is applied by the first call for a pair and not looked at again: a kernel's callers pass one constant, the most

@@ -385,7 +385,7 @@ extern "C" int mk_conv1x1_wgrad_act(const void* gy, const void* x, float* gw, in
     MK_REQUIRE(gy && x && gw, "null pointer");
     MK_REQUIRE(batch > 0 && cout > 0 && cin > 0 && P > 0, "bad sizes");
     MK_REQUIRE((P % 8) == 0, "P = H*W must be a multiple of 8 (16-byte row alignment)");
-    MK_REQUIRE((((uintptr_t)gy | (uintptr_t)x) & 15) == 0, "gy and x must be 16-byte aligned (the tiles are read as uint4)");
+    MK_REQUIRE(mk::aligned<16>(gy, x), "gy and x must be 16-byte aligned (the tiles are read as uint4)");
     MK_REQUIRE(x_act == 0 || x_act == 1, "x_act must be 0 (none) or 1 (exact GELU)");
     MK_REQUIRE(x_act == 0 || cout <= 384, "the activated operand is built for cout <= 384 (one block row covers all of gy)");
     WgradParams p;

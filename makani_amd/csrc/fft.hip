@@ -686,7 +686,7 @@ extern "C" int mk_irfft_affine_add(const float* xf, void* x, int x_dtype, const 
                                    const float* affine, void* stream) {
     MK_REQUIRE(z != nullptr && affine != nullptr, "null pointer");
     MK_REQUIRE(fft_split_applies(nlon, mmax), "the affine-add epilogue exists in the split kernels only");
-    MK_REQUIRE((((uintptr_t)z | (uintptr_t)x) & 15) == 0, "fields must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(z, x), "fields must be 16-byte aligned");
     XfLayout xl;
     if (int e = xf_plain(xf_layout, nlat, mmax, xl)) return e;
     return fft_synthesis(xf, x, x_dtype, twiddles, bc, nlat, nlon, mmax, scale0, scale_m, scale_h, xl,

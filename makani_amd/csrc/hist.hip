@@ -195,9 +195,8 @@ extern "C" int mk_field_hist(const float* x, const double* edges, long long* cou
     MK_REQUIRE(T >= 1 && C >= 1 && H >= 1 && W >= 1, "bad sizes");
     MK_REQUIRE(C <= 65535 && (long long)C * H * W <= 0x7fffffffLL, "C * H * W beyond the 32-bit grid range");
     MK_REQUIRE((long long)(H < kRows ? H : kRows) * W * T <= 0xffffffffLL, "a workgroup's points (rows * W * T) beyond a 32-bit bin");
-    MK_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "32-bit stream not 4-byte aligned");
-    MK_REQUIRE(((reinterpret_cast<uintptr_t>(edges) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(outside)) & 7) == 0,
-               "64-bit stream not 8-byte aligned");
+    MK_REQUIRE(mk::aligned<4>(x), "32-bit stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(edges, counts, outside), "64-bit stream not 8-byte aligned");
     const int R = replicas_for(nbins);
     const size_t lds = (size_t)(nbins + 1) * 4 + (size_t)R * replica_stride(nbins) * 4;
     hipLaunchKernelGGL(field_hist_kernel, dim3((unsigned)mk::ceil_div(H, kRows), (unsigned)C), dim3(kT), lds, (hipStream_t)stream, x,

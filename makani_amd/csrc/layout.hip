@@ -112,7 +112,7 @@ int transpose_add_launch(const char* who, const void* src, const void* addend, v
     const long long tiles_r = mk::ceil_div(R, LT), tiles_c = mk::ceil_div(C, LT);
     MK_REQUIRE_AS(who, tiles_r * tiles_c < 2147483647LL / batch, "grid too large");
     constexpr int V = 16 / (int)sizeof(T);
-    const bool vec = R % V == 0 && C % V == 0 && (((uintptr_t)src | (uintptr_t)addend | (uintptr_t)dst) & 15) == 0;
+    const bool vec = R % V == 0 && C % V == 0 && mk::aligned<16>(src, addend, dst);
     const auto kernel = vec ? transpose_add_kernel<T, true> : transpose_add_kernel<T, false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_r * tiles_c * batch)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const T*>(src), static_cast<const T*>(addend), static_cast<T*>(dst), R, C, (int)tiles_r,
@@ -126,7 +126,8 @@ int layout_check(const char* who, const void* a, const void* b, const void* adde
     MK_REQUIRE_AS(who, dtype == 0 || dtype == 1, "unknown dtype (0 fp32 | 1 bf16)");
     MK_REQUIRE_AS(who, batch >= 1 && n >= 1 && c >= 1, "bad sizes");
     const uintptr_t item = dtype ? 2 : 4;
-    MK_REQUIRE_AS(who, (((uintptr_t)a | (uintptr_t)b | (uintptr_t)addend) & (item - 1)) == 0, "operands must be aligned to their elements");
+    MK_REQUIRE_AS(who, mk::aligned_to(a, item) && mk::aligned_to(b, item) && mk::aligned_to(addend, item),
+                  "operands must be aligned to their elements");
     return 0;
 }
 

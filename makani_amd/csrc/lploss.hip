@@ -204,8 +204,6 @@ void launch_bwd(const T* pred, const float* tar, const float* wrow, const float*
         hipLaunchKernelGGL((geo_lp_bwd_kernel<T, 1>), grid, dim3(kT), 0, st, pred, tar, wrow, g, gpred, rows, H, W);
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 }  // namespace
 
 extern "C" long long mk_geo_lp_workspace(int B, int C, int H) {
@@ -220,9 +218,9 @@ extern "C" int mk_geo_lp_sums(const void* pred, int dtype, const float* tar, con
     MK_REQUIRE(B >= 1 && C >= 1 && C <= 65535 && H >= 1 && W >= 1, "bad sizes");
     MK_REQUIRE((long long)B * C * H * W < (1LL << 40), "field too large");
     MK_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16)");
-    MK_REQUIRE(aligned_to(pred, dtype == 0 ? 4 : 2), "prediction not aligned to its element");
-    MK_REQUIRE(aligned_to(tar, 4) && aligned_to(wrow, 4), "fp32 stream not 4-byte aligned");
-    MK_REQUIRE(aligned_to(workspace, 8) && aligned_to(sums, 8), "fp64 buffer not 8-byte aligned");
+    MK_REQUIRE(mk::aligned_to(pred, dtype == 0 ? 4 : 2), "prediction not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(tar, wrow), "fp32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(workspace, sums), "fp64 buffer not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 0)
         launch_nb<float>((const float*)pred, tar, wrow, workspace, p, B, C, H, W, st);
@@ -243,9 +241,9 @@ extern "C" int mk_geo_lp_bwd(const void* pred, int dtype, const float* tar, cons
     MK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "bad sizes");
     MK_REQUIRE((long long)B * C * H * W < (1LL << 40), "field too large");
     MK_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16)");
-    MK_REQUIRE(aligned_to(pred, dtype == 0 ? 4 : 2) && aligned_to(gpred, dtype == 0 ? 4 : 2),
+    MK_REQUIRE(mk::aligned_to(pred, dtype == 0 ? 4 : 2) && mk::aligned_to(gpred, dtype == 0 ? 4 : 2),
                "prediction or its gradient not aligned to its element");
-    MK_REQUIRE(aligned_to(tar, 4) && aligned_to(wrow, 4) && aligned_to(g, 4), "fp32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<4>(tar, wrow, g), "fp32 stream not 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)B * C * H;
     if (dtype == 0)

@@ -171,10 +171,8 @@ extern "C" int mk_geo_metric_sums(const void* pred, int dtype, const float* tar,
     MK_REQUIRE(B >= 1 && C >= 1 && C <= 65535 && H >= 1 && W >= 1, "bad sizes");
     MK_REQUIRE((long long)B * C * H * W < (1LL << 40), "field too large");
     MK_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16)");
-    MK_REQUIRE((reinterpret_cast<uintptr_t>(pred) & (dtype == 0 ? 3 : 1)) == 0, "prediction not aligned to its element");
-    MK_REQUIRE((reinterpret_cast<uintptr_t>(tar) & 3) == 0 && (reinterpret_cast<uintptr_t>(wrow) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(clim) & 3) == 0,
-               "fp32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned_to(pred, dtype == 0 ? 4 : 2), "prediction not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(tar, wrow, clim), "fp32 stream not 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 0)
         launch_nb<float>((const float*)pred, tar, clim, wrow, workspace, B, C, H, W, st);

@@ -238,14 +238,14 @@ void choose_tile(PatchTile& g) {
 
 // 16-byte accesses on the image side: every tile row starts and ends on a vector
 bool image_vec(const PatchTile& g, int V, const void* img) {
-    if ((uintptr_t)img & 15 || g.W % V) return false;
+    if (!mk::aligned<16>(img) || g.W % V) return false;
     if (g.njt > 1) return g.JT % V == 0 && g.p1 % V == 0;
     return g.nxt == 1 || (g.TX * g.p1) % V == 0;
 }
 
 // ... on the token side: every vector of a token's tile is V consecutive features that start on a vector
 bool token_vec(const PatchTile& g, int V, const void* tok) {
-    if ((uintptr_t)tok & 15 || g.ldt % V) return false;
+    if (!mk::aligned<16>(tok) || g.ldt % V) return false;
     const long long F = (long long)g.C * g.p0 * g.p1;
     if (g.order == 0) {
         if (g.JT == g.p1 && g.IT == g.p0 && ((long long)g.CC * g.p0 * g.p1) % V == 0 && F % V == 0) return true;    // one run per token
@@ -283,7 +283,7 @@ int patch_entry(const char* who, const void* src, int src_dtype, void* dst, int 
     const long long F = (long long)C * p0 * p1;
     MK_REQUIRE_AS(who, F < 2147483647LL, "a token row is too long");
     MK_REQUIRE_AS(who, ldt >= F, "ldt is smaller than the features of a token");
-    MK_REQUIRE_AS(who, ((uintptr_t)img & (img_dtype ? 1 : 3)) == 0 && ((uintptr_t)tok & (tok_dtype ? 1 : 3)) == 0,
+    MK_REQUIRE_AS(who, mk::aligned_to(img, img_dtype ? 2 : 4) && mk::aligned_to(tok, tok_dtype ? 2 : 4),
                   "operands must be aligned to their elements");
     PatchTile g{};
     g.C = C; g.H = H; g.W = W; g.p0 = p0; g.p1 = p1; g.hp = H / p0; g.wp = W / p1; g.order = order; g.ldt = ldt;

@@ -783,13 +783,13 @@ extern "C" int mk_pce_gemm_ex(const void* x, const void* wimg, void* y, const fl
     MK_REQUIRE(x && wimg && y, "null pointer");
     MK_REQUIRE(batch > 0 && M > 0 && K > 0 && P > 0, "bad sizes");
     MK_REQUIRE((P % 8) == 0, "P = H*W must be a multiple of 8 (16-byte row alignment)");
-    MK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)wimg & 15) == 0, "x and the weight image must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(x, wimg), "x and the weight image must be 16-byte aligned");
     PceCfg c;
     MK_REQUIRE(pce_config(M, K, &c), "unsupported shape (K <= 768, M <= 1536)");
     static const int pexp = [] { const char* e = getenv("MK_PCE_EXP"); return e ? atoi(e) : 0; }();
     MK_REQUIRE(!(addend && aux_in), "addend and aux_in are exclusive");
     MK_REQUIRE(!addend_affine || addend, "addend_affine needs an addend");
-    MK_REQUIRE(((uintptr_t)addend_affine & 7) == 0, "addend_affine must be 8-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(addend_affine), "addend_affine must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (rowstats) {
         MK_REQUIRE(c.npass <= 2, "row statistics are built for M <= 768");

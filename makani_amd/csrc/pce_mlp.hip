@@ -796,8 +796,7 @@ extern "C" int mk_pce_mlp(const void* x, const void* wimg, void* y, void* mid_ou
     MK_REQUIRE(mode == 1 || !rowsum_mid, "row sums of the kept field are built for mode 1");
     MK_REQUIRE(batch > 0 && P > 0, "bad sizes");
     MK_REQUIRE((P % 8) == 0, "P = H*W must be a multiple of 8 (16-byte row alignment)");
-    MK_REQUIRE((((uintptr_t)x | (uintptr_t)wimg | (uintptr_t)y | (uintptr_t)mid_out | (uintptr_t)mid_in) & 15) == 0,
-               "fields and the weight image must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(x, wimg, y, mid_out, mid_in), "fields and the weight image must be 16-byte aligned");
     MlpCfg c;
     MK_REQUIRE(mlp_config(M, Hd, K1, &c), "unsupported shape (K1 <= 384, Hd <= 768, M <= 384)");
     MK_REQUIRE((long long)(M > 32 ? M : 32) * P * 2 < (1LL << 31), "field too large for the 32-bit store offsets (M * P * 2 bytes per batch item)");

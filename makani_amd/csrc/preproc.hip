@@ -236,8 +236,6 @@ dim3 row_grid(long long rows) {
     return dim3((unsigned)(want < kGrid ? want : kGrid));
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 int check_shape(const Shape& s, const char** why) {
     if (!(s.B >= 1 && s.T >= 1 && s.C >= 1 && s.Cu >= 0 && s.Cs >= 0 && s.H >= 1 && s.W >= 1)) {
         *why = "bad sizes";
@@ -268,9 +266,9 @@ extern "C" int mk_input_assemble(const void* x, int x_dtype, const float* u, con
     MK_REQUIRE(n_mask >= 0 && n_mask <= kMaxMask, "bad number of masked channels");
     MK_REQUIRE(n_mask == 0 || mask_chans, "null pointer (masked channels)");
     MK_REQUIRE(n_mask == 0 || (mask_src >= 0 && mask_src < Cs), "mask source is not a static channel");
-    MK_REQUIRE(aligned_to(x, x_dtype == 0 ? 4 : 2) && aligned_to(out, out_dtype == 0 ? 4 : 2), "x or output not aligned to its element");
-    MK_REQUIRE(aligned_to(u, 4) && aligned_to(stat, 4) && aligned_to(mean, 4) && aligned_to(std, 4) && aligned_to(mask_chans, 4),
-               "fp32 / int32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned_to(x, x_dtype == 0 ? 4 : 2) && mk::aligned_to(out, out_dtype == 0 ? 4 : 2),
+               "x or output not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(u, stat, mean, std, mask_chans), "fp32 / int32 stream not 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)B * ((long long)T * (C + Cu) + Cs) * H;
     const dim3 grid = row_grid(rows);
@@ -299,8 +297,8 @@ extern "C" int mk_input_assemble_bwd(const void* gout, int g_dtype, const float*
     MK_REQUIRE(n_mask >= 0 && n_mask <= kMaxMask, "bad number of masked channels");
     MK_REQUIRE(n_mask == 0 || mask_chans, "null pointer (masked channels)");
     MK_REQUIRE(n_mask == 0 || (mask_src >= 0 && mask_src < Cs), "mask source is not a static channel");
-    MK_REQUIRE(aligned_to(gout, g_dtype == 0 ? 4 : 2) && aligned_to(gx, x_dtype == 0 ? 4 : 2), "gradient not aligned to its element");
-    MK_REQUIRE(aligned_to(stat, 4) && aligned_to(std, 4) && aligned_to(mask_chans, 4), "fp32 / int32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned_to(gout, g_dtype == 0 ? 4 : 2) && mk::aligned_to(gx, x_dtype == 0 ? 4 : 2), "gradient not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(stat, std, mask_chans), "fp32 / int32 stream not 4-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long long rows = (long long)B * T * C * H;
     const dim3 grid = row_grid(rows);
@@ -330,9 +328,9 @@ extern "C" int mk_history_sums(const void* x, int x_dtype, const float* u, const
     MK_REQUIRE((Cu == 0) == (u == nullptr), "u must be given exactly when Cu > 0");
     MK_REQUIRE(x_dtype == 0 || x_dtype == 1, "x dtype must be 0 (fp32) or 1 (bf16)");
     MK_REQUIRE(C + Cu <= 65535 && B <= 65535, "too many channels or samples for one grid");
-    MK_REQUIRE(aligned_to(x, x_dtype == 0 ? 4 : 2), "x not aligned to its element");
-    MK_REQUIRE(aligned_to(u, 4) && aligned_to(wt, 4), "fp32 stream not 4-byte aligned");
-    MK_REQUIRE(aligned_to(workspace, 8) && aligned_to(sums, 8), "fp64 buffer not 8-byte aligned");
+    MK_REQUIRE(mk::aligned_to(x, x_dtype == 0 ? 4 : 2), "x not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(u, wt), "fp32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(workspace, sums), "fp64 buffer not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int nslab = mk::ceil_div(H, kRows);
     const dim3 grid((unsigned)nslab, (unsigned)(C + Cu), (unsigned)B);

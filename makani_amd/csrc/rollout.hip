@@ -325,8 +325,6 @@ void launch_nb(const Args& a, dim3 grid, hipStream_t st) {
     else launch_score<T, 2>(a, grid, st);
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
-
 }  // namespace
 
 extern "C" long long mk_rollout_tail_workspace(int B, int C, int H) {
@@ -359,13 +357,11 @@ extern "C" int mk_rollout_tail(const void* yn, int dtype, const float* mean, con
     MK_REQUIRE(K >= 0 && K <= kMaxList, "bad number of emitted channels");
     MK_REQUIRE(K == 0 || (emit && emit_chans), "null pointer (emitted channels)");
     MK_REQUIRE(K > 0 || (!emit_scale && !emit_shift), "emit scale or shift without emitted channels");
-    MK_REQUIRE(aligned_to(yn, dtype == 0 ? 4 : 2), "model output not aligned to its element");
-    MK_REQUIRE(aligned_to(mean, 4) && aligned_to(std, 4) && aligned_to(mask, 4) && aligned_to(mask_chans, 4) && aligned_to(x_last, 4) &&
-                   aligned_to(scale, 4) && aligned_to(hold_chans, 4) && aligned_to(pred, 4) && aligned_to(tar, 4) &&
-                   aligned_to(clim, 4) && aligned_to(wrow, 4) && aligned_to(err_map, 4) && aligned_to(emit, 4) &&
-                   aligned_to(emit_chans, 4) && aligned_to(emit_scale, 4) && aligned_to(emit_shift, 4),
+    MK_REQUIRE(mk::aligned_to(yn, dtype == 0 ? 4 : 2), "model output not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(mean, std, mask, mask_chans, x_last, scale, hold_chans, pred, tar, clim, wrow, err_map, emit, emit_chans,
+                              emit_scale, emit_shift),
                "fp32 / int32 stream not 4-byte aligned");
-    MK_REQUIRE(aligned_to(workspace, 8) && aligned_to(sums, 8), "fp64 buffer not 8-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(workspace, sums), "fp64 buffer not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     Args g;
     g.yn = yn, g.mean = mean, g.std = std, g.mask = mask, g.mask_chans = mask_chans, g.n_mask = n_mask;

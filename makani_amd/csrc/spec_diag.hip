@@ -251,7 +251,7 @@ size_t lds_bytes(int tp, int bs, int n0, int n1) {
 int sd_setup(const char* who, SdParams& p, int& vec, size_t& lds, const void* a, const void* b, const void* out, const void* w,
              int lloc, int mloc, int batch, int cin, int cout, int l_off, int m_off, int dense) {
     MK_REQUIRE_AS(who, a && b && out, "null pointer");
-    MK_REQUIRE_AS(who, ((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) % 8 == 0, "operands must be 8-byte aligned");
+    MK_REQUIRE_AS(who, mk::aligned<8>(a, b, out), "operands must be 8-byte aligned");
     MK_REQUIRE_AS(who, lloc > 0 && mloc > 0 && batch > 0 && cin > 0 && cout > 0, "bad sizes");
     MK_REQUIRE_AS(who, l_off >= 0 && m_off >= 0 && (dense == 0 || dense == 1), "bad offsets / dense flag");
     MK_REQUIRE_AS(who, (long long)l_off + lloc < 2147483647LL && (long long)m_off + mloc < 2147483647LL,
@@ -259,7 +259,7 @@ int sd_setup(const char* who, SdParams& p, int& vec, size_t& lds, const void* a,
     // the two LDS rows of one position and one batch item bound the channel counts (and keep cin * cout, batch * chan in int)
     MK_REQUIRE_AS(who, (long long)cin + cout <= 2500, "cin + cout beyond what the LDS rows of two positions hold (2500)");
     MK_REQUIRE_AS(who, batch <= 65536, "batch beyond the index range (65536)");
-    vec = (mloc % 2 == 0 && (uintptr_t)w % 16 == 0) ? 2 : 1;
+    vec = (mloc % 2 == 0 && mk::aligned<16>(w)) ? 2 : 1;
     int tp = STP, bs = batch < SB ? batch : SB;
     while (tp > vec && tp / 2 >= mloc) tp /= 2;
     while (tp > 8 && tp > vec && lds_bytes(tp, bs, cin, cout) > SLDS) tp /= 2;

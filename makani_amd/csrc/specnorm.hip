@@ -99,8 +99,6 @@ __global__ __launch_bounds__(kT) void degree_power_bwd_kernel(const float2* __re
     gc[i] = out;
 }
 
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 bool sizes_ok(int L, int M, int BC, int l_off, int m_off) {
     return L >= 1 && M >= 1 && BC >= 1 && l_off >= 0 && m_off >= 0 && (long long)l_off + L < (1LL << 30) &&
            (long long)m_off + M < (1LL << 30) && (long long)L * M * BC < (1LL << 38);
@@ -117,7 +115,7 @@ extern "C" int mk_degree_power(const float* c, double* workspace, double* P, int
                                void* stream) {
     MK_REQUIRE(c && workspace && P, "null pointer");
     MK_REQUIRE(sizes_ok(L, M, BC, l_off, m_off), "bad sizes");
-    MK_REQUIRE(aligned8(c) && aligned8(workspace) && aligned8(P), "buffer not 8-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(c, workspace, P), "buffer not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int nchunk = mk::ceil_div(M, kChunk);
     const long long nparts = (long long)L * nchunk * BC;
@@ -135,7 +133,7 @@ extern "C" int mk_degree_power_bwd(const float* c, const double* gP, float* gc, 
                                    void* stream) {
     MK_REQUIRE(c && gP && gc, "null pointer");
     MK_REQUIRE(sizes_ok(L, M, BC, l_off, m_off), "bad sizes");
-    MK_REQUIRE(aligned8(c) && aligned8(gP) && aligned8(gc), "buffer not 8-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(c, gP, gc), "buffer not 8-byte aligned");
     const long long n = (long long)L * M * BC;
     hipLaunchKernelGGL(degree_power_bwd_kernel, dim3((unsigned)mk::ceil_div_ll(n, kT)), dim3(kT), 0, (hipStream_t)stream,
                        (const float2*)c, gP, (float2*)gc, n, M, BC, l_off, m_off);

@@ -302,11 +302,8 @@ extern "C" int mk_field_stats(const float* x, const float* prev, const float* pi
     MK_REQUIRE(n_wind == 0 || (wind_u && wind_v && wsums), "wind pairs without wind_u, wind_v and wsums");
     MK_REQUIRE(T >= 1 && C >= 1 && H >= 1 && W >= 1, "bad sizes");
     MK_REQUIRE(C <= 65535 && (long long)C * H * W <= 0x7fffffffLL, "C * H * W beyond the 32-bit grid range");
-    MK_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(pivot) |
-                 reinterpret_cast<uintptr_t>(wrow) | reinterpret_cast<uintptr_t>(minmax) | reinterpret_cast<uintptr_t>(wind_u) |
-                 reinterpret_cast<uintptr_t>(wind_v)) & 3) == 0, "32-bit stream not 4-byte aligned");
-    MK_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(sums) | reinterpret_cast<uintptr_t>(tsum) |
-                 reinterpret_cast<uintptr_t>(wsums)) & 7) == 0, "fp64 stream not 8-byte aligned");
+    MK_REQUIRE(mk::aligned<4>(x, prev, pivot, wrow, minmax, wind_u, wind_v), "32-bit stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(workspace, sums, tsum, wsums), "fp64 stream not 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int nslab = mk::ceil_div(H, kRows);
     double* psum = workspace;

@@ -421,8 +421,6 @@ __global__ __launch_bounds__(kT) void toklinear_wgrad_sum_kernel(const float* ws
 }
 
 // ---- validation ------------------------------------------------------------------------------------------------------------
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int check_sizes(const char* who, long long R, int O, int I) {
     MK_REQUIRE_AS(who, R >= 1 && O >= 8 && I >= 8, "bad sizes");
     MK_REQUIRE_AS(who, O % 8 == 0 && I % 8 == 0, "feature counts must be multiples of 8");
@@ -432,7 +430,7 @@ int check_sizes(const char* who, long long R, int O, int I) {
 // a [rows, len] operand: a 16-byte-aligned base pointer and a row stride in elements, a multiple of 8 of at least len
 int check_operand(const char* who, const void* ptr, long long ld, int len) {
     MK_REQUIRE_AS(who, ptr != nullptr, "null pointer");
-    MK_REQUIRE_AS(who, aligned16(ptr), "operand not 16-byte aligned");
+    MK_REQUIRE_AS(who, mk::aligned<16>(ptr), "operand not 16-byte aligned");
     MK_REQUIRE_AS(who, ld % 8 == 0, "row strides must be multiples of 8 elements");
     MK_REQUIRE_AS(who, ld >= len, "row stride smaller than the row length");
     return 0;
@@ -484,7 +482,7 @@ extern "C" int mk_token_linear_fwd(const void* x, long long ldx, const void* w, 
     if (int rc = check_sizes(__func__, R, O, I)) return rc;
     if (int rc = check_operand(__func__, x, ldx, I)) return rc;
     if (int rc = check_operand(__func__, w, ldw, I)) return rc;
-    MK_REQUIRE(bias == nullptr || aligned16(bias), "bias not 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(bias), "bias not 16-byte aligned");
     int mode;
     if (y && !act && !pre && !addend && !out_f32 && !aux) mode = kPlain;
     else if (act && !y && !addend && !out_f32 && !aux) mode = kGelu;
@@ -552,9 +550,9 @@ extern "C" int mk_token_linear_wgrad(const void* dy, long long lddy, const void*
     if (int rc = check_operand(__func__, dy, lddy, O)) return rc;
     if (int rc = check_operand(__func__, x, ldx, I)) return rc;
     if (int rc = check_operand(__func__, dw, lddw, I)) return rc;
-    MK_REQUIRE(db == nullptr || aligned16(db), "db not 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(db), "db not 16-byte aligned");
     const int s = resolve_slabs(R, O, I, slabs);
-    MK_REQUIRE(s == 1 || (workspace != nullptr && aligned16(workspace)), "workspace null or not 16-byte aligned");
+    MK_REQUIRE(s == 1 || (workspace != nullptr && mk::aligned<16>(workspace)), "workspace null or not 16-byte aligned");
     WgParams p{};
     p.dy = (const bf16*)dy, p.x = (const bf16*)x, p.lddy = lddy, p.ldx = ldx, p.R = R, p.O = O, p.I = I;
     p.n_ot = mk::ceil_div(O, kTO), p.n_it = mk::ceil_div(I, kTI);

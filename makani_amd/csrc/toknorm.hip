@@ -398,10 +398,9 @@ __global__ __launch_bounds__(256) void tok_finish(const float* __restrict__ ws, 
     if (lane == 0) gwb[i] = (float)v;
 }
 
-bool aligned_to(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 // an absent tensor restricts nothing
-bool elem_ok(const void* p, int bf) { return aligned_to(p, bf ? 2 : 4); }
-bool vec_ok(const void* p, long long ld, int bf) { return !p || (aligned_to(p, 16) && (ld * (bf ? 2 : 4)) % 16 == 0); }
+bool elem_ok(const void* p, int bf) { return mk::aligned_to(p, bf ? 2 : 4); }
+bool vec_ok(const void* p, long long ld, int bf) { return !p || (mk::aligned<16>(p) && (ld * (bf ? 2 : 4)) % 16 == 0); }
 
 long long min_ll(long long a, long long b) { return a < b ? a : b; }
 long long bwd_grid(long long rows, long long L) {
@@ -474,12 +473,12 @@ extern "C" int mk_token_layernorm_fwd(const void* x, int x_dtype, long long x_ld
                "a row stride is shorter than the row");
     MK_REQUIRE(elem_ok(x, x_dtype) && elem_ok(r, r_dtype) && elem_ok(y, y_dtype) && elem_ok(y2, 1) && elem_ok(s_out, s_dtype),
                "tensor not aligned to its element");
-    MK_REQUIRE(aligned_to(weight, 4) && aligned_to(bias, 4) && aligned_to(stats, 4), "fp32 stream not aligned");
+    MK_REQUIRE(mk::aligned<4>(weight, bias, stats), "fp32 stream not aligned");
     MK_REQUIRE(eps >= 0.f, "eps must not be negative");
     const FwdArgs a{{x, x_ld, x_dtype}, {r, r_ld, r_dtype}, weight, bias, {y, y_ld, y_dtype}, {y2, y2_ld, 1}, {s_out, s_ld, s_dtype},
                     stats, rows, (int)L, eps};
     const bool vec = L % kV == 0 && vec_ok(x, x_ld, x_dtype) && vec_ok(r, r_ld, r_dtype) && vec_ok(y, y_ld, y_dtype) &&
-                     vec_ok(y2, y2_ld, 1) && vec_ok(s_out, s_ld, s_dtype) && aligned_to(weight, 16) && aligned_to(bias, 16);
+                     vec_ok(y2, y2_ld, 1) && vec_ok(s_out, s_ld, s_dtype) && mk::aligned<16>(weight, bias);
     return vec ? launch_fwd<true>(a, (hipStream_t)stream) : launch_fwd<false>(a, (hipStream_t)stream);
 }
 
@@ -498,12 +497,11 @@ extern "C" int mk_token_layernorm_bwd(const void* x, int x_dtype, long long x_ld
                "a row stride is shorter than the row");
     MK_REQUIRE(elem_ok(x, x_dtype) && elem_ok(gx, x_dtype) && elem_ok(r, r_dtype) && elem_ok(gr, r_dtype) && elem_ok(gy, gy_dtype) &&
                    elem_ok(gy2, 1) && elem_ok(gs, gs_dtype), "tensor not aligned to its element");
-    MK_REQUIRE(aligned_to(weight, 4) && aligned_to(stats, 4) && aligned_to(workspace, 4) && aligned_to(gwb, 4),
-               "fp32 stream not aligned");
+    MK_REQUIRE(mk::aligned<4>(weight, stats, workspace, gwb), "fp32 stream not aligned");
     const BwdArgs a{{x, x_ld, x_dtype}, {r, r_ld, r_dtype}, {gy, gy_ld, gy_dtype}, {gy2, gy2_ld, 1}, {gs, gs_ld, gs_dtype}, stats, weight,
                     {gx, x_ld, x_dtype}, {gr, r_ld, r_dtype}, gwb ? workspace : nullptr, rows, (int)L};
     const bool vec = L % kV == 0 && vec_ok(x, x_ld, x_dtype) && vec_ok(gx, x_ld, x_dtype) && vec_ok(r, r_ld, r_dtype) &&
                      vec_ok(gr, r_ld, r_dtype) && vec_ok(gy, gy_ld, gy_dtype) && vec_ok(gy2, gy2_ld, 1) && vec_ok(gs, gs_ld, gs_dtype) &&
-                     aligned_to(weight, 16) && (!gwb || aligned_to(workspace, 16));
+                     mk::aligned<16>(weight) && (!gwb || mk::aligned<16>(workspace));
     return vec ? launch_bwd<true>(a, gwb, (hipStream_t)stream) : launch_bwd<false>(a, gwb, (hipStream_t)stream);
 }

@@ -105,7 +105,7 @@ static int conv_x3_launch(const float* a, long long lda, const float* b, long lo
     MK_REQUIRE(a && b && c, "null pointer");
     MK_REQUIRE(M > 0 && K > 0 && N > 0 && batch > 0, "bad sizes");
     MK_REQUIRE(mode >= 0 && mode <= 3, "mode must be 0 (store), 1 (accumulate), 2 (weight gradient) or 3 (store with bias / GELU)");
-    MK_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(a, b, c), "operands must be 16-byte aligned");
     ConvX3Params p;
     p.a = a; p.b = b; p.c = c;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc;

@@ -108,7 +108,7 @@ static int latdft_launch(bool inv, const float* src, const float* table, float* 
                          void* stream) {
     MK_REQUIRE(src && table && dst, "null pointer");
     MK_REQUIRE(nlat >= 2 && lmax >= 2 && lmax <= nlat && ncols >= 1, "need nlat >= 2, 2 <= lmax <= nlat and at least one column");
-    MK_REQUIRE(((uintptr_t)table & 15) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 7) == 0,
+    MK_REQUIRE(mk::aligned<16>(table) && mk::aligned<8>(src, dst),
                "the table must be 16-byte aligned, the complex operands 8-byte aligned");
     const long long KP = ((long long)nlat + 3) / 4 * 4, LP = ((long long)lmax + 3) / 4 * 4;
     MK_REQUIRE(mk_latdft_table_len(nlat, lmax) * 4 < (1LL << 31), "table over 2^31 bytes");

@@ -780,7 +780,7 @@ static int spec_mix_check(const void* a, const void* b, const void* c, int lloc,
     MK_REQUIRE(lloc > 0 && mloc > 0 && batch > 0 && cin > 0 && cout > 0, "bad sizes");
     MK_REQUIRE(l_off >= 0 && m_off >= 0, "negative shard offset");
     MK_REQUIRE(cin % 2 == 0 && cout % 2 == 0, "the spectral channel mix needs even channel counts");
-    MK_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(a, b, c), "operands must be 16-byte aligned");
     const long long cmax = cin > cout ? cin : cout;
     MK_REQUIRE((long long)mloc * batch * cmax * 8 < (1LL << 31) && 33LL * cmax * 4 < (1LL << 31),
                "one degree of the spectrum must stay below 2^31 bytes");
@@ -829,7 +829,7 @@ static int spec_cmlp_check(const void* a, const void* b, const void* c, int lloc
 extern "C" int mk_spec_cmlp_fwd(const float* x, const float* w, const float* bias, float* y, int lloc, int mloc, int batch, int cin,
                                 int cout, int l_off, int m_off, int per_degree, int act, void* stream) {
     if (int e = spec_cmlp_check(x, w, y, lloc, mloc, batch, cin, cout, l_off, m_off, per_degree, act)) return e;
-    MK_REQUIRE(((uintptr_t)bias & 7) == 0, "the bias must be 8-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(bias), "the bias must be 8-byte aligned");
     PanelParams p = panel_params(x, w, y, lloc, mloc, batch, cin, cout, l_off, m_off, mloc * batch, cout, per_degree);
     p.bias = bias;
     p.act = act;
@@ -839,7 +839,7 @@ extern "C" int mk_spec_cmlp_fwd(const float* x, const float* w, const float* bia
 extern "C" int mk_spec_cmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int lloc, int mloc, int batch, int cin,
                                   int cout, int l_off, int m_off, int per_degree, int act, void* stream) {
     if (int e = spec_cmlp_check(gy, w, gx, lloc, mloc, batch, cin, cout, l_off, m_off, per_degree, act)) return e;
-    MK_REQUIRE(((uintptr_t)a & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(a), "operands must be 16-byte aligned");
     MK_REQUIRE(a == nullptr || act != 0, "a mask operand needs an activation mode (1 real | 2 cartesian)");
     PanelParams p = panel_params(gy, w, gx, lloc, mloc, batch, cin, cout, l_off, m_off, mloc * batch, cin, per_degree);
     p.aux = a;
@@ -862,7 +862,7 @@ extern "C" int mk_spec_cmlp_wgrad(const float* x, const float* gy, float* gw, vo
     p.G = cmlp_group_size(lloc, cin, cout);
     p.ngroups = mk::ceil_div(lloc, p.G);
     if (p.ngroups > 1) {
-        MK_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "the shared weight gradient needs its 16-byte aligned workspace");
+        MK_REQUIRE(workspace && mk::aligned<16>(workspace), "the shared weight gradient needs its 16-byte aligned workspace");
         p.dst = static_cast<float*>(workspace);
     }
     if (int e = x3_launch(__func__, spec_cmlp_wgrad_shared_kernel, grid_blocks(p.ngroups, p.tiles_m, p.tiles_n), stream, p)) return e;
@@ -897,7 +897,7 @@ static int spec_bdmlp_check(const void* a, const void* b, const void* c, int row
     MK_REQUIRE(a && b && c, "null pointer");
     MK_REQUIRE(rows > 0 && nb > 0 && ib > 0 && ob > 0, "bad sizes");
     MK_REQUIRE(ib % 2 == 0 && ob % 2 == 0, "the block MLP needs even block sizes (block offsets must stay 16-byte aligned)");
-    MK_REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(a, b, c), "operands must be 16-byte aligned");
     const long long cmax = (long long)nb * (ib > ob ? ib : ob);
     // the stagers' 32-bit byte offsets span one row tile of a field (129 rows) and one block's weight panel
     MK_REQUIRE(129LL * cmax * 8 < (1LL << 31) && (long long)ib * ob * 8 < (1LL << 31),
@@ -926,7 +926,7 @@ extern "C" int mk_spec_bdmlp_fwd_bias(const float* x, const float* w, const floa
                                       int act, float lambda, void* stream) {
     if (!bias) return mk_spec_bdmlp_fwd(x, w, y, rows, nb, ib, ob, act, lambda, stream);
     if (int e = spec_bdmlp_check(x, w, y, rows, nb, ib, ob)) return e;
-    MK_REQUIRE(((uintptr_t)bias & 7) == 0, "the complex bias must be 8-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(bias), "the complex bias must be 8-byte aligned");
     MK_REQUIRE(act == 0 || act == 2 || act == 3, "unknown activation (0 none | 2 cartesian ReLU | 3 soft-shrink)");
     MK_REQUIRE(act != 3 || lambda >= 0.f, "the soft-shrink threshold must not be negative");
     BlockParams p = bdmlp_params(x, w, y, rows, nb, ib, ob, rows, ob);
@@ -941,7 +941,7 @@ extern "C" int mk_spec_bdmlp_fwd_bias(const float* x, const float* w, const floa
 extern "C" int mk_spec_bdmlp_dgrad(const float* gy, const float* w, const float* a, float* gx, int rows, int nb, int ib, int ob,
                                    int act, void* stream) {
     if (int e = spec_bdmlp_check(gy, w, gx, rows, nb, ib, ob)) return e;
-    MK_REQUIRE(((uintptr_t)a & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(a), "operands must be 16-byte aligned");
     MK_REQUIRE(act == 0 || act == 2, "unknown mask mode (0 none | 2 cartesian ReLU)");
     MK_REQUIRE((a != nullptr) == (act == 2), "the mask operand and the mask mode go together");
     BlockParams p = bdmlp_params(gy, w, gx, rows, nb, ib, ob, rows, ib);
@@ -966,7 +966,7 @@ extern "C" int mk_spec_bdmlp_wgrad(const float* x, const float* gy, float* gw, v
     MK_REQUIRE((p.rg + 16LL) * cmax * 8 < (1LL << 31), "one row group of the spectrum must stay below 2^31 bytes");
     MK_REQUIRE((long long)nb * p.ngroups < 2147483647LL, "too many row groups");
     if (p.ngroups > 1) {
-        MK_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0, "the block weight gradient needs its 16-byte aligned workspace");
+        MK_REQUIRE(workspace && mk::aligned<16>(workspace), "the block weight gradient needs its 16-byte aligned workspace");
         p.dst = static_cast<float*>(workspace);
     }
     if (int e = x3_launch(__func__, spec_bdmlp_wgrad_kernel, grid_blocks(nb * p.ngroups, p.tiles_m, p.tiles_n), stream, p)) return e;
@@ -982,7 +982,7 @@ extern "C" int mk_spec_bdmlp_wgrad(const float* x, const float* gy, float* gw, v
 extern "C" int mk_spec_bdmlp_mask(const float* gy, const float* s, float* out, long long n, void* stream) {
     MK_REQUIRE(gy && s && out, "null pointer");
     MK_REQUIRE(n > 0 && n % 4 == 0, "the element count must be a positive multiple of 4 floats");
-    MK_REQUIRE((((uintptr_t)gy | (uintptr_t)s | (uintptr_t)out) & 15) == 0, "operands must be 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(gy, s, out), "operands must be 16-byte aligned");
     const long long nblk = mk::ceil_div_ll(n / 4, 256LL);
     MK_REQUIRE(nblk < 2147483647LL, "grid too large");
     hipLaunchKernelGGL(spec_bdmlp_mask_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,

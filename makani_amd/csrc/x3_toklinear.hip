@@ -176,13 +176,11 @@ __global__ __launch_bounds__(256) void toklinear_x3_finish_kernel(const float* _
     }
 }
 
-bool tok_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // a [rows][len] fp32 operand: a 16-byte-aligned base pointer and a row stride in elements, a multiple of 4 of at least len;
 // `rows_in_tile`: the rows that one stager's 32-bit byte offsets span (128 tile rows, or the 32 rows of a k-step of a k-major operand)
 int tok_operand(const char* who, const void* ptr, long long ld, int len, int rows_in_tile) {
     MK_REQUIRE_AS(who, ptr != nullptr, "null pointer");
-    MK_REQUIRE_AS(who, tok_aligned16(ptr), "operand not 16-byte aligned");
+    MK_REQUIRE_AS(who, mk::aligned<16>(ptr), "operand not 16-byte aligned");
     MK_REQUIRE_AS(who, ld % 4 == 0, "row strides must be multiples of 4 elements");
     MK_REQUIRE_AS(who, ld >= len, "row stride smaller than the row length");
     MK_REQUIRE_AS(who, (rows_in_tile + 1) * ld * 4 < (1LL << 31), "row stride too large for the 32-bit offsets of one tile");
@@ -237,7 +235,7 @@ extern "C" int mk_token_linear_x3_fwd(const float* x, long long x_ld, const floa
         if (int rc = tok_operand(__func__, addend, addend_ld, O, 0)) return rc;
     if (aux)
         if (int rc = tok_operand(__func__, aux, aux_ld, O, 0)) return rc;
-    MK_REQUIRE(bias == nullptr || tok_aligned16(bias), "bias not 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(bias), "bias not 16-byte aligned");
     MK_REQUIRE(mk::ceil_div_ll(R, XM) < 2147483647LL / 2, "too many rows");
     TokFwdParams p{};
     p.x = x, p.w = w, p.bias = bias, p.addend = addend, p.aux = aux, p.y = y, p.pre = pre;
@@ -263,10 +261,10 @@ extern "C" int mk_token_linear_x3_wgrad(const float* dy, long long dy_ld, const 
     if (int rc = tok_operand(__func__, dy, dy_ld, O, XK)) return rc;
     if (int rc = tok_operand(__func__, x, x_ld, I, XK)) return rc;
     if (int rc = tok_operand(__func__, dw, dw_ld, I, 0)) return rc;
-    MK_REQUIRE(db == nullptr || tok_aligned16(db), "db not 16-byte aligned");
+    MK_REQUIRE(mk::aligned<16>(db), "db not 16-byte aligned");
     TokWgParams p{};
     tok_slabs((int)R, O, I, slabs, p.kslab, p.nslab);
-    MK_REQUIRE((p.nslab == 1 && db == nullptr) || (ws != nullptr && tok_aligned16(ws)), "workspace null or not 16-byte aligned");
+    MK_REQUIRE((p.nslab == 1 && db == nullptr) || (ws != nullptr && mk::aligned<16>(ws)), "workspace null or not 16-byte aligned");
     float* panels = static_cast<float*>(ws);
     const long long panel = (long long)O * I;
     double* part = reinterpret_cast<double*>(panels + (p.nslab > 1 ? p.nslab * panel : 0));

@@ -83,8 +83,6 @@ __global__ __launch_bounds__(kT) void cos_zenith_kernel(const float* __restrict_
     }
 }
 
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 }  // namespace
 
 extern "C" int mk_cos_zenith(const float* eph, const float* sin_lat, const float* cos_lat, const float* lon_rad, float* out,
@@ -93,8 +91,7 @@ extern "C" int mk_cos_zenith(const float* eph, const float* sin_lat, const float
     MK_REQUIRE(n <= (1LL << 31) && (double)n * H * W < (double)(1LL << 40), "field too large");
     if (n == 0) return 0;
     MK_REQUIRE(eph && sin_lat && cos_lat && lon_rad && out, "null pointer");
-    MK_REQUIRE(aligned4(eph) && aligned4(sin_lat) && aligned4(cos_lat) && aligned4(lon_rad) && aligned4(out),
-               "fp32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<4>(eph, sin_lat, cos_lat, lon_rad, out), "fp32 stream not 4-byte aligned");
     const int ntile = mk::ceil_div(W, kTile);
     int R = kRowsMax;
     while (R > kRowsMin && n * mk::ceil_div(H, R) * ntile < kWant) R /= 2;

@@ -207,8 +207,7 @@ class DistributedRealSHT(_DistSHTBase):
     def forward(self, x):
         if x.dim() != 4:
             raise ValueError("DistributedRealSHT expects [B, C, nlat_loc, nlon_loc]")
-        if x.dtype not in (torch.float32, torch.bfloat16):
-            x = x.float()
+        x = ops._lowp(x)
         B, C = x.shape[:2]
         c = ops.spec_unpack(self.forward_packed(x.contiguous()), self.l_off, self.m_off)
         return c.reshape(B, C, self.lmax_local, self.mmax_local)

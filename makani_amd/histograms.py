@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import comm
+from . import comm, ops
 
 KEYS = ("edges", "data", "outside", "count")
 
@@ -32,7 +32,6 @@ class DatasetHistograms:
     rank's rows and columns and ``shard_reduce`` combines the shards."""
 
     def __init__(self, num_channels, mins, maxs, nbins=100, edge_dtype="float32"):
-        from . import ops
         self.C = int(num_channels)
         lo, hi = np.asarray(mins, dtype=np.float64).reshape(-1), np.asarray(maxs, dtype=np.float64).reshape(-1)
         if lo.size != self.C or hi.size != self.C:
@@ -57,7 +56,6 @@ class DatasetHistograms:
         further replay of the graph needs ``count(T)``."""
         if batch.dim() != 4 or batch.shape[1] != self.C or batch.shape[0] < 1:
             raise ValueError(f"DatasetHistograms.update: batch {tuple(batch.shape)} is not [T, {self.C}, H, W]")
-        from . import ops
         batch = batch.float()
         if self.device is None:
             self._alloc(batch.device)

@@ -29,7 +29,7 @@ Deviations from the reference (a fork with local edits), keeping the evident int
 import torch
 import torch.distributed as dist
 
-from . import comm
+from . import comm, ops
 from .mappings import gather_from_parallel_region
 from .distributed import compute_split_shapes
 from .stepper import _engine_input_dtype
@@ -139,7 +139,6 @@ class Rollout:
 
     def _step(self, inpt, targ, emit):
         """assemble, the model and the tail: ``(pred, sums, emitted)``; updates the map when ``targ`` is given."""
-        from . import ops
         pp = self.preprocessor
         inpans = pp.assemble(inpt, out_dtype=_engine_input_dtype(self.model, inpt))
         yn = self.model(inpans)

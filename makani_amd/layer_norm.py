@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import comm
+from . import comm, ops
 from .mappings import copy_to_parallel_region, gather_from_parallel_region
 
 
@@ -60,7 +60,6 @@ class DistributedInstanceNorm2d(nn.Module):
         return self._counts[key]
 
     def forward(self, x, fuse_gelu=False, row_sums=None):
-        from . import ops
         if x.is_cuda and x.dim() == 4 and ops.pointwise_supported(x) and comm.get_size("spatial") > 1:
             # HIP path: local row sums -> one all-reduce of [B*C, 2] doubles -> apply (+ fused GELU); same two
             # streaming passes as the single-GPU norm instead of ~10 elementwise torch passes in fp32
@@ -109,7 +108,6 @@ class DistributedLayerNorm(nn.Module):
     def forward(self, x, fuse_gelu=False, out_dtype=None):
         """``out_dtype`` None: the dtype ``_forward_torch`` returns in the same context (``x.dtype``; fp32 under CUDA
         autocast, where ``layer_norm`` is one of torch's fp32 ops)."""
-        from . import ops
         if ops.channel_layer_norm_supported(x):
             if out_dtype is None:
                 out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype

@@ -13,6 +13,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
+from . import ops
+
 
 class _X3Conv(torch.autograd.Function):
     """y[b] = W @ x[b] (+ addend[b], accumulated in place) on fp32 ``[B, C, P]`` fields: forward, data gradient and weight
@@ -21,7 +23,6 @@ class _X3Conv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, w, addend):
-        from . import ops
         wf = w.detach().float()
         ctx.save_for_backward(x3, wf)
         ctx.cfg = (w.dtype, addend is not None)
@@ -29,7 +30,6 @@ class _X3Conv(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         x3, wf = ctx.saved_tensors
         wdt, has_addend = ctx.cfg
         gy = gy.contiguous()
@@ -48,7 +48,7 @@ class _PointwiseConv(torch.autograd.Function):
     output only [O x I]) on a few dozen workgroups; splitting the contraction into SPLIT batched
     chunks (strided views, no copies) and summing the partials in fp32 fills the chip.
     """
-    SPLIT = int(__import__("os").environ.get("MK_WGRAD_SPLIT", "32"))
+    SPLIT = int(os.environ.get("MK_WGRAD_SPLIT", "32"))
 
     @staticmethod
     def forward(ctx, x3, w_master, addend):
@@ -89,9 +89,8 @@ class _PointwiseConv(torch.autograd.Function):
             else:
                 gx = torch.bmm(w.t().unsqueeze(0).expand(B, -1, -1), gy)
         if ctx.needs_input_grad[1] and x3.is_cuda and x3.dtype == torch.bfloat16 and gy.dtype == torch.bfloat16 \
-                and P % 8 == 0 and os.environ.get("MK_CONV_WGRAD", "hip") == "hip":
+                and P % 8 == 0 and ops._knob("MK_CONV_WGRAD", "hip") == "hip":
             # hand-written bf16 MFMA kernel: pixel slabs per workgroup, fp32 atomics into gW
-            from . import ops
             gw = ops.conv1x1_wgrad_raw(gy, x3.contiguous()).to(ctx.master_dtype)
         elif ctx.needs_input_grad[1]:
             S = _PointwiseConv.SPLIT
@@ -112,13 +111,27 @@ class _PointwiseConv(torch.autograd.Function):
 def _step_items(w):
     """What the backward pass of a convolution with weight ``w`` takes from the open ``ops.EngineArena`` scope: (transposed
     image, zeroed gradient buffer), each None outside a scope (the backward pass then packs / allocates itself)."""
-    from . import ops
     return ops.arena_image(w, True), (ops.arena_grad_buffer(w) if w.requires_grad else None)
+
+
+def _engine_backward(ctx, g, x3, w, need_gx, need_gw, **gx_args):
+    """The backward block of one engine convolution ``y = W @ x3`` for the gradient ``g`` of ``y``: ``(gx, gw)``, each None where
+    not needed.  It uses up the next ``_step_items`` pair of ``ctx.step`` (a node with two weights stores two pairs, in the order
+    of its calls); ``gx_args`` go to the launch of the data gradient."""
+    # taken once: no reference may survive this call (autograd adopts gw only as its sole owner); a second backward pass
+    # through the same node packs / allocates for itself
+    step = ctx.step or (None, None)
+    (wimg_t, gbuf), ctx.step = step[:2], step[2:]
+    gx = gw = None
+    if need_gx:
+        gx = ops.pce_gemm(g, wimg_t if wimg_t is not None else ops.pce_pack(w, transpose=True), w.shape[1], **gx_args)
+    if need_gw:
+        gw = ops.conv1x1_wgrad_raw(g, x3, out=gbuf).to(w.dtype)
+    return gx, gw
 
 
 def _row_sums(t3):
     """sum over (batch, pixels) of a [B, C, P] field -> fp32 [C] (the HIP row-sum pass of the instance norm)."""
-    from . import ops
     r = ops.row_sums(t3).view(t3.shape[0], t3.shape[1])
     return r[0] if r.shape[0] == 1 else r.sum(0)      # one batch item: nothing to add up (saves a launch per bias gradient)
 
@@ -129,7 +142,6 @@ class _PceConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, w, bias, addend):
-        from . import ops
         ctx.save_for_backward(x3, w)
         ctx.has = (bias is not None, addend is not None)
         ctx.bias_dtype = None if bias is None else bias.dtype
@@ -138,18 +150,11 @@ class _PceConv(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         x3, w = ctx.saved_tensors
         has_bias, has_addend = ctx.has
         gy = gy.contiguous()
-        gx = gw = gb = None
-        # taken once: no reference may survive this call (autograd adopts gw only as its sole owner); a second backward pass
-        # through the same node packs / allocates for itself
-        (wimg_t, gbuf), ctx.step = (ctx.step or (None, None)), None
-        if ctx.needs_input_grad[0]:
-            gx = ops.pce_gemm(gy, wimg_t if wimg_t is not None else ops.pce_pack(w, transpose=True), w.shape[1])
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv1x1_wgrad_raw(gy, x3, out=gbuf).to(w.dtype)
+        gb = None
+        gx, gw = _engine_backward(ctx, gy, x3, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         if has_bias and ctx.needs_input_grad[2]:
             gb = _row_sums(gy).to(ctx.bias_dtype)
         return gx, gw, gb, (gy if has_addend else None)
@@ -164,7 +169,6 @@ class _PceConvNormAdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, w, bias, z4, sums, nw, nb, eps, group, count):
-        from . import ops
         B, C, H, W = z4.shape
         if group is not None:
             torch.distributed.all_reduce(sums, group=group)
@@ -182,19 +186,12 @@ class _PceConvNormAdd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         x3, w, z4, stats, wf, bf = ctx.saved_tensors
         bias_dtype, nw_dtype, nb_dtype, group, cnt = ctx.cfg
         B, C, H, W = z4.shape
         gy = gy.contiguous()
-        gx = gw = gb = None
-        # taken once: no reference may survive this call (autograd adopts gw only as its sole owner); a second backward pass
-        # through the same node packs / allocates for itself
-        (wimg_t, gbuf), ctx.step = (ctx.step or (None, None)), None
-        if ctx.needs_input_grad[0]:
-            gx = ops.pce_gemm(gy, wimg_t if wimg_t is not None else ops.pce_pack(w, transpose=True), w.shape[1])
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv1x1_wgrad_raw(gy, x3, out=gbuf).to(w.dtype)
+        gb = None
+        gx, gw = _engine_backward(ctx, gy, x3, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         if bias_dtype is not None and ctx.needs_input_grad[2]:
             gb = _row_sums(gy).to(bias_dtype)
         gz, gnw, gnb = ops.instance_norm_backward(z4, gy.view(B, C, H, W), stats, wf if nw_dtype is not None else None,
@@ -208,11 +205,11 @@ def conv_plus_instance_norm(conv, x, z, sums, norm):
     """``conv(x) + norm(z)`` as one launch (``_PceConvNormAdd``) when the engine can take it, else None: ``conv`` a
     ``Conv1x1``, ``norm`` an affine-or-not instance norm on the field's own statistics (single-GPU or spatially
     distributed), ``z`` a bf16 field that came with its row sums ``sums``."""
-    from . import comm, ops
+    from . import comm
     from .layer_norm import DistributedInstanceNorm2d
     if sums is None or not isinstance(conv, Conv1x1) or z.dtype != torch.bfloat16 or not z.is_contiguous() or z.dim() != 4:
         return None
-    if os.environ.get("MK_NORM_SKIP_FUSION", "1") == "0":
+    if ops._knob("MK_NORM_SKIP_FUSION", "1") == "0":
         return None
     group = count = None
     if isinstance(norm, DistributedInstanceNorm2d):
@@ -242,7 +239,6 @@ class _NormSkipAdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, r4, z4, sums, nw, nb, eps, group, count):
-        from . import ops
         B, C, H, W = z4.shape
         if group is not None:
             torch.distributed.all_reduce(sums, group=group)
@@ -258,7 +254,6 @@ class _NormSkipAdd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         z4, stats, wf, bf = ctx.saved_tensors
         nw_dtype, nb_dtype, group, cnt = ctx.cfg
         gy = gy.contiguous()
@@ -276,7 +271,6 @@ class _NormSkipAddFFT(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xf, twiddles, nlon, kmajor, z4, sums, nw, nb, eps):
-        from . import ops
         B, C, H, W = z4.shape
         wf = None if nw is None else nw.detach().float().contiguous()
         bf = None if nb is None else nb.detach().float().contiguous()
@@ -290,7 +284,6 @@ class _NormSkipAddFFT(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import ops
         z4, stats, wf, bf, tw = ctx.saved_tensors
         nw_dtype, nb_dtype, mmax, kmajor = ctx.cfg
         B, C, H, W = z4.shape
@@ -306,10 +299,9 @@ class _NormSkipAddFFT(torch.autograd.Function):
 def spectral_skip_supported(conv, z_like):
     """The outer skip ``conv`` may run on the spectrum: a bias-free ``Conv1x1`` the channel mix takes, in a step on the bf16
     engine (the conditions ``conv_plus_instance_norm`` checks before it sees the MLP output)."""
-    from . import ops
     if not isinstance(conv, Conv1x1) or conv.bias is not None or not ops.spec_mix_supported(conv.in_channels, conv.out_channels):
         return False
-    if os.environ.get("MK_NORM_SKIP_FUSION", "1") == "0" or os.environ.get("MK_CONV_ENGINE", "pce") != "pce":
+    if ops._knob("MK_NORM_SKIP_FUSION", "1") == "0" or ops._knob("MK_CONV_ENGINE", "pce") != "pce":
         return False
     if not (z_like.is_cuda and z_like.dim() == 4):
         return False
@@ -321,7 +313,7 @@ def spectral_skip_plus_instance_norm(conv, filt, spec, z, sums, norm):
     """``isht(conv.weight . spec) + norm(z)``: the skip convolution as a channel mix of the block's input spectrum ``spec``
     (``filt``: the block's ``SpectralConv``, whose inverse transform synthesises it), the norm's apply pass and the add in one
     streaming pass -- or None where ``conv_plus_instance_norm`` would decline too (the caller then synthesises the residual)."""
-    from . import comm, ops
+    from . import comm
     from .layer_norm import DistributedInstanceNorm2d
     if sums is None or z.dtype != torch.bfloat16 or not z.is_contiguous() or z.dim() != 4 or not ops.pointwise_supported(z):
         return None
@@ -358,7 +350,6 @@ class _PceConvGelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, w, bias, keep_pre):
-        from . import ops
         if keep_pre:
             h, pre = ops.pce_gemm(x3, ops.pce_pack(w), w.shape[0], bias=bias, want_pre=True, gelu=True)
         else:
@@ -370,26 +361,17 @@ class _PceConvGelu(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gh):
-        from . import ops
         x3, w, pre = ctx.saved_tensors
-        (wimg_t, gbuf), ctx.step = (ctx.step or (None, None)), None
         need_gb = ctx.bias_dtype is not None and ctx.needs_input_grad[2]
         gpre, gsum = ops.gelu_backward(pre, gh.contiguous(), need_gb)
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = ops.pce_gemm(gpre, wimg_t if wimg_t is not None else ops.pce_pack(w, transpose=True), w.shape[1])
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv1x1_wgrad_raw(gpre, x3, out=gbuf).to(w.dtype)
-        if need_gb:
-            gb = gsum.to(ctx.bias_dtype)
-        return gx, gw, gb, None
+        gx, gw = _engine_backward(ctx, gpre, x3, w, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return gx, gw, (gsum.to(ctx.bias_dtype) if need_gb else None), None
 
 
 def encoder_head(encoder, x):
     """``(h, last)`` with ``h`` the field in front of the encoder's last convolution ``last`` -- for a caller that evaluates
     that convolution behind a spherical harmonic analysis (``ops.spec_mix``) -- or None where the pattern is not the one the
     engine takes in one launch: ``[Conv1x1, exact GELU, no-ops..., bias-free Conv1x1]`` on a bf16 (or autocast-to-bf16) field."""
-    from . import ops
     mods = list(encoder.fwd)
     pat = _mlp_pattern(mods)
     if pat is None or x.dim() != 4:
@@ -418,7 +400,6 @@ class _PceMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x3, w1, b1, w2, b2, apply_b2, want_row_sums, keep_pre=True):
         # keep_pre: the caller's `torch.is_grad_enabled()` (inside forward grad mode is always off, and needs_input_grad ignores it)
-        from . import ops
         if keep_pre:
             h, pre = ops.pce_gemm(x3, ops.pce_pack(w1), w1.shape[0], bias=b1, want_pre=True, gelu=True)
         else:       # inference: nobody will ask for GELU'(pre) -- the first launch writes the hidden field once, not twice
@@ -429,36 +410,28 @@ class _PceMLP(torch.autograd.Function):
         y, sums = y if want_row_sums else (y, x3.new_empty(0, dtype=torch.float64))
         ctx.save_for_backward(x3, w1, w2, pre, h)
         ctx.cfg = (None if b1 is None else b1.dtype, None if b2 is None else (b2.dtype, tuple(b2.shape)), bool(apply_b2))
-        ctx.step = _step_items(w1) + _step_items(w2)
+        ctx.step = _step_items(w2) + _step_items(w1)       # in the order the backward pass uses them
         ctx.mark_non_differentiable(sums)
         return y, sums
 
     @staticmethod
     def backward(ctx, gy, _gsums):
-        from . import ops
         x3, w1, w2, pre, h = ctx.saved_tensors
         b1_dtype, b2_info, apply_b2 = ctx.cfg
         gy = gy.contiguous()
         need_gb1 = b1_dtype is not None and ctx.needs_input_grad[2]
         fused_gb1 = need_gb1 and w2.shape[1] <= 768
-        (w1img_t, g1buf, w2img_t, g2buf), ctx.step = (ctx.step or (None, None, None, None)), None
-        gpre = ops.pce_gemm(gy, w2img_t if w2img_t is not None else ops.pce_pack(w2, transpose=True), w2.shape[1], aux_in=pre,
-                            want_row_sums=fused_gb1)
+        gpre, gw2 = _engine_backward(ctx, gy, h, w2, True, ctx.needs_input_grad[3], aux_in=pre, want_row_sums=fused_gb1)
         if fused_gb1:       # the bias gradient is the pixel sum of gpre: a by-product of the launch that wrote it
             gpre, gsum = gpre
-        gx = gw1 = gb1 = gw2 = gb2 = None
-        if ctx.needs_input_grad[0]:
-            gx = ops.pce_gemm(gpre, w1img_t if w1img_t is not None else ops.pce_pack(w1, transpose=True), w1.shape[1])
-        if ctx.needs_input_grad[1]:
-            gw1 = ops.conv1x1_wgrad_raw(gpre, x3, out=g1buf).to(w1.dtype)
+        gb1 = gb2 = None
+        gx, gw1 = _engine_backward(ctx, gpre, x3, w1, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         if need_gb1:
             if fused_gb1:
                 g1 = gsum.view(gy.shape[0], -1, 2)[..., 0]
                 gb1 = (g1[0] if g1.shape[0] == 1 else g1.sum(0)).to(b1_dtype)
             else:
                 gb1 = _row_sums(gpre).to(b1_dtype)
-        if ctx.needs_input_grad[3]:
-            gw2 = ops.conv1x1_wgrad_raw(gy, h, out=g2buf).to(w2.dtype)
         if b2_info is not None and ctx.needs_input_grad[4]:
             gb2 = _row_sums(gy).to(b2_info[0]) if apply_b2 else torch.zeros(b2_info[1], dtype=b2_info[0], device=gy.device)
         return gx, gw1, gb1, gw2, gb2, None, None, None
@@ -473,7 +446,6 @@ class _PceMLPFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, w1, b1, w2, b2, apply_b2, want_row_sums):
-        from . import ops
         out = ops.pce_mlp(x3, ops.pce_mlp_pack(w1, False, w2, False), 0, b1=b1,
                           b2=b2 if (apply_b2 and b2 is not None) else None, want_row_sums=bool(want_row_sums))
         y, pre = out[0], out[1]
@@ -486,7 +458,6 @@ class _PceMLPFused(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gsums):
-        from . import ops
         x3, w1, w2, pre = ctx.saved_tensors
         b1_dtype, b2_info, apply_b2 = ctx.cfg
         (g1buf, g2buf), ctx.step = (ctx.step or (None, None)), None
@@ -509,17 +480,16 @@ class _PceMLPFused(torch.autograd.Function):
 
 def _mlp_fused_ok(fc1, fc2):
     """The fused node takes the layer in both directions (K1, M <= 384, hidden <= 768) and is switched on."""
-    from . import ops
-    return (os.environ.get("MK_MLP_FUSED", "0") == "1" and fc2.out_channels <= 384
+    return (ops._knob("MK_MLP_FUSED", "0") == "1" and fc2.out_channels <= 384
             and ops.pce_mlp_supported(fc2.out_channels, fc1.out_channels, fc1.in_channels)
             and ops.pce_mlp_supported(fc1.in_channels, fc1.out_channels, fc2.out_channels))
 
 
 def _engine_field(x):
     """The field as the pixel-column engine takes it (bf16 ``[B, C, P]``, contiguous, P a multiple of 8), or None."""
-    if not (x.is_cuda and x.dim() == 4 and x.is_contiguous() and (x.shape[2] * x.shape[3]) % 8 == 0):
+    if ops._knob("MK_CONV_ENGINE", "pce") != "pce":
         return None
-    if os.environ.get("MK_CONV_ENGINE", "pce") != "pce":
+    if not (x.is_cuda and x.dim() == 4 and x.is_contiguous() and (x.shape[2] * x.shape[3]) % 8 == 0):
         return None
     if x.dtype == torch.bfloat16:
         return x.view(x.shape[0], x.shape[1], -1)
@@ -539,7 +509,6 @@ class Conv1x1(nn.Conv2d):
 
     def forward(self, x, add_bias=True, addend=None):
         """``addend`` (same shape as the output) is added inside the GEMM epilogue: y = addend + conv(x)."""
-        from . import ops
         B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
         x3 = _engine_field(x) if x.dim() == 4 else None
         if x3 is not None and ops.pce_supported_train(self.out_channels, self.in_channels):
@@ -565,7 +534,7 @@ class Conv1x1(nn.Conv2d):
             a3 = None
             if addend is not None:
                 a3 = addend.contiguous().view(B, self.out_channels, H * W).to(x3.dtype)
-            if ops.conv1x1_x3_supported(x3) and (H * W) % 4 == 0 and os.environ.get("MK_CONV_FP32", "x3") == "x3":
+            if ops.conv1x1_x3_supported(x3) and (H * W) % 4 == 0 and ops._knob("MK_CONV_FP32", "x3") == "x3":
                 y = _X3Conv.apply(x3, self.weight2d(), a3)
             else:
                 y = _PointwiseConv.apply(x3, self.weight2d(), a3)
@@ -577,10 +546,9 @@ class Conv1x1(nn.Conv2d):
 def _x3_inference_conv(m, x, gelu):
     """fp32 field, grad mode off: ``act(conv(x) + bias)`` as ONE launch of the bf16x3 engine (bias and exact GELU in the epilogue,
     ``mk_conv1x1_x3_bias_act``), or None where that path does not apply."""
-    from . import ops
     if torch.is_grad_enabled() or x.dim() != 4 or not x.is_cuda or not x.is_contiguous() or x.dtype != torch.float32:
         return None
-    if torch.is_autocast_enabled() or os.environ.get("MK_CONV_FP32", "x3") != "x3":
+    if torch.is_autocast_enabled() or ops._knob("MK_CONV_FP32", "x3") != "x3":
         return None
     B, H, W = x.shape[0], x.shape[2], x.shape[3]
     x3 = x.view(B, x.shape[1], H * W)
@@ -623,7 +591,6 @@ def _token_mlp_pattern(mods):
 def _run_token_chain(mods, x, addend):
     """The chain on token input ``[..., features]``: the two-linear pattern as ``ops.token_mlp`` (which takes the torch calls for what
     the kernels decline); with active dropout or another activation every module runs singly."""
-    from . import ops
     pat = _token_mlp_pattern(mods)
     if pat is not None:
         fc1, fc2 = pat
@@ -649,7 +616,6 @@ def run_pointwise_chain(mods, x, skip_last_bias=False, want_row_sums=False, adde
 
     ``addend`` (token input only): return ``addend + chain(x)``; the two-linear pattern adds it in ``fc2``'s epilogue.
     """
-    from . import ops
     mods = list(mods)
     if any(isinstance(m, nn.Linear) for m in mods):
         y = _run_token_chain(mods, x, addend)
@@ -718,7 +684,6 @@ class InstanceNorm2d(nn.InstanceNorm2d):
     (row sums, apply), optionally with the block's GELU fused into the apply pass."""
 
     def forward(self, x, fuse_gelu=False, row_sums=None):
-        from . import ops
         if self.track_running_stats or not ops.pointwise_supported(x):
             y = super().forward(x)
             return F.gelu(y) if fuse_gelu else y
@@ -732,7 +697,6 @@ class Linear(nn.Linear):
     and ``ops.token_linear_x3_supported`` decline and with both knobs at ``torch`` it is exactly ``nn.Linear.forward``."""
 
     def forward(self, x):
-        from . import ops
         fp32_hip = ops.token_linear_fp32_hip()
         if ops.token_linear_hip() and ops.token_linear_supported(x, self.weight, self.bias):
             return ops.token_linear(x, self.weight, self.bias)
@@ -747,19 +711,16 @@ class LayerNorm(nn.LayerNorm):
     ``ops.token_layer_norm_supported`` declines and with ``MK_TOKEN_NORM=torch`` it is exactly ``nn.LayerNorm.forward``."""
 
     def hip_ready(self, x):
-        from . import ops
         return ops.token_norm_hip() and ops.token_layer_norm_supported(x, self.normalized_shape, self.weight, self.bias)
 
     def forward(self, x):
         if not self.hip_ready(x):
             return super().forward(x)
-        from . import ops
         return ops.token_layer_norm(x, self.weight, self.bias, self.eps, normalized_shape=self.normalized_shape)
 
     def forward_add(self, x, residual=None, lowp=False, want_sum=False, out_dtype=None):
         """The norm of ``x + residual`` for callers that fuse: a tuple of ``y`` (``out_dtype``: as ``ops.token_layer_norm``), then
         its bf16 copy if ``lowp``, then the sum if ``want_sum``.  One launch on the HIP path; the torch formulation elsewhere."""
-        from . import ops
         if self.hip_ready(x) and (residual is None or (residual.shape == x.shape
                                                        and ops.token_layer_norm_supported(residual, self.normalized_shape))):
             out = ops.token_layer_norm(x, self.weight, self.bias, self.eps, residual, out_dtype, lowp, want_sum, self.normalized_shape)
@@ -819,7 +780,6 @@ class PatchEmbed(nn.Module):
         H, W = x.shape[-2], x.shape[-1]
         assert H == self.img_size[0] and W == self.img_size[1], \
             f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
-        from . import ops
         patch, fp32_hip = ops.patch_hip(), ops.token_linear_fp32_hip()
         if patch and (ops.patch_embed_supported(x, self.proj.weight, self.proj.bias)
                       or (fp32_hip and ops.patch_embed_x3_supported(x, self.proj.weight, self.proj.bias))):
@@ -928,7 +888,6 @@ PLANAR_FFT_DEFAULT = "torch"
 def planar_fft_hip():
     """The planar transforms run on this package's kernels: ``MK_PLANAR_FFT`` (``hip`` | ``torch``, read at call time), and
     the bf16x3 engine selected -- ``MK_SPECTRAL_GEMM=f32`` has no fp32-MFMA variant of the latitude DFT."""
-    from . import ops
     return ops._hip_or_torch("MK_PLANAR_FFT", PLANAR_FFT_DEFAULT) and ops.SPECTRAL_GEMM == "bf16x3"
 
 
@@ -947,7 +906,6 @@ class _PlanarFFT2Base(nn.Module):
         self.lmax_low = math.floor(self.lmax / 2)
         self._hip_sizes = nlon % 2 == 0 and nlon >= 2 and self.lmax >= 2 and nlat >= 2
         if self._hip_sizes:
-            from . import ops
             self.register_buffer("twiddles", ops.fft_twiddles(nlon), persistent=False)
             self.register_buffer("dft_table", ops.latdft_table(nlat, self.lmax), persistent=False)
 
@@ -972,7 +930,6 @@ class RealFFT2(_PlanarFFT2Base):
 
     def forward_packed(self, x3):
         """x3 [BC, nlat, nlon] (fp32 or bf16, contiguous) -> private spectrum [lmax, mmax, BC] (every entry is data: no triangle)."""
-        from . import ops
         xf = ops.rfft(x3, self.twiddles, self.mmax, True, scale=1.0 / math.sqrt(self.nlon))
         return ops.lat_dft(xf, self.dft_table, self.lmax)
 
@@ -986,7 +943,6 @@ class RealFFT2(_PlanarFFT2Base):
         if (x.dim() < 2 or x.dtype not in (torch.float32, torch.bfloat16) or tuple(x.shape[-2:]) != (self.nlat, self.nlon)
                 or x.numel() == 0 or not self.hip_ready(x)):
             return self._forward_torch(x)
-        from . import ops
         lead, x3 = self._flatten(x.contiguous(), (self.nlat, self.nlon))
         c = ops.spec_unpack(self.forward_packed(x3), self.mmax, 0)       # degree offset mmax: dense, no triangle zeroed
         return c.reshape(*lead, self.lmax, self.mmax)
@@ -1000,7 +956,6 @@ class InverseRealFFT2(_PlanarFFT2Base):
         """private spectrum [lmax, mmax, BC] -> x [BC, nlat, nlon] (fp32, or bf16 rows straight from the FFT kernel); with
         ``want_row_sums`` (and a length the split kernels serve) also the fp64 ``[BC, 2]`` sums / sums of squares of the rows of x,
         else None in their place -- the conventions of ``InverseRealSHT.inverse_packed``."""
-        from . import ops
         s = 1.0 / math.sqrt(self.nlon)
         xf = ops.lat_idft(c, self.dft_table, self.nlat)
         if want_row_sums:
@@ -1022,7 +977,6 @@ class InverseRealFFT2(_PlanarFFT2Base):
         if (x.dim() < 2 or x.dtype != torch.complex64 or tuple(x.shape[-2:]) != (self.lmax, self.mmax) or x.numel() == 0
                 or not self.hip_ready(x)):
             return self._forward_torch(x)
-        from . import ops
         lead, c3 = self._flatten(x.contiguous(), (self.lmax, self.mmax))
         y = self.inverse_packed(ops.spec_pack(c3, self.mmax, 0))
         return y.reshape(*lead, self.nlat, self.nlon)

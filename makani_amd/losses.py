@@ -30,14 +30,13 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import comm
+from . import comm, ops
 from .distributed import compute_split_shapes
 from .mappings import gather_from_parallel_region, reduce_from_parallel_region
 
 
 def _latitude_weights(rule, nlat):
     """Quadrature weights over cos(theta) in [-1, 1] for the rules of torch_harmonics.quadrature."""
-    from . import ops
     if rule == "legendre-gauss":
         return torch.from_numpy(ops.quadrature("legendre-gauss", nlat)[1])
     if rule == "clenshaw-curtiss":
@@ -104,7 +103,6 @@ class GeometricLpLoss(nn.Module):
 
     def _fused_abs_sq_l2(self, prd, tar, chw):
         """Absolute squared L2 with one weight for all channels: a single streaming pass (None if it does not apply)."""
-        from . import ops
         if not (self.p == 2 and self.squared and self.reduction and not self.size_average and prd.is_cuda):
             return None
         if not (prd.dim() == 4 and prd.is_contiguous() and tar.is_contiguous() and tar.dtype == torch.float32
@@ -128,7 +126,6 @@ class GeometricLpLoss(nn.Module):
     def sums(self, prd, tar, rows=None):
         """``[B, C, 2]`` float64 integrals of ``|prd - tar| ** p`` and ``|tar| ** p`` over the fields' latitude rows
         ``rows`` (a slice of the cropped grid's rows; all of them by default) -- they add up over spatial shards."""
-        from . import ops
         wrow = self.wrow32 if prd.is_cuda else self.wrow
         return ops.geo_lp_sums(prd, tar, wrow if rows is None else wrow[rows], int(self.p))
 
@@ -200,7 +197,6 @@ class GeometricH1Loss(nn.Module):
         """``[batch, 2]`` float64 (L2 norm squared, H1 seminorm squared) of the packed spectrum ``[L_loc, M_loc, batch * C]``
         of the degrees from ``l_off`` and the orders from ``m_off`` on: sums over channels, degrees and orders (m > 0
         twice).  They add up over the shards of a spectrum."""
-        from . import ops
         power = ops.degree_power(c_packed, l_off, m_off)                  # [batch * C, L_loc] float64
         nl = power.shape[1]
         power = power.reshape(batch, -1, nl)
@@ -211,8 +207,7 @@ class GeometricH1Loss(nn.Module):
         """(L2 norm squared, H1 seminorm squared) per sample: sums over channels, degrees and orders (m > 0 twice)."""
         n = x.size()[0]
         if x.is_cuda:
-            if x.dtype not in (torch.float32, torch.bfloat16):
-                x = x.float()
+            x = ops._lowp(x)
             nlat, nlon = x.shape[-2:]
             if self.sharded:
                 c = self.sht.forward_packed(x.reshape(n, -1, nlat, nlon).contiguous())

@@ -21,7 +21,7 @@ Deliberate differences:
 import torch
 import torch.distributed as dist
 
-from . import comm
+from . import comm, ops
 from .distributed import compute_split_shapes
 from .mappings import gather_from_parallel_region
 from .metrics import GeometricACC, GeometricL1, GeometricRMSE, Quadrature
@@ -131,7 +131,6 @@ class MetricsHandler:
 
     def _global_sums(self, prediction, target):
         """[B, C, 5] float64 sums over the whole (cropped) field: this rank's shard, all-reduced over the spatial group."""
-        from . import ops
         sums = ops.geo_metric_sums(prediction, target, self.clim, self.wrow)
         if self.spatial_size > 1:
             dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))

@@ -10,6 +10,7 @@ depend on the latitude only, so the kernel reads one weight per row.
 """
 import torch
 
+from . import ops
 from .losses import GridQuadrature
 
 
@@ -43,7 +44,6 @@ class _GeometricMetric(torch.nn.Module):
         return x.is_cuda and y.is_cuda and x.dim() == 4 and not need_grad
 
     def _sums(self, x, y):
-        from . import ops
         return ops.geo_metric_sums(x, y, None, self._wrow())
 
     def _out_dtype(self, x, y):

@@ -32,12 +32,52 @@ def _need_cuda(*tensors):
                                "there is no CPU fallback")
 
 
+_HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
+# Every switch of the package with a closed value set, and that set (README "Environment knobs" says what each one selects).  The
+# free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
+KNOBS = {
+    **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ROWSUM"),
+                    _HIP_TORCH),
+    "MK_SPEC_DIAG": ("fused", "public"),
+    "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
+    "MK_CONV_ENGINE": ("pce", "blas"),
+    "MK_CONV_FP32": ("x3", "torch"),
+    "MK_CONV_WGRAD": ("hip", "blas"),
+    **dict.fromkeys(("MK_FFT_LEGACY", "MK_IRFFT_SUMS", "MK_IRFFT_AFFINE_ADD", "MK_SPEC_MIX", "MK_NORM_SKIP_FUSION", "MK_MLP_FUSED",
+                     "MK_ENGINE_ARENA"), _OFF_ON),
+}
+
+
+def _knob(env, default):
+    """The value of switch ``env`` (``default`` where it is unset), read at call time; a value outside ``KNOBS[env]`` is an error."""
+    mode, values = os.environ.get(env, default), KNOBS[env]
+    if mode not in values:
+        raise ValueError(f"unknown {env} {mode!r} ({' | '.join(values)})")
+    return mode
+
+
 def _hip_or_torch(env, default):
     """A family's ``hip | torch`` switch, read and validated at call time; True for ``hip``."""
-    mode = os.environ.get(env, default)
-    if mode not in ("hip", "torch"):
-        raise ValueError(f"unknown {env} {mode!r} (hip | torch)")
-    return mode == "hip"
+    return _knob(env, default) == "hip"
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+_LOWP = (torch.float32, torch.bfloat16)                     # the element types the streaming kernels read and write
+_DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}         # ... and their codes in the C ABI
+
+
+def _lowp(t):
+    """``t`` as the kernels take it: fp32 and bf16 as they are, anything else as fp32."""
+    return t if t.dtype in _LOWP else t.float()
+
+
+def _f32(t):
+    """A detached contiguous fp32 tensor of ``t``; None stays None."""
+    return t.detach().float().contiguous() if t is not None else None
 
 
 def _autocast_dtype():
@@ -109,7 +149,7 @@ def latdft_table(nlat, lmax, first=None):
 def _fft_split(nlon, mmax):
     """The split FFT kernels apply: a production length, no mode above 240, not switched off (``MK_FFT_LEGACY=1``).  They alone
     have bf16 output rows, the peer-major layout, the row statistics and the affine-add epilogue."""
-    return nlon in (480, 1440) and mmax <= 241 and os.environ.get("MK_FFT_LEGACY", "0") != "1"
+    return nlon in (480, 1440) and mmax <= 241 and _knob("MK_FFT_LEGACY", "0") != "1"
 
 
 def _xf_dims(xf, kmajor=False, chans=0, cpp=0):
@@ -140,7 +180,7 @@ def irfft_bf16_rows(nlon, mmax):
 
 def irfft_sums_supported(nlon, mmax):
     """The inverse FFT can deliver the row statistics of its output (``mk_irfft_sums``: the split kernels)."""
-    return _fft_split(nlon, mmax) and os.environ.get("MK_IRFFT_SUMS", "1") != "0"
+    return _fft_split(nlon, mmax) and _knob("MK_IRFFT_SUMS", "1") != "0"
 
 
 def irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor=False, chans=0, cpp=0, scale=1.0, exact=False):
@@ -166,7 +206,7 @@ def irfft_sums_raw(xf, twiddles, nlon, out_dtype, kmajor=False, chans=0, cpp=0, 
 def irfft_affine_add_supported(nlon, mmax):
     """The inverse FFT can add ``a * z + b`` per row in its store epilogue (``mk_irfft_affine_add``: the split kernels);
     ``MK_IRFFT_AFFINE_ADD=0`` keeps the separate streaming pass (``affine_add``) -- the A/B switch of the variant."""
-    return _fft_split(nlon, mmax) and os.environ.get("MK_IRFFT_AFFINE_ADD", "1") != "0"
+    return _fft_split(nlon, mmax) and _knob("MK_IRFFT_AFFINE_ADD", "1") != "0"
 
 
 def irfft_affine_add_raw(xf, twiddles, nlon, z, affine, kmajor=False):
@@ -223,14 +263,14 @@ def irfft_pm_raw(xf, twiddles, nlon, s0, sm, sh, chans, chans_per_peer, out_dtyp
 
 
 # Arithmetic of the spectral GEMMs (Legendre, dhconv): "bf16x3" = exact three-way bf16 split of every fp32
-# operand, six bf16 MFMA products, fp32 accumulation (fp32-accurate, csrc/gemm_x3.hip); "f32" = fp32 MFMA
+# operand, six bf16 MFMA products, fp32 accumulation (fp32-accurate, csrc/x3_engine.h and the x3_*.hip families); "f32" = fp32 MFMA
 # (csrc/gemm.hip).  Both meet the 1e-5 parity budget; bf16x3 is the faster one on gfx950.
 SPECTRAL_GEMM = os.environ.get("MK_SPECTRAL_GEMM", "bf16x3")
 
 
 def _gemm_mode(mode):
     mode = mode or SPECTRAL_GEMM
-    if mode not in ("bf16x3", "f32"):
+    if mode not in KNOBS["MK_SPECTRAL_GEMM"]:
         raise ValueError(f"unknown spectral GEMM mode {mode!r} (bf16x3 | f32)")
     return mode
 
@@ -459,10 +499,7 @@ SPEC_DIAG_DEFAULT = "public"
 def spec_diag_fused():
     """``MK_SPEC_DIAG=fused|public`` (read at call time): the diagonal filter of ``SpectralConv`` on the private spectrum
     (``mk_spec_diag_*`` between ``forward_packed`` and ``inverse_packed``), or through the public layout (``mk_diag_*``)."""
-    mode = os.environ.get("MK_SPEC_DIAG", SPEC_DIAG_DEFAULT)
-    if mode not in ("fused", "public"):
-        raise ValueError(f"unknown MK_SPEC_DIAG {mode!r} (fused | public)")
-    return mode == "fused"
+    return _knob("MK_SPEC_DIAG", SPEC_DIAG_DEFAULT) == "fused"
 
 
 def spec_diag_supported(c, w):
@@ -579,7 +616,7 @@ def conv1x1_x3(w, x3, out=None, bias=None, gelu=False):
         assert bf is None or bf.numel() == m
         y = torch.empty(b, m, p, dtype=torch.float32, device=x3.device)
         _lib.check(_lib.load().mk_conv1x1_x3_bias_act(a.data_ptr(), a.stride(0), x3.data_ptr(), p, y.data_ptr(), p, m, k, p, b, k * p,
-                                                      m * p, None if bf is None else bf.data_ptr(), int(bool(gelu)), _stream()),
+                                                      m * p, _ptr(bf), int(bool(gelu)), _stream()),
                    "mk_conv1x1_x3_bias_act")
         return y
     if out is not None:
@@ -624,7 +661,7 @@ class EngineArena:
         # the parameter's AccumulateGrad node; keeping it across steps pins that node to the stream of the first step and a
         # later capture on another stream dies in capture_end -- the round-1 crash)
         self.weights = [w.detach() for w in weights if w.is_cuda and w.dim() == 2 and w.stride(1) == 1
-                        and w.dtype in (torch.float32, torch.bfloat16)]
+                        and w.dtype in _LOWP]
         lib = _lib.load()
         rows, self.slots, off, goff = [], {}, 0, 0
         self.gslots = {}
@@ -751,7 +788,7 @@ def pce_pack(w, transpose=False):
     img = arena_image(w, transpose)
     if img is not None:
         return img
-    assert w.dim() == 2 and w.stride(1) == 1 and w.dtype in (torch.float32, torch.bfloat16)
+    assert w.dim() == 2 and w.stride(1) == 1 and w.dtype in _LOWP
     m, k = (w.shape[1], w.shape[0]) if transpose else (w.shape[0], w.shape[1])
     lib = _lib.load()
     nbytes = lib.mk_pce_image_bytes(m, k)
@@ -773,7 +810,7 @@ def pce_mlp_pack(a1, a1_transposed, a2, a2_transposed):
     ``[K1, Hd]``), ``A2 [M, Hd]`` = ``a2`` (or ``a2^T``: ``a2`` is ``[Hd, M]``).  Returns ``(image, M, Hd, K1)``."""
     _need_cuda(a1, a2)
     assert a1.dim() == 2 and a2.dim() == 2 and a1.stride(1) == 1 and a2.stride(1) == 1 and a1.dtype == a2.dtype
-    assert a1.dtype in (torch.float32, torch.bfloat16)
+    assert a1.dtype in _LOWP
     hd, k1 = (a1.shape[1], a1.shape[0]) if a1_transposed else (a1.shape[0], a1.shape[1])
     m, hd2 = (a2.shape[1], a2.shape[0]) if a2_transposed else (a2.shape[0], a2.shape[1])
     assert hd == hd2, "the two matrices do not share the hidden dimension"
@@ -807,9 +844,7 @@ def pce_mlp(x3, packed, mode, b1=None, b2=None, pre=None, want_row_sums=False, w
     sums = torch.empty(b * m, 2, dtype=torch.float64, device=x3.device) if want_row_sums else None
     msum = torch.empty(b * hd, dtype=torch.float64, device=x3.device) if want_mid_sums else None
     _lib.check(_lib.load().mk_pce_mlp(x3.data_ptr(), img.data_ptr(), y.data_ptr(), mid.data_ptr(),
-                                      None if pre is None else pre.data_ptr(), None if bf1 is None else bf1.data_ptr(),
-                                      None if bf2 is None else bf2.data_ptr(), None if sums is None else sums.data_ptr(),
-                                      None if msum is None else msum.data_ptr(), int(mode), b, m, hd, k1, p, _stream()),
+                                      _ptr(pre), _ptr(bf1), _ptr(bf2), _ptr(sums), _ptr(msum), int(mode), b, m, hd, k1, p, _stream()),
                "mk_pce_mlp")
     return (y, mid) + ((sums,) if want_row_sums else ()) + ((msum,) if want_mid_sums else ())
 
@@ -847,11 +882,8 @@ def pce_gemm(x3, wimg, m, bias=None, addend=None, aux_in=None, want_pre=False, g
         assert (addend is not None and addend_affine.dtype == torch.float32 and addend_affine.is_contiguous()
                 and addend_affine.numel() == 2 * b * m)
     _lib.check(_lib.load().mk_pce_gemm_ex(x3.data_ptr(), wimg.data_ptr(), y.data_ptr(), bf.data_ptr(),
-                                          None if addend is None else addend.data_ptr(),
-                                          None if addend_affine is None else addend_affine.data_ptr(),
-                                          None if aux_in is None else aux_in.data_ptr(),
-                                          None if pre is None else pre.data_ptr(), int(bool(gelu)),
-                                          None if sums is None else sums.data_ptr(), b, m, k, p, _stream()),
+                                          _ptr(addend), _ptr(addend_affine), _ptr(aux_in), _ptr(pre), int(bool(gelu)),
+                                          _ptr(sums), b, m, k, p, _stream()),
                "mk_pce_gemm_ex")
     out = (y,) + ((pre,) if want_pre else ()) + ((sums,) if want_row_sums else ())
     return out if len(out) > 1 else y
@@ -911,8 +943,7 @@ class _IRFFT(torch.autograd.Function):
     def backward(ctx, gx, *_):
         (tw,) = ctx.saved_tensors
         mmax, kmajor, pm, s = ctx.cfg         # the adjoint of mk_irfft(s, s, s) is mk_rfft(s, 2 s, s)
-        if gx.dtype not in (torch.float32, torch.bfloat16):
-            gx = gx.float()
+        gx = _lowp(gx)
         if pm:
             gxf = rfft_pm_raw(gx.contiguous(), tw, mmax, s, 2.0 * s, s, *pm)
         else:
@@ -1022,7 +1053,7 @@ class _Dhconv(torch.autograd.Function):
 def spec_mix_supported(cin, cout):
     """The spectral channel mix runs on the bf16x3 engine only (even channel counts); ``MK_SPEC_MIX=0`` switches its call
     sites back to the convolutions on the grid."""
-    return (os.environ.get("MK_SPEC_MIX", "1") != "0" and _gemm_mode(None) == "bf16x3" and cin % 2 == 0 and cout % 2 == 0)
+    return (_knob("MK_SPEC_MIX", "1") != "0" and _gemm_mode(None) == "bf16x3" and cin % 2 == 0 and cout % 2 == 0)
 
 
 def _spec_mix_args(x, batch):
@@ -1435,7 +1466,7 @@ def afnov1_hip():
 
 
 def _layout_args(x, other=None):
-    assert x.dim() == 3 and x.numel() > 0 and x.dtype in (torch.float32, torch.bfloat16), "[B, N, C] / [B, C, N] fp32 or bf16"
+    assert x.dim() == 3 and x.numel() > 0 and x.dtype in _LOWP, "[B, N, C] / [B, C, N] fp32 or bf16"
     assert other is None or (other.dtype == x.dtype and other.device == x.device)
 
 
@@ -1460,7 +1491,7 @@ def fields_to_tokens_raw(r, addend=None, out=None):
     assert addend is None or (tuple(addend.shape) == (B, N, C) and addend.is_contiguous())
     out = torch.empty((B, N, C), dtype=r.dtype, device=r.device) if out is None else out
     assert tuple(out.shape) == (B, N, C) and out.is_contiguous() and out.dtype == r.dtype and out.device == r.device
-    _lib.check(_lib.load().mk_fields_to_tokens(r.data_ptr(), addend.data_ptr() if addend is not None else 0, out.data_ptr(),
+    _lib.check(_lib.load().mk_fields_to_tokens(r.data_ptr(), _ptr(addend), out.data_ptr(),
                                                _pw_dtype(r), B, N, C, _stream()), "mk_fields_to_tokens")
     return out
 
@@ -1558,16 +1589,14 @@ def dhconv(x, w, batch, l_off=0, m_off=0):
 # fused pointwise ops of the FNO block (bias + GELU, instance norm [+ GELU])
 # ----------------------------------------------------------------------------
 def _pw_dtype(t):
-    if t.dtype == torch.float32:
-        return 0
-    if t.dtype == torch.bfloat16:
-        return 1
+    if t.dtype in _DTYPE_CODE:
+        return _DTYPE_CODE[t.dtype]
     raise TypeError(f"makani_amd pointwise ops: unsupported dtype {t.dtype}")
 
 
 def pointwise_supported(x):
     """NCHW, contiguous, on the GPU, fp32/bf16, H*W a multiple of 8, B*C <= 65535."""
-    return (x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
+    return (x.is_cuda and x.dim() == 4 and x.is_contiguous() and x.dtype in _LOWP
             and (x.shape[2] * x.shape[3]) % 8 == 0 and x.shape[0] * x.shape[1] <= 65535)
 
 
@@ -1580,7 +1609,7 @@ class _BiasGelu(torch.autograd.Function):
         B, C, H, W = x.shape
         y = torch.empty_like(x)
         bf = None if bias is None else bias.detach().float().contiguous()
-        _lib.check(_lib.load().mk_bias_gelu_fwd(x.data_ptr(), 0 if bf is None else bf.data_ptr(), y.data_ptr(),
+        _lib.check(_lib.load().mk_bias_gelu_fwd(x.data_ptr(), _ptr(bf), y.data_ptr(),
                                                 _pw_dtype(x), B * C, C, H * W, _stream()), "mk_bias_gelu_fwd")
         ctx.save_for_backward(x, bf if bf is not None else x.new_empty(0))
         ctx.has_bias = bias is not None
@@ -1595,7 +1624,7 @@ class _BiasGelu(torch.autograd.Function):
         gx = torch.empty_like(x)
         gb = torch.zeros(C, dtype=torch.float32, device=x.device) if ctx.has_bias else None
         _lib.check(_lib.load().mk_bias_gelu_bwd(x.data_ptr(), bf.data_ptr() if ctx.has_bias else 0, gy.data_ptr(),
-                                                gx.data_ptr(), 0 if gb is None else gb.data_ptr(), _pw_dtype(x),
+                                                gx.data_ptr(), _ptr(gb), _pw_dtype(x),
                                                 B * C, C, H * W, _stream()), "mk_bias_gelu_bwd")
         return gx, (gb.to(ctx.bias_dtype) if gb is not None else None)
 
@@ -1623,8 +1652,8 @@ class _InstanceNorm(torch.autograd.Function):
         cnt = H * W if group is None else int(count)
 
         def run(phase):
-            _lib.check(lib.mk_instnorm_fwd_ex(x.data_ptr(), 0 if wf is None else wf.data_ptr(),
-                                              0 if bf is None else bf.data_ptr(), y.data_ptr(), stats.data_ptr(),
+            _lib.check(lib.mk_instnorm_fwd_ex(x.data_ptr(), _ptr(wf),
+                                              _ptr(bf), y.data_ptr(), stats.data_ptr(),
                                               ws.data_ptr(), _pw_dtype(x), B * C, C, H * W, cnt, float(eps),
                                               int(fuse_gelu), phase, _stream()), "mk_instnorm_fwd_ex")
         if group is None:
@@ -1661,8 +1690,7 @@ def instance_norm_backward(x, gy, stats, wf, bf, fuse_gelu=False, group=None, co
     cnt = H * W if group is None else int(count)
 
     def run(phase):
-        _lib.check(lib.mk_instnorm_bwd_ex(x.data_ptr(), gy.data_ptr(), stats.data_ptr(),
-                                          wf.data_ptr() if wf is not None else 0, bf.data_ptr() if bf is not None else 0,
+        _lib.check(lib.mk_instnorm_bwd_ex(x.data_ptr(), gy.data_ptr(), stats.data_ptr(), _ptr(wf), _ptr(bf),
                                           gx.data_ptr(), ws.data_ptr(), _pw_dtype(x), B * C, C, H * W, cnt, int(fuse_gelu),
                                           phase, _stream()), "mk_instnorm_bwd_ex")
     if group is None and B == 1 and grad_dtype == torch.float32 and wf is not None and bf is not None:
@@ -1696,8 +1724,8 @@ def instance_norm_coeffs(sums, weight, bias, rows, channels, count, eps):
     assert sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() == 2 * rows
     stats = torch.empty(rows, 2, dtype=torch.float32, device=sums.device)
     affine = torch.empty(rows, 2, dtype=torch.float32, device=sums.device)
-    _lib.check(_lib.load().mk_instnorm_coeffs(sums.data_ptr(), 0 if weight is None else weight.data_ptr(),
-                                              0 if bias is None else bias.data_ptr(), stats.data_ptr(), affine.data_ptr(),
+    _lib.check(_lib.load().mk_instnorm_coeffs(sums.data_ptr(), _ptr(weight),
+                                              _ptr(bias), stats.data_ptr(), affine.data_ptr(),
                                               rows, channels, int(count), float(eps), _stream()), "mk_instnorm_coeffs")
     return stats, affine
 
@@ -1731,7 +1759,7 @@ def weighted_mse(pred, tar, wrow, scale=1.0):
     """``scale * (((pred - tar) ** 2) * wrow[None, None, :, None]).sum()`` for pred [B, C, H, W] (fp32 / bf16, contiguous),
     tar fp32 of the same shape, wrow fp32 [H]; gradient w.r.t. pred only."""
     if not (pred.is_cuda and pred.is_contiguous() and tar.is_contiguous() and tar.dtype == torch.float32
-            and pred.dtype in (torch.float32, torch.bfloat16) and pred.shape[-1] % 8 == 0):
+            and pred.dtype in _LOWP and pred.shape[-1] % 8 == 0):
         w = wrow.view(1, 1, -1, 1)
         return scale * (((pred.float() - tar) ** 2) * w).sum()
     return _WeightedMSE.apply(pred, tar, wrow.float().contiguous(), scale)
@@ -1742,7 +1770,7 @@ def row_sums(t3):
     _need_cuda(t3)
     assert t3.dim() == 3 and t3.is_contiguous()
     b, c, p = t3.shape
-    if os.environ.get("MK_ROWSUM") == "torch":
+    if not _hip_or_torch("MK_ROWSUM", "hip"):
         return torch.sum(t3, dim=-1, dtype=torch.float32).view(-1)
     ws = torch.empty(b * c, 2, dtype=torch.float64, device=t3.device)
     _lib.check(_lib.load().mk_instnorm_fwd_ex(t3.data_ptr(), 0, 0, 0, 0, ws.data_ptr(), _pw_dtype(t3), b * c, c, p, p, 0.0, 0,
@@ -1762,7 +1790,7 @@ def gelu_backward(pre, gy, want_row_sums=False):
     b, c, p = pre.shape
     gx = torch.empty_like(pre)
     gsum = torch.zeros(c, dtype=torch.float32, device=pre.device) if want_row_sums else None
-    _lib.check(_lib.load().mk_bias_gelu_bwd(pre.data_ptr(), 0, gy.data_ptr(), gx.data_ptr(), 0 if gsum is None else gsum.data_ptr(),
+    _lib.check(_lib.load().mk_bias_gelu_bwd(pre.data_ptr(), 0, gy.data_ptr(), gx.data_ptr(), _ptr(gsum),
                                             _pw_dtype(pre), b * c, c, p, _stream()), "mk_bias_gelu_bwd")
     return gx, gsum
 
@@ -1791,7 +1819,7 @@ def instance_norm(x, weight, bias, eps=1e-5, fuse_gelu=False, group=None, count=
 # ----------------------------------------------------------------------------
 def channel_layer_norm_supported(x):
     """NCHW on the GPU in fp32 / bf16; any H * W, any C (``channel_layer_norm`` makes the field contiguous itself)."""
-    return x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and x.numel() > 0
+    return x.is_cuda and x.dim() == 4 and x.dtype in _LOWP and x.numel() > 0
 
 
 class _ChannelLayerNorm(torch.autograd.Function):
@@ -1810,8 +1838,8 @@ class _ChannelLayerNorm(torch.autograd.Function):
         wf = None if weight is None else weight.detach().float().contiguous()
         bf = None if bias is None else bias.detach().float().contiguous()
         stats = torch.empty(B, H * W, 2, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().mk_chan_layernorm_fwd(x.data_ptr(), _pw_dtype(x), 0 if wf is None else wf.data_ptr(),
-                                                     0 if bf is None else bf.data_ptr(), y.data_ptr(), _pw_dtype(y),
+        _lib.check(_lib.load().mk_chan_layernorm_fwd(x.data_ptr(), _pw_dtype(x), _ptr(wf),
+                                                     _ptr(bf), y.data_ptr(), _pw_dtype(y),
                                                      stats.data_ptr(), B, C, H * W, float(eps), int(fuse_gelu), _stream()),
                    "mk_chan_layernorm_fwd")
         empty = x.new_empty(0, dtype=torch.float32)
@@ -1825,8 +1853,7 @@ class _ChannelLayerNorm(torch.autograd.Function):
         x, stats, wf, bf = ctx.saved_tensors
         has_w, has_b, fuse, wdt, bdt = ctx.cfg
         B, C, H, W = x.shape
-        if gy.dtype not in (torch.float32, torch.bfloat16):
-            gy = gy.float()
+        gy = _lowp(gy)
         gy = gy.contiguous()
         gx = torch.empty_like(x)
         lib = _lib.load()
@@ -1837,7 +1864,7 @@ class _ChannelLayerNorm(torch.autograd.Function):
             gwb = torch.empty(2, C, dtype=torch.float32, device=x.device)
         _lib.check(lib.mk_chan_layernorm_bwd(x.data_ptr(), _pw_dtype(x), gy.data_ptr(), _pw_dtype(gy), stats.data_ptr(),
                                              wf.data_ptr() if has_w else 0, bf.data_ptr() if has_b else 0, gx.data_ptr(),
-                                             0 if ws is None else ws.data_ptr(), 0 if gwb is None else gwb.data_ptr(), B, C,
+                                             _ptr(ws), _ptr(gwb), B, C,
                                              H * W, int(fuse), _stream()), "mk_chan_layernorm_bwd")
         gw = gwb[0].to(wdt) if (has_w and ctx.needs_input_grad[1]) else None
         gb = gwb[1].to(bdt) if (has_b and ctx.needs_input_grad[2]) else None
@@ -1891,8 +1918,7 @@ def geo_metric_sums(prd, tar, clim, wrow):
     if not prd.is_cuda:
         return _geo_metric_sums_torch(prd, tar, clim, wrow)
     _need_cuda(prd, tar, wrow, *([clim] if clim is not None else []))
-    if prd.dtype not in (torch.float32, torch.bfloat16):
-        prd = prd.float()
+    prd = _lowp(prd)
     prd = prd.contiguous()
     tar = tar.float().contiguous()
     wrow = wrow.float().contiguous()
@@ -1900,7 +1926,7 @@ def geo_metric_sums(prd, tar, clim, wrow):
     lib = _lib.load()
     ws = torch.empty(lib.mk_geo_metric_workspace(B, C, H), dtype=torch.float64, device=prd.device)
     out = torch.empty(B, C, 5, dtype=torch.float64, device=prd.device)
-    _lib.check(lib.mk_geo_metric_sums(prd.data_ptr(), _pw_dtype(prd), tar.data_ptr(), clim.data_ptr() if clim is not None else None,
+    _lib.check(lib.mk_geo_metric_sums(prd.data_ptr(), _pw_dtype(prd), tar.data_ptr(), _ptr(clim),
                                       wrow.data_ptr(), ws.data_ptr(), out.data_ptr(), B, C, H, W, _stream()), "mk_geo_metric_sums")
     return out
 
@@ -1961,8 +1987,7 @@ def geo_lp_sums(prd, tar, wrow, p):
     if not prd.is_cuda or tar.requires_grad:
         return _geo_lp_sums_torch(prd, tar, wrow, int(p))
     _need_cuda(prd, tar, wrow)
-    if prd.dtype not in (torch.float32, torch.bfloat16):
-        prd = prd.float()
+    prd = _lowp(prd)
     return _GeoLpSums.apply(prd.contiguous(), tar.float().contiguous(), wrow.detach().float().contiguous(), int(p))
 
 
@@ -2036,10 +2061,6 @@ def degree_power(c_packed, l_off=0, m_off=0):
 # ----------------------------------------------------------------------------
 # input assembly of the step wrappers (csrc/preproc.hip)
 # ----------------------------------------------------------------------------
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _history_sums_torch(xa, wt):
     """``[B, Cn, 2]`` float64 from the concatenated history ``xa`` ``[B, T, Cn, H, W]``, differentiable by autograd."""
     w = wt.double().reshape(1, -1, 1, 1, 1)
@@ -2064,8 +2085,7 @@ def history_sums(x, u, wt):
     if not x.is_cuda:
         return _history_sums_torch(x if u is None else torch.cat([x.float(), u], dim=2), wt.reshape(-1))
     _need_cuda(x, wt, *([u] if u is not None else []))
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        x = x.float()
+    x = _lowp(x)
     x = x.contiguous()
     u = u.float().contiguous() if u is not None else None
     wt = wt.float().reshape(-1).contiguous()
@@ -2101,8 +2121,7 @@ class _InputAssemble(torch.autograd.Function):
     def backward(ctx, g):
         stat, std, mask_chans = ctx.saved_tensors
         x_dtype, mask_src, B, T, C, Cu, Cs, H, W = ctx.meta
-        if g.dtype not in (torch.float32, torch.bfloat16):
-            g = g.float()
+        g = _lowp(g)
         g = g.contiguous()
         gx = torch.empty(B, T, C, H, W, dtype=x_dtype, device=g.device)
         n_mask = mask_chans.numel() if mask_chans is not None else 0
@@ -2132,19 +2151,15 @@ def input_assemble(x, u=None, stat=None, mean=None, std=None, mask_chans=None, m
     Cn = C + (u.shape[2] if u is not None else 0)
     if (mean is None) != (std is None) or (mean is not None and (mean.numel() != B * Cn or std.numel() != B * Cn)):
         raise ValueError(f"input_assemble: mean and std must both be [B, C + Cu] = {(B, Cn)}")
-    if out_dtype not in (torch.float32, torch.bfloat16):
+    if out_dtype not in _LOWP:
         raise ValueError(f"input_assemble: output dtype {out_dtype} is neither fp32 nor bf16")
     if mask_chans is not None and mask_chans.numel() == 0:
         mask_chans = None
     if mask_chans is not None and mask_chans.dtype != torch.int32:
         raise ValueError("input_assemble: mask_chans must be int32")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        x = x.float()
+    x = _lowp(x)
 
-    def f32(t):
-        return t.detach().float().contiguous() if t is not None else None
-
-    return _InputAssemble.apply(x.contiguous(), f32(u), f32(stat), f32(mean), f32(std),
+    return _InputAssemble.apply(x.contiguous(), _f32(u), _f32(stat), _f32(mean), _f32(std),
                                 mask_chans.contiguous() if mask_chans is not None else None, int(mask_src), out_dtype)
 
 
@@ -2277,14 +2292,10 @@ def rollout_tail(yn, mean=None, std=None, mask=None, mask_chans=None, x_last=Non
         if t is not None and (K == 0 or t.numel() != K):
             raise ValueError(f"rollout_tail: {name} {tuple(t.shape)} needs K = {K} emitted channels")
 
-    def f32(t):
-        return t.detach().float().contiguous() if t is not None else None
-
-    if yn.dtype not in (torch.float32, torch.bfloat16):
-        yn = yn.float()
+    yn = _lowp(yn)
     yn = yn.detach()
-    mean, std, mask, scale, tar, clim, wrow = (f32(t) for t in (mean, std, mask, scale, tar, clim, wrow))
-    emit_scale, emit_shift = f32(emit_scale), f32(emit_shift)
+    mean, std, mask, scale, tar, clim, wrow = (_f32(t) for t in (mean, std, mask, scale, tar, clim, wrow))
+    emit_scale, emit_shift = _f32(emit_scale), _f32(emit_shift)
     if not (residual or hold_chans is not None):
         x_last = None
     if x_last is not None:
@@ -2390,11 +2401,8 @@ def field_stats(x, wrow, tsum, prev=None, pivot=None, wind_u=None, wind_v=None):
     if (wind_u is None) != (wind_v is None) or (wind_u is not None and wind_u.numel() != wind_v.numel()):
         raise ValueError("field_stats: wind_u and wind_v must name the same number of channels")
 
-    def f32(t):
-        return t.detach().float().contiguous() if t is not None else None
-
     x = x.detach()
-    prev, pivot, wrow = f32(prev), f32(pivot), f32(wrow)
+    prev, pivot, wrow = _f32(prev), _f32(pivot), _f32(wrow)
     if not (hip and x.is_cuda):
         return _field_stats_torch(x, prev, pivot, wrow, tsum, wind_u, wind_v)
     _need_cuda(*[t for t in (prev, pivot, wrow) if t is not None])
@@ -2538,10 +2546,7 @@ def cos_zenith(eph, sin_lat, cos_lat, lon_rad, out=None):
         if t.device != eph.device:
             raise ValueError(f"cos_zenith: tables on {t.device}, eph on {eph.device}")
 
-    def f32(t):
-        return t.detach().float().contiguous()
-
-    eph, sin_lat, cos_lat, lon_rad = f32(eph), f32(sin_lat), f32(cos_lat), f32(lon_rad)
+    eph, sin_lat, cos_lat, lon_rad = _f32(eph), _f32(sin_lat), _f32(cos_lat), _f32(lon_rad)
     _lib.check(_lib.load().mk_cos_zenith(eph.data_ptr(), sin_lat.data_ptr(), cos_lat.data_ptr(), lon_rad.data_ptr(),
                                          out.data_ptr(), n, H, W, _stream()), "mk_cos_zenith")
     return out
@@ -2865,7 +2870,7 @@ def token_layer_norm_supported(x, normalized_shape, weight=None, bias=None):
     fp32 parameters (or none).  Everything else is the caller's torch path."""
     shape, L = _trailing(normalized_shape)
     k = len(shape)
-    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and k >= 1 and x.dim() >= k):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in _LOWP and k >= 1 and x.dim() >= k):
         return False
     if tuple(x.shape[x.dim() - k:]) != shape or x.numel() == 0:
         return False
@@ -2950,9 +2955,9 @@ class _TokenLayerNorm(torch.autograd.Function):
                 return None, 0
             return _token_rows(g if g.dtype in dtypes else g.to(dtypes[0]), k, L)
 
-        gy, gy_ld = rows_of(gy, (torch.float32, torch.bfloat16))
+        gy, gy_ld = rows_of(gy, _LOWP)
         gy2, gy2_ld = rows_of(gy2, (torch.bfloat16,))
-        gs, gs_ld = rows_of(gs, (torch.float32, torch.bfloat16))
+        gs, gs_ld = rows_of(gs, _LOWP)
         gx = torch.empty_strided(x.shape, x.stride(), dtype=x.dtype, device=x.device)
         gr = torch.empty_strided(r.shape, r.stride(), dtype=r.dtype, device=x.device) if has_r and ctx.needs_input_grad[1] else None
         want = (has_w and ctx.needs_input_grad[2]) or (has_b and ctx.needs_input_grad[3])
@@ -3228,14 +3233,10 @@ def _toklin_x3_gelu_grad(g, g_ld, pre, R, O):
     return gelu_backward(pre.view(1, 1, R * O), gc.view(1, 1, R * O))[0].view(R, O)
 
 
-_TOKLIN_BF16 = _LinearArith(torch.bfloat16, 8, (torch.float32, torch.bfloat16), False, lambda w: token_linear_pack_raw(w),
+_TOKLIN_BF16 = _LinearArith(torch.bfloat16, 8, _LOWP, False, lambda w: token_linear_pack_raw(w),
                             _toklin_bf16_gemm, _toklin_bf16_dgrad, lambda *a: token_linear_wgrad_raw(*a), _toklin_bf16_gelu_grad)
 _TOKLIN_X3 = _LinearArith(torch.float32, 4, (torch.float32,), True, _toklin_x3_weight,
                           _toklin_x3_gemm, _toklin_x3_dgrad, lambda *a: token_linear_x3_wgrad_raw(*a), _toklin_x3_gelu_grad)
-
-
-def _toklin_bias(bias):
-    return None if bias is None else bias.detach().float().contiguous()        # fp32 as it is; a bf16 bias exactly
 
 
 def _toklin_grad_rows(g, O, a):
@@ -3260,7 +3261,7 @@ def _token_linear_node(name, a, doc):
         xr, x_ld = _toklin_rows(x, a.unit)
         R = x.numel() // I
         w = a.weight(weight)
-        bf = _toklin_bias(bias)
+        bf = _f32(bias)
         need = any(ctx.needs_input_grad[:3])
         ar, a_ld = (None, 0) if addend is None else _toklin_rows(addend.detach().reshape(-1, O), a.unit)
         out = torch.empty(x.shape[:-1] + (O,), dtype=a.dtype if addend is None else torch.float32, device=x.device)
@@ -3313,10 +3314,10 @@ def _token_mlp_node(name, a, doc):
         w1p, w2p = a.weight(w1), a.weight(w2)
         need = any(ctx.needs_input_grad[:5])
         act = torch.empty(R, H, dtype=a.dtype, device=x.device)
-        pre = a.gemm(xr, x_ld, w1p, _toklin_bias(b1), R, act, True, need)
+        pre = a.gemm(xr, x_ld, w1p, _f32(b1), R, act, True, need)
         ar, a_ld = (None, 0) if addend is None else _toklin_rows(addend.detach().reshape(-1, O), a.unit)
         out = torch.empty(x.shape[:-1] + (O,), dtype=a.dtype if addend is None else torch.float32, device=x.device)
-        a.gemm(act, H, w2p, _toklin_bias(b2), R, out, False, False, ar, a_ld)
+        a.gemm(act, H, w2p, _f32(b2), R, out, False, False, ar, a_ld)
         if need:
             ctx.save_for_backward(xr, w1p, w2p, pre, act)
         ctx.cfg = (x_ld, R, tuple(x.shape), w1.dtype, _dtype_of(b1), w2.dtype, _dtype_of(b2))
@@ -3435,7 +3436,6 @@ def token_mlp(x, w1, b1, w2, b2, addend=None):
 # Opt-in by the rule of DESIGN section 19 until every row of tools/patch_bench.py has been measured faster than the torch path
 # (DESIGN section 29).
 PATCH_DEFAULT = "torch"
-_PATCH_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 
 
 def patch_hip():
@@ -3488,7 +3488,7 @@ def patchify_raw(img, tok, patch, order=0, ldt=None):
     _need_cuda(img, tok)
     B, C, H, W = img.shape
     assert img.is_contiguous() and img.device == tok.device
-    _lib.check(_lib.load().mk_patchify(img.data_ptr(), _PATCH_DTYPES[img.dtype], tok.data_ptr(), _PATCH_DTYPES[tok.dtype],
+    _lib.check(_lib.load().mk_patchify(img.data_ptr(), _DTYPE_CODE[img.dtype], tok.data_ptr(), _DTYPE_CODE[tok.dtype],
                                        C * patch[0] * patch[1] if ldt is None else ldt, B, C, H, W, patch[0], patch[1], order,
                                        _stream()), "mk_patchify")
     return tok
@@ -3499,8 +3499,8 @@ def unpatchify_raw(tok, img, patch, order=0, ldt=None):
     _need_cuda(img, tok)
     B, C, H, W = img.shape
     assert img.is_contiguous() and img.device == tok.device
-    _lib.check(_lib.load().mk_unpatchify(tok.data_ptr(), _PATCH_DTYPES[tok.dtype], C * patch[0] * patch[1] if ldt is None else ldt,
-                                         img.data_ptr(), _PATCH_DTYPES[img.dtype], B, C, H, W, patch[0], patch[1], order, _stream()),
+    _lib.check(_lib.load().mk_unpatchify(tok.data_ptr(), _DTYPE_CODE[tok.dtype], C * patch[0] * patch[1] if ldt is None else ldt,
+                                         img.data_ptr(), _DTYPE_CODE[img.dtype], B, C, H, W, patch[0], patch[1], order, _stream()),
                "mk_unpatchify")
     return img
 
@@ -3517,7 +3517,7 @@ class _Patchify(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         shape, dtype, patch, order = ctx.cfg
-        g = g if g.dtype in _PATCH_DTYPES else g.float()
+        g = _lowp(g)
         return unpatchify_raw(g.contiguous(), torch.empty(shape, dtype=dtype, device=g.device), patch, order), None, None, None
 
 
@@ -3533,12 +3533,12 @@ class _Unpatchify(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         shape, dtype, patch, order = ctx.cfg
-        g = g if g.dtype in _PATCH_DTYPES else g.float()
+        g = _lowp(g)
         return (patchify_raw(g.contiguous(), torch.empty(shape, dtype=dtype, device=g.device), patch, order),) + (None,) * 6
 
 
 def _patch_kernels_take(t, dtype):
-    return t.is_cuda and t.numel() > 0 and t.dtype in _PATCH_DTYPES and dtype in _PATCH_DTYPES
+    return t.is_cuda and t.numel() > 0 and t.dtype in _DTYPE_CODE and dtype in _DTYPE_CODE
 
 
 def patchify(img, patch, order=0, dtype=None):
@@ -3580,7 +3580,7 @@ def _patch_embed_supported(a, img, weight, bias):
     if a.x3:
         if img.dtype != torch.float32 or lowp:
             return False
-    elif img.dtype not in _PATCH_DTYPES or not (lowp or all(t.dtype == torch.bfloat16 for t in (img, weight, bias) if t is not None)):
+    elif img.dtype not in _DTYPE_CODE or not (lowp or all(t.dtype == torch.bfloat16 for t in (img, weight, bias) if t is not None)):
         return False
     return _toklin_param_ok(a, weight, (E, C, p0, p1), img.device) and (bias is None or _toklin_param_ok(a, bias, (E,), img.device))
 
@@ -3608,7 +3608,7 @@ def _patch_embed_node(name, a, doc):
         N = hp * wp
         rows = patchify_raw(img.detach().contiguous(), torch.empty(B * N, F, dtype=a.dtype, device=img.device), (p0, p1), 0)
         w = a.weight(weight.detach().reshape(E, F))
-        bf = _toklin_bias(bias)
+        bf = _f32(bias)
         out = torch.empty(B, N, E, dtype=a.dtype if pos is None else torch.float32, device=img.device)
         if pos is not None:
             pr, p_ld = _toklin_rows(pos.detach().reshape(N, E), a.unit)

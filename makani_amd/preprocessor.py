@@ -53,7 +53,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import comm
+from . import comm, ops
 from .mappings import copy_to_parallel_region, reduce_from_parallel_region
 
 _STAT_MODES = ("exponential", "mean")
@@ -281,7 +281,6 @@ class Preprocessor2D(nn.Module):
             self.history_mean = torch.zeros((1, 1, 1, 1), dtype=torch.float32, device=x.device)
             self.history_std = torch.ones((1, 1, 1, 1), dtype=torch.float32, device=x.device)
             return
-        from . import ops
         xr = self.expand_history(x, self.n_history + 1)
         wt = self.history_normalization_weights.reshape(-1)
         if use_hip and xr.is_cuda and not (xr.requires_grad and torch.is_grad_enabled()):
@@ -453,7 +452,6 @@ class Preprocessor2D(nn.Module):
         needs_grad = inp.requires_grad and torch.is_grad_enabled()
         if not inp.is_cuda or (stats and needs_grad):
             return self._assemble_torch(inp, out_dtype)
-        from . import ops
         x = self.expand_history(inp, self.n_history + 1)
         uinp, _ = self._unpredicted()
         cn = x.shape[2] + (uinp.shape[2] if uinp is not None else 0)

@@ -16,7 +16,6 @@ Spatial model parallelism (``comm.get_size("spatial") > 1``) selects the distrib
 filter runs on the HIP transforms with the ``mk_spec_cmlp_*`` channel MLP in between (``spectral_convolution.SpectralAttention``).
 """
 import math
-import os
 from functools import partial
 
 import torch
@@ -24,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
-from . import comm
+from . import comm, ops
 from .distributed import DistributedInverseRealFFT2, DistributedInverseRealSHT, DistributedRealFFT2, DistributedRealSHT
 from .layer_norm import DistributedInstanceNorm2d, DistributedLayerNorm
 from .layers import (Conv1x1, DropPath, EncoderDecoder, InstanceNorm2d, InverseRealFFT2, MLP, RealFFT2, _engine_field,
@@ -377,9 +376,8 @@ class SphericalFourierNeuralOperatorNet(nn.Module):
 
     def _engine_arena(self, x):
         """The per-step arena of the pointwise stack (``ops.EngineArena``) when this call runs on the bf16 engine, else None."""
-        from . import ops
         from .layers import Conv1x1
-        if not (x.is_cuda and x.dim() == 4 and os.environ.get("MK_ENGINE_ARENA", "1") != "0"):
+        if not (x.is_cuda and x.dim() == 4 and ops._knob("MK_ENGINE_ARENA", "1") != "0"):
             return None
         if not (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)):
             return None

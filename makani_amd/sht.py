@@ -66,8 +66,7 @@ class RealSHT(_SHTBase):
     def forward(self, x):
         if x.shape[-2] != self.nlat or x.shape[-1] != self.nlon:
             raise ValueError(f"expected [..., {self.nlat}, {self.nlon}], got {tuple(x.shape)}")
-        if x.dtype not in (torch.float32, torch.bfloat16):
-            x = x.float()
+        x = ops._lowp(x)
         lead, x3 = self._flatten(x.contiguous(), (self.nlat, self.nlon))
         c = ops.spec_unpack(self.forward_packed(x3), 0, 0)
         return c.reshape(*lead, self.lmax, self.mmax)

@@ -49,7 +49,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import comm
+from . import comm, ops
 from .distributed import compute_split_shapes
 from .losses import GridQuadrature
 
@@ -136,7 +136,6 @@ class DatasetStats:
         replay; every further replay of the graph needs ``count(T)``, or ``finalize`` divides by too little."""
         if batch.dim() != 4 or tuple(batch.shape[1:]) != (self.C, self.H, self.W) or batch.shape[0] < 1:
             raise ValueError(f"DatasetStats.update: batch {tuple(batch.shape)} is not [T, {self.C}, {self.H}, {self.W}]")
-        from . import ops
         batch = batch.float()
         if self.device is None:
             self._alloc(batch.device)

@@ -23,11 +23,10 @@ Deviations from the reference (a fork with local edits), keeping the evident int
   ``target: "default"``).
 * ``history_denormalize`` works in the statistics modes and ``add_residual`` is out of place (``preprocessor.py``).
 """
-import os
-
 import torch
 from torch import nn
 
+from . import ops
 from .preprocessor import Preprocessor2D
 
 
@@ -41,7 +40,7 @@ def _engine_input_dtype(model, inp):
         return None
     if not (model.big_skip and model.out_shape == model.inp_shape and (inp.shape[-2] * inp.shape[-1]) % 8 == 0):
         return None
-    if os.environ.get("MK_CONV_ENGINE", "pce") != "pce":
+    if ops._knob("MK_CONV_ENGINE", "pce") != "pce":
         return None
     return torch.bfloat16
 

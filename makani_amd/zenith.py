@@ -32,6 +32,8 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import ops
+
 _F32 = np.float32
 _J2000 = np.datetime64("2000-01-01T12:00:00", "us")
 _EPOCH = datetime.datetime(1970, 1, 1, tzinfo=datetime.timezone.utc)
@@ -239,5 +241,4 @@ class CosZenith(nn.Module):
             raise ValueError(f"CosZenith: eph {tuple(eph.shape)} must be [B, T, 4]")
         if not (eph.is_cuda and use_hip):
             return self._forward_torch(eph)
-        from . import ops
         return ops.cos_zenith(eph, self.sin_lat, self.cos_lat, self.lon_rad).unsqueeze(2)

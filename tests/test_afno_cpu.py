@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 BOUND = 2e-6
 NET_KW = dict(inp_shape=(24, 40), patch_size=(4, 4), inp_chans=3, out_chans=2, embed_dim=16, num_layers=2, num_blocks=4,
               mlp_ratio=2, normalization_layer="instance_norm", skip_fno="linear", sparsity_threshold=0.5)
@@ -211,3 +213,19 @@ def test_file_path_registration_like_model_registry():
     spec.loader.exec_module(module)
     net = module.AdaptiveFourierNeuralOperatorNet(**dict(NET_KW, num_layers=1))
     assert isinstance(net, torch.nn.Module) and tuple(net(torch.zeros(1, 3, 24, 40)).shape) == (1, 2, 24, 40)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_spec_bdmlp_mask", (_A, _A + 8, _A, 8), "operands must be 16-byte aligned"),
+    ("mk_spec_bdmlp_wgrad", (_A, _A + 8, _A, _A, 4096, 2, 4, 4), "operands must be 16-byte aligned", "spec_bdmlp_check"),
+    ("mk_spec_bdmlp_wgrad", (_A, _A, _A, _A + 8, 4096, 2, 4, 4), "the block weight gradient needs its 16-byte aligned workspace"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

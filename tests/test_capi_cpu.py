@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from makani_amd import _lib, ops
 from oracle import sht as osht
 
@@ -81,6 +83,45 @@ def test_build_header_list_is_what_the_sources_include():
                 todo.append(target)
     assert seen == {norm(os.path.join(build.CSRC, h)) for h in build.HEADERS}
     assert len(build.HEADERS) == len(set(build.HEADERS))
+
+
+def test_readme_knob_table_is_what_the_code_reads():
+    """README's "Environment knobs" names exactly the ``MK_*`` variables that the package, its C sources and bench.py read --
+    directly, or by name through ``ops._knob`` / ``ops._hip_or_torch`` -- and every switch of ``ops.KNOBS`` has such a read."""
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    documented = set(re.findall(r"MK_[A-Z0-9_]*[A-Z0-9]", readme.split("## Environment knobs", 1)[1]))
+    files = [os.path.join(ROOT, "bench.py")]
+    for sub in ("makani_amd", os.path.join("makani_amd", "csrc")):
+        d = os.path.join(ROOT, sub)
+        files += [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith((".py", ".hip", ".h", ".cpp"))]
+    read = set()
+    for path in files:
+        read |= set(re.findall(r'(?:getenv\(|os\.environ\.get\(|os\.environ\[|_knob\(|_hip_or_torch\()\s*"(MK_[A-Z0-9_]+)"', open(path).read()))
+    assert documented == read, (sorted(documented - read), sorted(read - documented))
+    assert set(ops.KNOBS) <= read, sorted(set(ops.KNOBS) - read)
+
+
+@pytest.mark.parametrize("env", sorted(set(ops.KNOBS) - {"MK_SPECTRAL_GEMM"}))
+def test_knob_reader_validates(env, monkeypatch):
+    """``ops._knob``: the default where the variable is unset, every allowed value as it is, anything else an error that names
+    the variable and its values.  (``MK_SPECTRAL_GEMM`` reaches the code through ``ops.SPECTRAL_GEMM`` and ``_gemm_mode``.)"""
+    values = ops.KNOBS[env]
+    monkeypatch.delenv(env, raising=False)
+    for v in values:
+        assert ops._knob(env, v) == v
+    for v in values:
+        monkeypatch.setenv(env, v)
+        assert ops._knob(env, values[0]) == v
+    monkeypatch.setenv(env, "bogus")
+    with pytest.raises(ValueError, match=re.escape(f"unknown {env} 'bogus' ({' | '.join(values)})")):
+        ops._knob(env, values[0])
+
+
+def test_spectral_gemm_mode_keeps_its_own_message():
+    assert ops.KNOBS["MK_SPECTRAL_GEMM"] == ("bf16x3", "f32")
+    assert [ops._gemm_mode(m) for m in ops.KNOBS["MK_SPECTRAL_GEMM"]] == ["bf16x3", "f32"]
+    with pytest.raises(ValueError, match=re.escape("unknown spectral GEMM mode 'bogus' (bf16x3 | f32)")):
+        ops._gemm_mode("bogus")
 
 
 @pytest.mark.parametrize("grid", ["equiangular", "legendre-gauss"])
@@ -173,3 +214,28 @@ def test_errors_are_loud():
     # CPU tensors never reach a kernel, and there is no CPU fallback
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.rfft_raw(torch.zeros(1, 4, 8), ops.fft_twiddles(8), 5, 1.0, 1.0, 1.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_pce_gemm_ex", (_A, _A + 8, _A) + (None,) * 5 + (0, None, 1, 64, 64, 64), "x and the weight image must be 16-byte aligned"),
+    ("mk_pce_gemm_ex", (_A, _A, _A, None, _A, _A + 4, None, None, 0, None, 1, 64, 64, 64), "addend_affine must be 8-byte aligned"),
+    ("mk_pce_mlp", (_A, _A, _A, _A + 8, None, None, None, None, None, 0, 1, 64, 128, 64, 64), "fields and the weight image must be 16-byte aligned"),
+    ("mk_pce_mlp", (_A, _A, _A, _A, _A + 4, None, None, None, None, 1, 1, 64, 128, 64, 64), "fields and the weight image must be 16-byte aligned"),
+    ("mk_conv1x1_wgrad_act", (_A, _A + 8, _A, 1, 64, 64, 64, 1), "gy and x must be 16-byte aligned (the tiles are read as uint4)"),
+    ("mk_conv1x1_wgrad", (_A + 4, _A, _A, 1, 64, 64, 64), "gy and x must be 16-byte aligned (the tiles are read as uint4)", "mk_conv1x1_wgrad_act"),
+    ("mk_conv1x1_x3", (_A, 8, _A + 8, 16, _A, 16, 4, 8, 16, 1, 0, 0, 0, 0), "operands must be 16-byte aligned", "conv_x3_launch"),
+    ("mk_conv1x1_x3", (_A, 16, _A, 16, _A + 4, 8, 4, 8, 16, 1, 0, 0, 0, 2), "operands must be 16-byte aligned", "conv_x3_launch"),
+    ("mk_conv1x1_x3_bias_act", (_A + 8, 8, _A, 16, _A, 16, 4, 8, 16, 1, 0, 0, _A, 1), "operands must be 16-byte aligned", "conv_x3_launch"),
+    ("mk_spec_mix_fwd", (_A + 8, _A, _A, 4, 5, 1, 2, 4, 0, 0), "operands must be 16-byte aligned", "spec_mix_check"),
+    ("mk_spec_mix_dgrad", (_A, _A, _A + 8, 4, 5, 1, 2, 4, 0, 0), "operands must be 16-byte aligned", "spec_mix_check"),
+    ("mk_spec_mix_wgrad", (_A, _A + 8, _A, 4, 5, 1, 2, 4, 0, 0), "operands must be 16-byte aligned", "spec_mix_check"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

@@ -1,11 +1,14 @@
 """CPU tests of the channel layer norm: the C ABI is exported and bound, and ``DistributedLayerNorm`` on the CPU is still the
 reference's formulation (transpose -> nn.LayerNorm -> transpose), bit for bit; the constants of chnorm_checks.py against its
 emulation of the kernels' arithmetic.  No kernel launches here."""
+import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import capi_checks as capi
 import chnorm_checks as cc
+
 from makani_amd import _lib, ops
 from makani_amd.layer_norm import DistributedLayerNorm
 
@@ -117,3 +120,20 @@ def test_rows_and_field_are_inverse():
     x = torch.arange(2 * 3 * 5.0).view(2, 3, 5)
     r = cc.rows(x)
     assert r.shape == (10, 3) and torch.equal(r[7], x[1, :, 2]) and torch.equal(cc.field(r, 2), x)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_chan_layernorm_fwd", (_A + 2, 0, _A, _A, _A, 0, _A, 1, 8, 16, 1e-5, 0), "field not aligned to its element"),
+    ("mk_chan_layernorm_fwd", (_A, 0, _A, _A, _A, 1, _A + 4, 1, 8, 16, 1e-5, 0), "fp32 stream not aligned"),
+    ("mk_chan_layernorm_bwd", (_A, 0, _A + 1, 1, _A, _A, _A, _A, _A, _A, 1, 8, 16, 0), "field not aligned to its element"),
+    ("mk_chan_layernorm_bwd", (_A, 0, _A, 0, _A, _A, _A, _A, _A, _A + 2, 1, 8, 16, 0), "fp32 stream not aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

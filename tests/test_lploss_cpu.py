@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from oracle import losses as ol
 
 LOSS_TOL, GRAD_TOL = 2e-6, 1e-6
@@ -231,3 +233,21 @@ def test_loss_handler_cpu(spec, n_future, training, tmp_path):
     assert out.dtype == torch.float32
     assert abs(float(out.detach()) - want) < LOSS_TOL * abs(want)
     assert rel(x.grad, gwant) < GRAD_TOL
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_geo_lp_sums", (_A + 2, 0, _A, _A, _A, _A, 2, 1, 2, 4, 8), "prediction not aligned to its element"),
+    ("mk_geo_lp_sums", (_A, 0, _A, _A + 2, _A, _A, 1, 1, 2, 4, 8), "fp32 stream not 4-byte aligned"),
+    ("mk_geo_lp_sums", (_A + 2, 1, _A, _A, _A, _A + 4, 2, 1, 2, 4, 8), "fp64 buffer not 8-byte aligned"),
+    ("mk_geo_lp_bwd", (_A, 0, _A, _A, _A, _A + 2, 2, 1, 2, 4, 8), "prediction or its gradient not aligned to its element"),
+    ("mk_geo_lp_bwd", (_A, 1, _A, _A, _A + 2, _A, 1, 1, 2, 4, 8), "fp32 stream not 4-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from oracle.losses import quad_weight
 
 TOL = 1e-5
@@ -266,3 +268,20 @@ def test_matmul_parallel_raises(monkeypatch):
     with pytest.raises(NotImplementedError):
         MetricsHandler(params, torch.ones(len(CHANNELS)), torch.zeros(len(CHANNELS), 16, 24), torch.device("cpu"))
     MetricsHandler(make_params(16, 24), torch.ones(len(CHANNELS)), torch.zeros(len(CHANNELS), 16, 24), torch.device("cpu"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_geo_metric_sums", (_A + 2, 0, _A, None, _A, _A, _A, 1, 2, 4, 8), "prediction not aligned to its element"),
+    ("mk_geo_metric_sums", (_A + 1, 1, _A, None, _A, _A, _A, 1, 2, 4, 8), "prediction not aligned to its element"),
+    ("mk_geo_metric_sums", (_A, 0, _A + 2, None, _A, _A, _A, 1, 2, 4, 8), "fp32 stream not 4-byte aligned"),
+    ("mk_geo_metric_sums", (_A, 1, _A, _A + 2, _A, _A, _A, 1, 2, 4, 8), "fp32 stream not 4-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

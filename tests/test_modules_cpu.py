@@ -2,6 +2,7 @@
 key list, parameter annotations, weight storage layout.  No kernel launches."""
 import math
 import os
+import re
 
 import numpy as np
 import pytest
@@ -88,6 +89,16 @@ def test_fft_variant_constructs():
                                           max_modes=(16, 16)))
     x = torch.randn(1, 4, 32, 64)
     assert net(x).shape == (1, 2, 32, 64)
+
+
+@pytest.mark.parametrize("env,bad,values", [("MK_CONV_ENGINE", "PCE", "pce | blas"), ("MK_SPEC_MIX", "off", "0 | 1")])
+def test_a_mistyped_switch_stops_the_forward(env, bad, values, monkeypatch):
+    """The switches of the pointwise stack go through ``ops._knob``: a value outside the set is an error in the first forward,
+    on any device (it is read before the first transform, which is what refuses CPU tensors), not a silently chosen path."""
+    net = SphericalFourierNeuralOperatorNet(**KW)
+    monkeypatch.setenv(env, bad)
+    with pytest.raises(ValueError, match=re.escape(f"unknown {env} {bad!r} ({values})")):
+        net(torch.randn(1, 4, 33, 64))
 
 
 # --------------------------------------------------------------------------- losses (utils/losses.py, utils/grids.py)

@@ -12,6 +12,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import capi_checks as capi
+
 TOL = 1e-6
 
 
@@ -352,3 +354,18 @@ def test_reducer_index_runs(monkeypatch):
     assert plan == {"h": [0, 2, 3, 5], "w": [3]}
     cache = {}
     assert optim._reducer_for(ps, torch.device("cpu"), cache) is optim._reducer_for(ps, torch.device("cpu"), cache)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_adam_step", (_A, _A, _A, _A + 4, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1), "buffers must be 16-byte aligned"),
+    ("mk_adam_step", (_A, _A + 8, _A, _A, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1), "buffers must be 16-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from test_stepper_cpu import make_params as stepper_params, toy_model
 
 NAMES = ["u10m", "t2m", "z500"]
@@ -258,3 +260,22 @@ def test_matmul_parallel_raises(monkeypatch, tmp_path):
     monkeypatch.setattr(comm, "get_size", lambda name: 2 if name == "matmul" else 1)
     with pytest.raises(NotImplementedError):
         Rollout(params, wrap)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_rollout_tail", (_A + 2, 0) + (None,) * 4 + (0, None, 0, 0, None, None, 0, _A) + (None,) * 10 + (0, 1, 2, 4, 8),
+     "model output not aligned to its element"),
+    ("mk_rollout_tail", (_A, 1) + (None,) * 4 + (0, None, 0, 0, None, None, 0, _A + 2) + (None,) * 10 + (0, 1, 2, 4, 8),
+     "fp32 / int32 stream not 4-byte aligned"),
+    ("mk_rollout_tail", (_A, 0) + (None,) * 4 + (0, None, 0, 0, None, None, 0, _A, _A, None, _A, _A + 4, _A) + (None,) * 5 + (0, 1, 2, 4, 8),
+     "fp64 buffer not 8-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

@@ -4,6 +4,8 @@ being the torch formulation whatever the knob says."""
 import pytest
 import torch
 
+import capi_checks as capi
+
 from makani_amd import comm, ops
 from makani_amd.sht import InverseRealSHT, RealSHT
 from makani_amd.spectral_convolution import SpectralAttention
@@ -166,3 +168,17 @@ def test_cpu_forward_is_the_torch_formulation(monkeypatch, knob):
     assert res is x and torch.allclose(y, want, rtol=1e-6, atol=1e-6)
     y3 = mod(x, want_row_sums=True)
     assert len(y3) == 3 and y3[2] is None and torch.equal(y3[0], y)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_spec_cmlp_wgrad", (_A, _A, _A, _A + 8, 240, 241, 1, 384, 768, 0, 0, 0), "the shared weight gradient needs its 16-byte aligned workspace"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from makani_amd import ops
 from makani_amd.distributed import compute_split_shapes
 
@@ -97,3 +99,19 @@ def test_norms_from_spectrum_adds_up_over_shards(lsplit, msplit):
             shard = c[l0:l0 + ls[i], m0:m0 + ms[j]].contiguous()
             total = total + loss.norms_from_spectrum(shard, batch, l0, m0)
     assert ((total - whole).abs() <= 1e-12 * whole.abs()).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_degree_power", (_A + 4, _A, _A, 4, 5, 6, 0, 0), "buffer not 8-byte aligned"),
+    ("mk_degree_power", (_A, _A, _A + 4, 4, 5, 6, 0, 0), "buffer not 8-byte aligned"),
+    ("mk_degree_power_bwd", (_A, _A, _A + 4, 4, 5, 6, 0, 0), "buffer not 8-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

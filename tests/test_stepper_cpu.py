@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from makani_amd.preprocessor import Preprocessor2D, get_preprocessor
 from makani_amd.stepper import MultiStepWrapper, SingleStepWrapper
 
@@ -332,3 +334,25 @@ def test_state_dict_keys_are_the_models():
         wrap = cls(make_params(H, W, add_grid=True, n_future=1), lambda: SphericalFourierNeuralOperatorNet(**kw))
         assert list(wrap.state_dict()) == keys
         assert isinstance(wrap.preprocessor, Preprocessor2D) and isinstance(wrap.model, SphericalFourierNeuralOperatorNet)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_input_assemble", (_A + 2, 0, None, None, None, None, None, 0, 0, _A, 0, 1, 2, 3, 0, 0, 4, 8), "x or output not aligned to its element"),
+    ("mk_input_assemble", (_A, 1, None, None, None, None, None, 0, 0, _A + 1, 1, 1, 2, 3, 0, 0, 4, 8), "x or output not aligned to its element"),
+    ("mk_input_assemble", (_A, 0, _A, _A, _A + 2, _A, None, 0, 0, _A, 0, 1, 2, 3, 1, 1, 4, 8), "fp32 / int32 stream not 4-byte aligned"),
+    ("mk_input_assemble", (_A, 0, None, _A, None, None, _A + 2, 1, 0, _A, 0, 1, 2, 3, 0, 1, 4, 8), "fp32 / int32 stream not 4-byte aligned"),
+    ("mk_input_assemble_bwd", (_A, 0, None, None, None, 0, 0, _A + 2, 0, 1, 2, 3, 0, 0, 4, 8), "gradient not aligned to its element"),
+    ("mk_input_assemble_bwd", (_A, 1, None, _A + 2, None, 0, 0, _A, 0, 1, 2, 3, 0, 0, 4, 8), "fp32 / int32 stream not 4-byte aligned"),
+    ("mk_history_sums", (_A + 2, 0, None, _A, _A, _A, 1, 2, 3, 0, 4, 8), "x not aligned to its element"),
+    ("mk_history_sums", (_A, 0, None, _A + 2, _A, _A, 1, 2, 3, 0, 4, 8), "fp32 stream not 4-byte aligned"),
+    ("mk_history_sums", (_A, 1, _A, _A, _A + 4, _A, 1, 2, 3, 1, 4, 8), "fp64 buffer not 8-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

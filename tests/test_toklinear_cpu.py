@@ -7,6 +7,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import toklinear_checks as tc
+
+import capi_checks as capi
 from makani_amd import layers, ops
 
 BF = torch.bfloat16
@@ -168,3 +170,23 @@ def test_a_missing_bias_is_caught(small):
             check(nobias.to(BF), s["ref"], "no bias")
     with pytest.raises(AssertionError):
         tc.check_addend((s["addend"].double() + nobias.to(BF).double()).float(), s["addend"], s["ref"], "no bias")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_token_linear_fwd", (_A + 8, 16, _A, 16, None, _A, 8) + (None, 0) * 5 + (3, 8, 16), "operand not 16-byte aligned"),
+    ("mk_token_linear_fwd", (_A, 16, _A, 16, _A + 4, _A, 8) + (None, 0) * 5 + (3, 8, 16), "bias not 16-byte aligned"),
+    ("mk_token_linear_pack", (_A + 8, 0, 16, _A, 16, 8, 16, 0), "operand not 16-byte aligned"),
+    ("mk_token_linear_gelu_grad", (_A, 8, _A + 8, 8, _A, 8, 3, 8), "operand not 16-byte aligned"),
+    ("mk_token_linear_wgrad", (_A, 8, _A, 16, _A + 8, 16, None, None, 3, 8, 16, 1), "operand not 16-byte aligned"),
+    ("mk_token_linear_wgrad", (_A, 8, _A, 16, _A, 16, _A + 4, None, 3, 8, 16, 1), "db not 16-byte aligned"),
+    ("mk_token_linear_wgrad", (_A, 8, _A, 16, _A, 16, None, _A + 8, 4096, 8, 16, 2), "workspace null or not 16-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

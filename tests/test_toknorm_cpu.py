@@ -7,6 +7,8 @@ import torch.nn as nn
 
 import toknorm_checks as tc
 
+import capi_checks as capi
+
 
 def test_emulation_stays_within_half_of_each_constant():
     worst = tc.emulation_worst()
@@ -157,3 +159,19 @@ def test_symbols_have_signatures_and_validate():
     assert b"mk_token_layernorm_fwd" in lib.mk_last_error()
     assert bwd(stats=None) == 1 and bwd(ws=None) == 1 and bwd(gr=p) == 1 and bwd(gyld=7) == 1 and bwd(xd=5) == 1
     assert b"mk_token_layernorm_bwd" in lib.mk_last_error()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_token_layernorm_bwd", (_A, 0, 8, None, 0, 8, _A + 2, 0, 8, None, 8, None, 0, 8, _A, _A, _A, None, _A, _A, 2, 8), "tensor not aligned to its element"),
+    ("mk_token_layernorm_bwd", (_A, 0, 8, None, 0, 8, _A, 0, 8, None, 8, None, 0, 8, _A + 2, _A, _A, None, _A, _A, 2, 8), "fp32 stream not aligned"),
+    ("mk_token_layernorm_fwd", (_A, 0, 8, None, 0, 8, _A, _A + 2, _A, 0, 8, None, 8, None, 0, 8, _A, 2, 8, 1e-5), "fp32 stream not aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

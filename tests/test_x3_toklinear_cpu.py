@@ -9,6 +9,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import kernel_checks as kc
+
+import capi_checks as capi
 from makani_amd import _lib, layers, ops
 
 FWD_SHAPES = [(1, 4, 4), (33, 36, 68), (129, 132, 132), (200, 280, 260)]       # (R, I, O) of the GPU test
@@ -222,3 +224,21 @@ def test_planted_wgrad_defects_are_caught(R, O, I, slabs):
     db, db_bad = dy.double().sum(0), dy.double()[1:].sum(0)
     tol = U * db_bad.abs() + 2.0 ** -40 * dy.double().abs().sum(0)
     assert bool(((db.float().double() - db_bad).abs() > tol).any())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_token_linear_x3_fwd", (_A, 8, _A, 8, 0, None, _A + 4, 4) + (None, 0) * 3 + (0, 3, 4, 8), "operand not 16-byte aligned"),
+    ("mk_token_linear_x3_fwd", (_A, 8, _A, 8, 0, _A + 8, _A, 4) + (None, 0) * 3 + (0, 3, 4, 8), "bias not 16-byte aligned"),
+    ("mk_token_linear_x3_wgrad", (_A, 4, _A + 4, 8, _A, 8, None, None, 3, 4, 8, 1), "operand not 16-byte aligned"),
+    ("mk_token_linear_x3_wgrad", (_A, 4, _A, 8, _A, 8, _A + 8, _A, 3, 4, 8, 1), "db not 16-byte aligned"),
+    ("mk_token_linear_x3_wgrad", (_A, 4, _A, 8, _A, 8, _A, _A + 8, 3, 4, 8, 1), "workspace null or not 16-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import capi_checks as capi
+
 from makani_amd import ops, zenith
 from test_stepper_cpu import make_params
 
@@ -306,3 +308,18 @@ def test_the_op_has_no_cpu_fallback():
     z = torch.zeros(4)
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         ops.cos_zenith(z, torch.zeros(3), torch.ones(3), torch.zeros(5))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# misaligned pointers: refused by the host checks, with the message of the check (tests/capi_checks.py)
+# ---------------------------------------------------------------------------------------------------------------------
+_A = capi.A
+MISALIGNED = [      # entry point, its arguments in front of the stream with one pointer moved off its alignment, the refusal
+    ("mk_cos_zenith", (_A, _A, _A, _A, _A + 2, 1, 4, 8), "fp32 stream not 4-byte aligned"),
+    ("mk_cos_zenith", (_A + 2, _A, _A, _A, _A, 1, 4, 8), "fp32 stream not 4-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("case", MISALIGNED, ids=capi.case_ids(MISALIGNED))
+def test_misaligned_pointer_is_refused_before_any_launch(case):
+    capi.assert_refused(*case)
