@@ -657,6 +657,36 @@ int mk_field_stats(const float* x, const float* prev, const float* pivot, const 
 int mk_field_hist(const float* x, const double* edges, long long* counts, long long* outside, int nbins, int T, int C, int H,
                   int W, void* stream);
 
+/* ---- ensemble scores (csrc/ens.hip): CRPS, spread, ensemble-mean error and the rank histogram of an ensemble
+ * ens [B][E][C][H][W] (fp32: dtype 0, bf16: 1) against a target tar [B][C][H][W] fp32, in one pass.  A member's [C][H][W]
+ * block is contiguous; bstride and estride are the batch and member strides in ELEMENTS (a [B E][C][H][W] model output is
+ * read in place with bstride = E C H W, estride = C H W; larger strides leave gaps that are never read).  Per point, with
+ * the members x_e and the target y widened to fp64 and every value formed in fp64:
+ *   a = (1/E) sum_e |x_e - y|
+ *   g = (1/E^2) sum_e sum_f |x_e - x_f|, computed as (2/E^2) sum_k (2k - E - 1) x_(k) over the members sorted ascending
+ *   m = (1/E) sum_e x_e,  q = (m - y)^2,  v = (1/(E - 1)) sum_e (x_e - m)^2 (two-pass about m)
+ *   r = #{e : x_e < y}: a tie with the target counts as not less
+ *   sums [B][C][4] fp64 = sum_hw wrow[h] (a, g, q, v), wrow [H] fp32          written, not accumulated
+ *     CRPS = a - g / 2, fair CRPS = a - g E / (2 (E - 1)), spread^2 = v, squared error of the ensemble mean = q
+ *   ranks [C][E + 1] int64, ADDED TO, or NULL: the histogram of r over b, h, w
+ *   skipped [C] int64, added to, or NULL: the points whose target or one of whose members is NaN.  Such a point is not
+ *     ranked and makes all four sums of its (b, c) NaN (the sorting network alone would drop the NaN: it is looked for
+ *     before the sort).  Infinite inputs are out of contract
+ * E is 2 ... 64: a thread sorts the E fp32 members of its point (ordering fp32 values loses nothing) in P registers, P the
+ * power of two >= E, padded with +inf that the rank weights never touch.  Workgroup (slab of 8 rows, channel, sample)
+ * stages tiles of 256 (P = 64: 128) consecutive points through LDS, every member and the target from its OWN 16-byte
+ * boundary (scalar head, 16-byte body, scalar tail): any W, any element-aligned pointers and strides.  Sums are
+ * accumulated in fp64 per thread, folded in a fixed order and written to a workspace slot per workgroup; a finish adds
+ * the slabs in slab order: no floating-point atomics, the same bits every run.  Ranks and skipped go through LDS to
+ * device-scope 64-bit INTEGER atomics, which commute and do not round: the same counts every run and for every split
+ * of the rows.  Element offsets are 64-bit (B E C H W may pass 2^31); B, C <= 65535.  The file is compiled with fp
+ * contraction off.  Every refusal returns 1 before any launch.  Two launches, no allocation, synchronisation or host
+ * copy: `workspace` holds mk_ens_workspace(B, C, H) doubles. */
+long long mk_ens_workspace(int B, int C, int H);
+int mk_ens_sums(const void* ens, int dtype, long long bstride, long long estride, const float* tar, const float* wrow,
+                double* workspace, double* sums, long long* ranks, long long* skipped, int B, int E, int C, int H, int W,
+                void* stream);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

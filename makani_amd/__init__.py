@@ -16,6 +16,8 @@ Mirrors the reference's interfaces for the hot path only:
 * ``makani_amd.inference``            Rollout (the inferencer's autoregressive rollout on a one-pass HIP step tail)
 * ``makani_amd.stats``                DatasetStats (the statistics files of a dataset from one HIP pass per batch)
 * ``makani_amd.histograms``           DatasetHistograms (per-channel value histograms, equal to np.histogram's, on one HIP pass)
+* ``makani_amd.ensemble``             EnsembleScores (CRPS, spread, ensemble-mean RMSE and rank histogram per lead time, on one HIP pass;
+                                      ``inference.EnsembleRollout`` runs and scores the perturbed members)
 
 All arithmetic of the spectral path runs in libmakani_amd.so (include/makani_amd.h).
 """

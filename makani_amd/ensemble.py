@@ -1,0 +1,108 @@
+"""``EnsembleScores``: probabilistic scores of an ensemble forecast per lead time, the counterpart of ``MetricsHandler``
+(``metric.py``) for E perturbed members -- the runs the reference configures with ``n_initial_conditions``, ``noise_std`` and
+``perturb`` (``inferencer.py``) and scores only member by member.  Per autoregressive step and output channel it keeps
+
+* the CRPS of the ensemble's empirical distribution, ``A - G / 2`` with ``A = E|X - y|`` and ``G = E|X - X'|`` over the members,
+  and its fair (unbiased in E) form ``A - G E / (2 (E - 1))``;
+* the RMSE of the ensemble mean and the spread (root of the unbiased member variance), both as the mean over samples of the
+  root of the latitude-weighted integral, which is ``MetricsHandler``'s convention for the RMSE, and their ratio with the
+  finite-ensemble factor ``sqrt((E + 1) / E)`` (1 for a statistically consistent ensemble);
+* the rank histogram of the target among the members, as integer counts, and the number of points skipped for a NaN.
+
+Built from the same ``params`` as ``MetricsHandler`` (grid, crop, ``valid_autoreg_steps``, ``N_out_channels``) with the same
+normalised latitude weights, cut to this rank's shard.  ``update`` is one ``ops.ensemble_sums`` pass (``csrc/ens.hip`` on CUDA
+tensors with ``MK_ENSEMBLE=hip``) and an epilogue on ``[B, C]`` that stays on the device: no host synchronisation, capturable.
+Under spatial parallelism the ``[B, C, 4]`` float64 sums are all-reduced over ``"spatial"`` per update (the roots come after
+the reduction); the rank counts add up over shards and are reduced once, in ``finalize``.  All scores are linear in a
+channel's scale, so scoring runs on normalised fields and ``finalize(stds)`` scales the curves.
+"""
+import math
+
+import torch
+import torch.distributed as dist
+
+from . import comm, ops
+from .distributed import compute_split_shapes
+from .losses import GridQuadrature
+
+
+class EnsembleScores:
+    """Buffers and arithmetic of the ensemble scores (see the module docstring).  ``members``: E >= 1, fixed."""
+
+    def __init__(self, params, members, device):
+        self.device = torch.device(device)
+        self.members = int(members)
+        if self.members < 1:
+            raise ValueError(f"EnsembleScores: members must be at least 1, got {members}")
+        if getattr(params, "split_data_channels", False) and comm.get_size("matmul") > 1:
+            raise NotImplementedError("EnsembleScores: channel (matmul) parallelism is not supported")
+        self.steps = int(params.valid_autoreg_steps) + 1
+        self.N_out_channels = int(params.N_out_channels)
+        self.img_shape = (params.img_shape_x, params.img_shape_y)
+        self.crop_shape = (params.img_crop_shape_x, params.img_crop_shape_y)
+        self.crop_offset = (params.img_crop_offset_x, params.img_crop_offset_y)
+        rule = "legendre-gauss" if params.model_grid_type == "legendre_gauss" else "naive"
+        quad = GridQuadrature(rule, img_shape=self.img_shape, crop_shape=self.crop_shape, crop_offset=self.crop_offset, normalize=True)
+        wrow = quad.quad_weight[0, 0, :, 0]
+        self.spatial_size = comm.get_size("spatial")
+        if self.spatial_size > 1:
+            hs = compute_split_shapes(self.crop_shape[0], comm.get_size("h"))
+            h0 = sum(hs[:comm.get_rank("h")])
+            wrow = wrow[h0:h0 + hs[comm.get_rank("h")]]
+        self.wrow = wrow.float().contiguous().to(self.device)
+        C, E = self.N_out_channels, self.members
+        self.sums = torch.zeros(self.steps, C, 4, dtype=torch.float64, device=self.device)      # over samples: A, G, sqrt Q, sqrt V
+        self.counter = torch.zeros(self.steps, dtype=torch.float64, device=self.device)          # samples per lead time
+        self.rank_histogram = torch.zeros(self.steps, C, E + 1, dtype=torch.int64, device=self.device)
+        self.skipped = torch.zeros(self.steps, C, dtype=torch.int64, device=self.device)
+        self.last_sums = None
+
+    def zero_buffers(self):
+        """set buffers to zero"""
+        with torch.no_grad():
+            for t in (self.sums, self.counter, self.rank_histogram, self.skipped):
+                t.fill_(0)
+
+    def update(self, ens, tar, idt):
+        """accumulate one lead time: ``ens`` ``[B, E, C, H, W]`` or ``[B * E, C, H, W]`` (member fastest), ``tar``
+        ``[B, C, H, W]``, both this rank's shard; no host synchronisation"""
+        with torch.no_grad():
+            B = tar.shape[0]
+            if ens.numel() != self.members * tar.numel():
+                raise ValueError(f"EnsembleScores.update: ensemble {tuple(ens.shape)} is not {self.members} members of a target "
+                                 f"{tuple(tar.shape)}")
+            s = ops.ensemble_sums(ens, tar, self.wrow, self.rank_histogram[idt], self.skipped[idt])
+            if self.spatial_size > 1:
+                dist.all_reduce(s, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))
+            self.sums[idt, :, :2] += s[..., :2].sum(dim=0)
+            self.sums[idt, :, 2:] += torch.sqrt(s[..., 2:]).sum(dim=0)
+            self.counter[idt] += B
+            self.last_sums = s              # [B, C, 4] float64 of the whole field (ops.ENSEMBLE_SUMS), this update's
+
+    def finalize(self, stds=None):
+        """Reduce over the ranks and return the curves, ``[steps, C]`` float64 on the device, averaged over samples:
+        ``crps``, ``fair_crps``, ``ens_mean_rmse``, ``spread`` (times ``stds`` ``[C]`` where given), ``spread_skill``, and the
+        counts ``rank_histogram`` ``[steps, C, E + 1]`` and ``skipped`` ``[steps, C]`` (int64).  A lead time without an update
+        is NaN.  The accumulators are left as they are."""
+        E = self.members
+        with torch.no_grad():
+            sums, n = self.sums.clone(), self.counter.clone()
+            ranks, skipped = self.rank_histogram.clone(), self.skipped.clone()
+            if dist.is_initialized():
+                if self.spatial_size > 1:       # every spatial rank counted its own shard; the sums are whole already
+                    for t in (ranks, skipped):
+                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))
+                if comm.get_size("data") > 1:
+                    for t in (sums, n, ranks, skipped):
+                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=comm.get_group("data"))
+            mean = sums / n.reshape(-1, 1, 1)
+            A, G, rmse, spread = mean.unbind(dim=-1)
+            nan = torch.full_like(A, float("nan"))
+            out = {"crps": A - 0.5 * G, "fair_crps": A - G * (E / (2.0 * (E - 1))) if E > 1 else nan,
+                   "ens_mean_rmse": rmse, "spread": spread}
+            if stds is not None:
+                stds = torch.as_tensor(stds, dtype=torch.float64).reshape(1, -1).to(self.device)
+                out = {k: v * stds for k, v in out.items()}
+            out["spread_skill"] = math.sqrt((E + 1) / E) * out["spread"] / out["ens_mean_rmse"]
+            out["rank_histogram"], out["skipped"] = ranks, skipped
+        return out

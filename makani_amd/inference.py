@@ -25,6 +25,9 @@ Deviations from the reference (a fork with local edits), keeping the evident int
   the pass, and the result goes to pinned host memory with non-blocking copies and ONE synchronisation at the end of ``run``.
 * The ``Inferencer`` itself (a ``Trainer`` subclass with loaders, checkpoints and logging) is not part of this package:
   the caller brings the tensors.
+
+``EnsembleRollout`` runs E perturbed members per initial condition through the same step and scores them per lead time
+with ``ensemble.EnsembleScores`` (CRPS, spread, rank histogram); ``Rollout`` itself is unchanged by it.
 """
 import torch
 import torch.distributed as dist
@@ -177,6 +180,28 @@ class Rollout:
         g["graph"].replay()
         return g["out"]
 
+    def _emit_args(self, output_channels, output_stats, device):
+        """The pass's ``(emit_chans, emit_scale, emit_shift)`` for ``run``'s ``output_channels`` / ``output_stats``, or None."""
+        if output_channels is None:
+            if output_stats is not None:
+                raise ValueError("Rollout.run: output_stats without output_channels")
+            return None
+        chans = [int(c) for c in output_channels]
+        if not chans or min(chans) < 0 or max(chans) >= self.n_out:
+            raise ValueError(f"Rollout.run: output_channels {chans} out of range for {self.n_out} output channels")
+        means = stds = None
+        if output_stats is not None:
+            means, stds = (torch.as_tensor(t, dtype=torch.float32).reshape(-1).cpu() for t in output_stats)
+            if means.numel() != len(chans) or stds.numel() != len(chans):
+                raise ValueError(f"Rollout.run: output_stats have {means.numel()} means and {stds.numel()} stds for "
+                                 f"{len(chans)} output channels")
+        # uploaded once per (channels, statistics, device): a captured step keeps reading the same tensors
+        key = (tuple(chans), None if means is None else (tuple(means.tolist()), tuple(stds.tolist())), str(device))
+        if key not in self._emits:
+            self._emits[key] = (torch.tensor(chans, dtype=torch.int32, device=device),
+                                None if stds is None else stds.to(device), None if means is None else means.to(device))
+        return self._emits[key]
+
     # ---------------------------------------------------------------- the rollout
     def run(self, inp, tar=None, steps=None, inp_times=None, tar_times=None, output_channels=None, output_stats=None):
         """One rollout from the initial condition ``inp`` (``[B, T, C, H, W]`` or flattened ``[B, T * C, H, W]``).
@@ -209,25 +234,8 @@ class Rollout:
                 self._ensure_buffers(tar.shape[2], tar.shape[3], tar.shape[4], device)
             else:
                 nsteps = int(steps) if steps is not None else self.steps
-            emit = out = None
-            if output_channels is not None:
-                chans = [int(c) for c in output_channels]
-                if not chans or min(chans) < 0 or max(chans) >= self.n_out:
-                    raise ValueError(f"Rollout.run: output_channels {chans} out of range for {self.n_out} output channels")
-                means = stds = None
-                if output_stats is not None:
-                    means, stds = (torch.as_tensor(t, dtype=torch.float32).reshape(-1).cpu() for t in output_stats)
-                    if means.numel() != len(chans) or stds.numel() != len(chans):
-                        raise ValueError(f"Rollout.run: output_stats have {means.numel()} means and {stds.numel()} stds for "
-                                         f"{len(chans)} output channels")
-                # uploaded once per (channels, statistics, device): a captured step keeps reading the same tensors
-                key = (tuple(chans), None if means is None else (tuple(means.tolist()), tuple(stds.tolist())), str(device))
-                if key not in self._emits:
-                    self._emits[key] = (torch.tensor(chans, dtype=torch.int32, device=device),
-                                        None if stds is None else stds.to(device), None if means is None else means.to(device))
-                emit = self._emits[key]
-            elif output_stats is not None:
-                raise ValueError("Rollout.run: output_stats without output_channels")
+            out = None
+            emit = self._emit_args(output_channels, output_stats, device)
             n_global = float(self.global_shape[0] * self.global_shape[1])
             for idt in range(nsteps):
                 targ = tar[:, idt] if scored else None
@@ -281,3 +289,94 @@ class Rollout:
                 curve = curve * stds[None, :]
                 space = space * stds[:, None, None]
         return curve, space
+
+
+class EnsembleRollout(Rollout):
+    """An ensemble of ``members`` perturbed rollouts per initial condition, scored by an ``ensemble.EnsembleScores``.
+
+    ``run`` repeats each of the B initial conditions E = ``members`` times (member fastest, so the model runs at batch
+    B * E and sample b's members are rows b E ... b E + E - 1), adds ``noise_std * N(0, 1)`` (``torch.randn`` with ``run``'s
+    ``generator``; ``noise_std`` defaults to ``params.noise_std``, else 0) to the predicted channels of every history step of
+    members 1 ... E - 1 -- member 0 is the unperturbed control -- and steps with ``Rollout``'s own assemble, model and tail.
+    Per step the tail's prediction, viewed as ``[B, E, C, H, W]``, goes to ``scores.update(pred, tar[:, idt], idt)``: one
+    ``ops.ensemble_sums`` pass, no field is copied.  With ``capture=True`` the step graph is ``Rollout``'s and the scoring
+    launch follows the replay on the same stream.  ``Rollout``'s deterministic scores (``metrics``, ``loss``, the RMSE
+    accumulators) are not kept here: they are scores of ONE forecast.
+
+    The unpredicted channels: ``inp_times`` / ``tar_times`` are repeated per member before they are cached; fields that
+    the caller cached for B samples are replaced by their per-member repeats."""
+
+    def __init__(self, params, stepper, scores, members, noise_std=None, capture=False):
+        super().__init__(params, stepper, metrics=None, loss=None, capture=capture)
+        self.members = int(members)
+        if self.members < 1:
+            raise ValueError(f"EnsembleRollout: members must be at least 1, got {members}")
+        if scores is not None and scores.members != self.members:
+            raise ValueError(f"EnsembleRollout: {self.members} members, the scores were built for {scores.members}")
+        self.scores = scores
+        self.noise_std = float(getattr(params, "noise_std", 0.0) or 0.0) if noise_std is None else float(noise_std)
+
+    def _repeat_times(self, times):
+        if times is None:
+            return None
+        if torch.is_tensor(times):
+            return (times if times.dim() == 3 else times[None]).repeat_interleave(self.members, dim=0)
+        import numpy as np
+        return np.repeat(np.atleast_2d(np.asarray(times)), self.members, axis=0)
+
+    def perturb(self, inp, generator=None):
+        """``[B * E, T * C, H, W]``: each initial condition E times, noise on members 1 ... E - 1 (a new tensor)."""
+        inpt = self.preprocessor.flatten_history(inp)
+        B, E = inpt.shape[0], self.members
+        x = inpt.repeat_interleave(E, dim=0)
+        if E > 1 and self.noise_std != 0.0:
+            noise = torch.randn((B, E - 1) + tuple(inpt.shape[1:]), generator=generator, device=inpt.device, dtype=inpt.dtype)
+            x.view((B, E) + tuple(inpt.shape[1:]))[:, 1:] += self.noise_std * noise
+        return x
+
+    def run(self, inp, tar=None, steps=None, generator=None, inp_times=None, tar_times=None, output_channels=None,
+            output_stats=None):
+        """One ensemble rollout from ``inp`` (``[B, T, C, H, W]`` or flattened).  With ``tar`` ``[B, steps, C, H, W]`` every
+        step is scored (``scores`` must be given); without it the ensemble runs free for ``steps`` steps.
+        ``output_channels`` / ``output_stats`` as in ``Rollout.run``; the result is fp32 ``[steps, B, E, K, H, W]`` on the
+        host, or None."""
+        pp, E = self.preprocessor, self.members
+        with torch.no_grad():
+            x = self.perturb(inp, generator)
+            B, device = x.shape[0] // E, x.device
+            if inp_times is not None or tar_times is not None:
+                pp.cache_unpredicted_times(self._repeat_times(inp_times), self._repeat_times(tar_times), device=device)
+            mode = "train" if pp.training else "eval"
+            for name in ("unpredicted_inp_" + mode, "unpredicted_tar_" + mode):
+                z = getattr(pp, name)
+                if z is not None and E > 1 and z.shape[0] == B:
+                    setattr(pp, name, z.repeat_interleave(E, dim=0))
+            scored = tar is not None
+            if scored:
+                if self.scores is None:
+                    raise ValueError("EnsembleRollout.run: a target needs scores")
+                if tar.dim() != 5 or tar.shape[0] != B:
+                    raise ValueError(f"EnsembleRollout.run: target {tuple(tar.shape)} must be [B, steps, C, H, W] with B = {B}")
+                nsteps = tar.shape[1]
+                if nsteps > self.steps:
+                    raise ValueError(f"EnsembleRollout.run: {nsteps} target steps, valid_autoreg_steps + 1 = {self.steps}")
+            else:
+                nsteps = int(steps) if steps is not None else self.steps
+            emit = self._emit_args(output_channels, output_stats, device)
+            out = None
+            for idt in range(nsteps):
+                if self.capture and device.type == "cuda":
+                    pred, _, emitted = self._captured_step(x, None, emit)
+                else:
+                    pred, _, emitted = self._step(x, None, emit)
+                if scored:
+                    self.scores.update(pred.view((B, E) + tuple(pred.shape[1:])), tar[:, idt], idt)
+                if emitted is not None:
+                    if out is None:
+                        out = torch.empty((nsteps, B, E) + tuple(emitted.shape[1:]), dtype=torch.float32,
+                                          pin_memory=device.type == "cuda")
+                    out[idt].copy_(emitted.view((B, E) + tuple(emitted.shape[1:])), non_blocking=True)
+                x = pp.append_history(x, pred, idt)
+            if device.type == "cuda":
+                torch.cuda.current_stream(device).synchronize()         # once, for the host copies
+        return out

@@ -37,7 +37,7 @@ _HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
 # free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
 KNOBS = {
     **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
-                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ROWSUM"),
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ROWSUM"),
                     _HIP_TORCH),
     "MK_SPEC_DIAG": ("fused", "public"),
     "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
@@ -2518,6 +2518,104 @@ def field_hist(x, edges, counts, outside=None):
     _lib.check(_lib.load().mk_field_hist(x.data_ptr(), edges.data_ptr(), counts.data_ptr(), _ptr(outside), nbins, T, C, H, W,
                                          _stream()), "mk_field_hist")
     return counts
+
+
+# ----------------------------------------------------------------------------
+# ensemble scores (csrc/ens.hip)
+# ----------------------------------------------------------------------------
+ENSEMBLE_DEFAULT = "hip"        # MK_ENSEMBLE: hip | torch.  The rule of DESIGN section 19 on tools/ens_bench.py
+ENSEMBLE_MAX_MEMBERS = 64       # what mk_ens_sums takes: a thread sorts the members of its point in registers
+ENSEMBLE_SUMS = ("abs_err", "pair_dist", "mean_sq_err", "variance")     # order of the last axis of ensemble_sums: a, g, q, v
+_ENS_TORCH_CHUNK = 1 << 26      # ensemble elements per channel chunk of the torch formulation (its float64 temporaries)
+
+
+def _ensemble_sums_torch(ens, tar, wrow, ranks=None, skipped=None):
+    """``ensemble_sums`` as torch float64 ops on the tensors' device, by the same definition (``ens`` ``[B, E, C, H, W]``):
+    a sort over the member axis for ``g``, the two-pass variance, NaN points counted and made NaN by hand.  The channels
+    are walked in chunks so that a temporary holds at most ``_ENS_TORCH_CHUNK`` elements; no host synchronisation."""
+    B, E, C, H, W = ens.shape
+    dev = ens.device
+    w = wrow.double().reshape(1, 1, H, 1)
+    coef = (2.0 * torch.arange(1, E + 1, dtype=torch.float64, device=dev) - E - 1.0).reshape(1, E, 1, 1, 1)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    out = torch.empty(B, C, 4, dtype=torch.float64, device=dev)
+    step = max(1, _ENS_TORCH_CHUNK // max(1, B * E * H * W))
+    for c0 in range(0, C, step):
+        x, y = ens[:, :, c0:c0 + step].double(), tar[:, c0:c0 + step].double()
+        bad = torch.isnan(y) | torch.isnan(x).any(dim=1)
+        a = (x - y.unsqueeze(1)).abs().sum(dim=1) / E
+        g = (coef * torch.sort(x, dim=1).values).sum(dim=1) * (2.0 / (E * E))
+        m = x.sum(dim=1) / E
+        q = (m - y) ** 2
+        v = ((x - m.unsqueeze(1)) ** 2).sum(dim=1) / (E - 1) if E > 1 else torch.full_like(m, float("nan"))
+        for k, f in enumerate((a, g, q, v)):
+            out[:, c0:c0 + step, k] = (w * torch.where(bad, nan, f)).sum(dim=(-2, -1))
+        if ranks is not None:
+            cc = y.shape[1]
+            r = (x < y.unsqueeze(1)).sum(dim=1)                                  # [B, cc, H, W], 0 ... E
+            idx = torch.where(bad, E + 1, r) + (E + 2) * torch.arange(cc, device=dev).reshape(1, cc, 1, 1)
+            cnt = torch.zeros(cc * (E + 2), dtype=torch.int64, device=dev)
+            cnt.scatter_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.int64, device=dev))
+            ranks[c0:c0 + step] += cnt.view(cc, E + 2)[:, :E + 1]
+        if skipped is not None:
+            skipped[c0:c0 + step] += bad.sum(dim=(0, 2, 3))
+    return out
+
+
+@torch.no_grad()
+def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
+    """Latitude-weighted integrals of the ensemble scores, ``[B, C, 4]`` float64 in the order of ``ENSEMBLE_SUMS``, of an
+    ensemble ``ens`` ``[B, E, C, H, W]`` (a ``[B * E, C, H, W]`` model output is viewed, member fastest) against a target
+    ``tar`` ``[B, C, H, W]``.  Per point, members ``x_e`` and target ``y`` widened to float64:
+
+    * ``a = mean_e |x_e - y|``, ``g = mean_ef |x_e - x_f|`` (over all E^2 pairs; computed from the sorted members),
+    * ``m = mean_e x_e``, ``q = (m - y)^2``, ``v = sum_e (x_e - m)^2 / (E - 1)`` (NaN for ``E = 1``),
+
+    each summed over the field with ``w = wrow[h]``.  CRPS is ``a - g / 2``, the fair CRPS ``a - g E / (2 (E - 1))``.
+
+    * ``ranks`` ``[C, E + 1]`` int64 (contiguous) or None, added to: the histogram of ``r = #{e : x_e < y}`` (a member
+      equal to the target is not below it);
+    * ``skipped`` ``[C]`` int64 (contiguous) or None, added to: the points whose target or one of whose members is NaN.
+      Such a point is not ranked and makes the four sums of its ``(b, c)`` NaN.  Infinite values are out of contract.
+
+    ``MK_ENSEMBLE=hip`` (read on every call): CUDA tensors with 2 to ``ENSEMBLE_MAX_MEMBERS`` members take one HIP pass
+    (``mk_ens_sums``: fp32 or bf16 members read in place through their batch and member strides, no floating-point atomics,
+    the same bits every run, capturable).  CPU tensors, ``E = 1``, more members and ``MK_ENSEMBLE=torch`` take
+    ``_ensemble_sums_torch``.  No gradient flows through this op."""
+    hip = _hip_or_torch("MK_ENSEMBLE", ENSEMBLE_DEFAULT)
+    if tar.dim() != 4:
+        raise ValueError(f"ensemble_sums: the target must be [B, C, H, W], got {tuple(tar.shape)}")
+    B, C, H, W = tar.shape
+    if ens.dim() == 4 and B >= 1 and ens.shape[0] % B == 0 and tuple(ens.shape[1:]) == (C, H, W):
+        ens = ens.view(B, ens.shape[0] // B, C, H, W) if ens.is_contiguous() else ens.reshape(B, ens.shape[0] // B, C, H, W)
+    if ens.dim() != 5 or ens.shape[0] != B or tuple(ens.shape[2:]) != (C, H, W) or ens.shape[1] < 1 or min(B, C, H, W) < 1:
+        raise ValueError(f"ensemble_sums: ensemble {tuple(ens.shape)} must be [B, E, C, H, W] or [B * E, C, H, W] for a target "
+                         f"{tuple(tar.shape)}")
+    E = ens.shape[1]
+    dev = ens.device
+    if tar.device != dev or wrow.device != dev:
+        raise ValueError(f"ensemble_sums: ensemble on {dev}, target on {tar.device}, wrow on {wrow.device}")
+    if wrow.numel() != H:
+        raise ValueError(f"ensemble_sums: wrow has {wrow.numel()} weights for {H} latitude rows")
+    for name, t, shape in (("ranks", ranks, (C, E + 1)), ("skipped", skipped, (C,))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"ensemble_sums: {name} must be a contiguous int64 {list(shape)} on {dev}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    ens, tar = ens.detach(), tar.detach()
+    if not (hip and ens.is_cuda and 2 <= E <= ENSEMBLE_MAX_MEMBERS):
+        return _ensemble_sums_torch(ens, tar, wrow, ranks, skipped)
+    ens = _lowp(ens)
+    if ens.stride()[2:] != (H * W, W, 1) or min(ens.stride(0), ens.stride(1)) < C * H * W:
+        ens = ens.contiguous()             # every member's [C, H, W] block contiguous; the batch and member strides are free
+    tar = tar.float().contiguous()
+    wrow = wrow.float().contiguous()
+    lib = _lib.load()
+    ws = torch.empty(lib.mk_ens_workspace(B, C, H), dtype=torch.float64, device=dev)
+    out = torch.empty(B, C, 4, dtype=torch.float64, device=dev)
+    bstride = ens.stride(0) if B > 1 else E * ens.stride(1)      # a stride of a size-1 axis means nothing
+    _lib.check(lib.mk_ens_sums(ens.data_ptr(), _pw_dtype(ens), bstride, ens.stride(1), tar.data_ptr(), wrow.data_ptr(),
+                               ws.data_ptr(), out.data_ptr(), _ptr(ranks), _ptr(skipped), B, E, C, H, W, _stream()), "mk_ens_sums")
+    return out
 
 
 # ----------------------------------------------------------------------------
