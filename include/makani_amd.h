@@ -687,6 +687,26 @@ int mk_ens_sums(const void* ens, int dtype, long long bstride, long long estride
                 double* workspace, double* sums, long long* ranks, long long* skipped, int B, int E, int C, int H, int W,
                 void* stream);
 
+/* The gradient of the first two sums, S [B][C][2] = sum_hw wrow[h] (a, g), with respect to the members: the backward of the
+ * ensemble CRPS loss a - (kappa / 2) g (kappa = 1: CRPS, kappa = E / (E - 1): fair CRPS).  With the upstream gradient
+ * gs [B][C][2] fp64, L_e = #{f : x_f < x_e} and G_e = #{f : x_f > x_e},
+ *   gens[b][e][c][h][w] = wrow[h] (gs[b][c][0] sgn(x_e - y) / E + gs[b][c][1] 2 (L_e - G_e) / E^2),   sgn(0) = 0
+ * which is what autograd gives for the all-pairs expression (abs'(0) = 0): tied members get the same value and the member
+ * order does not matter (the gradient through a sort hands tied members different values).  If the target or any member
+ * of a point is NaN, the gradient of EVERY member of that point is NaN.  No gradient goes to the target.
+ * The comparisons are fp32 (exact: members are fp32, or bf16 widened), the counts integers; wrow, gs[.][.][0] / E and
+ * 2 gs[.][.][1] / E^2 are fp64, the value is formed in fp64 and rounded ONCE to the gradient's dtype, which is the
+ * members' (a bf16 value is not rounded through fp32).  E is 2 ... 16: a thread holds the members of its point in
+ * registers and compares all pairs.  ens, bstride, estride, tar, wrow as for mk_ens_sums; gens has batch and member strides
+ * gbstride, gestride of its own (elements, a member's [C][H][W] block contiguous) and only the points are written: gaps
+ * between the blocks keep what they hold.  Same decomposition and staging as mk_ens_sums; a tile leaves LDS through the
+ * mirror image of the staging: per member a scalar head up to that member's own 16-byte boundary, 16-byte stores, a scalar
+ * tail.  One launch, no atomics, no workspace, the same bits every run; 64-bit element offsets; B, C <= 65535; fp
+ * contraction off.  Every refusal (what mk_ens_sums refuses, for both sides, and E above 16) returns 1 before any launch. */
+int mk_ens_crps_bwd(const void* ens, int dtype, long long bstride, long long estride, const float* tar, const float* wrow,
+                    const double* gs, void* gens, long long gbstride, long long gestride, int B, int E, int C, int H, int W,
+                    void* stream);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

@@ -28,6 +28,13 @@
 // an odd number of words apart) and from there to `ranks` with device-scope 64-bit INTEGER atomics, which commute and do
 // not round: the counts are the same every run and for every split of the rows (as hist.hip).  Capturable: two launches, no
 // allocation, synchronisation or host copy.
+//
+// The training loss a - (kappa / 2) g needs the gradient of (sum w a, sum w g) with respect to the members: mk_ens_crps_bwd,
+// one launch of the same decomposition and staging.  Per point d|x_e - y|/dx_e = sgn(x_e - y) and
+// d sum_ef |x_e - x_f| / dx_e = 2 (L_e - G_e), L_e and G_e the members below and above x_e, counted by comparing ALL PAIRS in
+// registers (E <= 16): exact, symmetric among tied members, independent of the member order -- the sorted form of g is not
+// differentiated, it hands tied members different values.  The value is formed in fp64, rounded once, put into the thread's
+// column of the tile in place of the member, and the tile leaves through `unstage`, the mirror image of `stage`.
 #include "common.h"
 #include "stream_io.h"
 #include "../../include/makani_amd.h"
@@ -253,6 +260,125 @@ void launch_e(const T* ens, const float* tar, const float* wrow, double* part, l
 #undef MK_ENS_CASE
 }
 
+// ---- the gradient of (sum_hw w a, sum_hw w g) with respect to the members (mk_ens_crps_bwd; the header has the definition)
+constexpr int kMaxLossE = 16;      // all pairs in registers: at most 256 comparisons per point
+
+// The mirror image of `stage`: n points of `nstreams` rows of src [nstreams][TP] fp32 -> stream s at dst + s * dstride, each
+// stream from ITS OWN 16-byte boundary: a scalar head, 16-byte stores, a scalar tail.  Nothing outside the n points is written.
+template <typename S, int TP>
+__device__ __forceinline__ void unstage(const float* __restrict__ src, S* __restrict__ dst, long long dstride, int nstreams, int n,
+                                        int tid) {
+    constexpr int VPS = TP / kV;
+    constexpr int NS = 2 * (kV - 1);
+    for (int i = tid; i < nstreams * VPS; i += TP) {
+        const int s = i / VPS, j = i - s * VPS;
+        S* p = dst + s * dstride;
+        const int head = head_points(p, n);
+        if (j < (n - head) / kV) {
+            float v[kV];
+            const float* d = src + s * TP + head + j * kV;
+#pragma unroll
+            for (int k = 0; k < kV; ++k) v[k] = d[k];
+            IO<S>::store(p + head + j * kV, v);
+        }
+    }
+    for (int i = tid; i < nstreams * NS; i += TP) {
+        const int s = i / NS, q = i - s * NS;
+        S* p = dst + s * dstride;
+        const int head = head_points(p, n);
+        const int tail0 = head + (n - head) / kV * kV;
+        const int idx = q < kV - 1 ? q : tail0 + (q - (kV - 1));
+        if (q < kV - 1 ? q < head : idx < n) IO<S>::st1(p + idx, src[s * TP + idx]);
+    }
+}
+
+// v rounded ONCE to T, as the fp32 value the tile holds (the store's conversion of it is exact)
+template <typename T> __device__ __forceinline__ float round_once(double v);
+template <> __device__ __forceinline__ float round_once<float>(double v) { return (float)v; }
+template <> __device__ __forceinline__ float round_once<__hip_bfloat16>(double v) {
+    // double -> fp32 -> bf16 rounds twice, and differs from one rounding only where the fp32 value sits exactly half way
+    // between two bf16 values although v does not: there the fp32 value is moved one step towards v first
+    const float f = (float)v;
+    unsigned int u = __float_as_uint(f);
+    if ((u & 0xffffu) == 0x8000u && (double)f != v) u = fabs(v) > fabs((double)f) ? u + 1u : u - 1u;
+    return __bfloat162float(__float2bfloat16(__uint_as_float(u)));
+}
+
+struct GradScales {
+    double inv_e, g;               // 1 / E, 2 / E^2
+};
+
+// workgroup (slab, c, b) as in ens_sums_kernel; thread t of a tile forms the E gradients of its point and leaves them in its
+// column of the tile, which then goes out through `unstage`
+template <typename T, int P, int TP>
+__global__ __launch_bounds__(TP) void ens_crps_bwd_kernel(const T* __restrict__ ens, const float* __restrict__ tar,
+                                                          const float* __restrict__ wrow, const double* __restrict__ gs,
+                                                          T* __restrict__ gens, long long bstride, long long estride,
+                                                          long long gbstride, long long gestride, GradScales sc, int E, int C,
+                                                          int H, int W) {
+    extern __shared__ float lds[];                           // tile [E + 1][TP]
+    float* tile = lds;
+    const int s = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int h0 = s * kRows;
+    const int npts = (min(H, h0 + kRows) - h0) * W;
+    const long long HW = (long long)H * W;
+    const long long off = c * HW + (long long)h0 * W;
+    const T* eb = ens + b * bstride + off;
+    T* gb = gens + b * gbstride + off;
+    const float* tb = tar + ((long long)b * C + c) * HW + (long long)h0 * W;
+    const double k0 = gs[((long long)b * C + c) * 2] * sc.inv_e;          // gS0 / E
+    const double k1 = gs[((long long)b * C + c) * 2 + 1] * sc.g;          // 2 gS1 / E^2
+    for (int p0 = 0; p0 < npts; p0 += TP) {
+        const int n = min(TP, npts - p0);
+        __syncthreads();                                     // the tile before has left
+        stage<T, TP>(eb + p0, estride, E, tile, n, tid);
+        stage<float, TP>(tb + p0, 0, 1, tile + E * TP, n, tid);
+        __syncthreads();
+        if (tid < n) {
+            const float yf = tile[E * TP + tid];
+            float* col = tile + tid;
+            // a pad is NaN: it compares false both ways and counts for nobody
+            float x[P];
+#pragma unroll
+            for (int e = 0; e < P; ++e) x[e] = e < E ? col[(e < E ? e : 0) * TP] : NAN;
+            bool bad = yf != yf;
+#pragma unroll
+            for (int e = 0; e < P; ++e) bad = bad || (e < E && x[e] != x[e]);
+            const double w = (double)wrow[h0 + (p0 + tid) / W];
+#pragma unroll
+            for (int e = 0; e < P; ++e) {
+                int d = 0;                                   // L_e - G_e, exact
+#pragma unroll
+                for (int f = 0; f < P; ++f)
+                    if (f != e) d += (x[f] < x[e] ? 1 : 0) - (x[f] > x[e] ? 1 : 0);
+                const int sg = (x[e] > yf ? 1 : 0) - (x[e] < yf ? 1 : 0);
+                const double v = w * (k0 * (double)sg + k1 * (double)d);
+                if (e < E) col[e * TP] = round_once<T>(bad ? (double)NAN : v);
+            }
+        }
+        __syncthreads();
+        unstage<T, TP>(tile, gb + p0, gestride, E, n, tid);
+    }
+}
+
+template <typename T>
+void launch_bwd(const T* ens, const float* tar, const float* wrow, const double* gs, T* gens, long long bstride, long long estride,
+                long long gbstride, long long gestride, int B, int E, int C, int H, int W, hipStream_t st) {
+    constexpr int TP = 256;
+    const GradScales sc = {1.0 / E, 2.0 / ((double)E * E)};
+    const dim3 grid((unsigned)mk::ceil_div(H, kRows), (unsigned)C, (unsigned)B);
+    const size_t lds = (size_t)(E + 1) * TP * 4;
+#define MK_ENS_CASE(P)                                                                                                          \
+    hipLaunchKernelGGL((ens_crps_bwd_kernel<T, P, TP>), grid, dim3(TP), lds, st, ens, tar, wrow, gs, gens, bstride, estride, \
+                       gbstride, gestride, sc, E, C, H, W)
+    if (E <= 2) MK_ENS_CASE(2);
+    else if (E <= 4) MK_ENS_CASE(4);
+    else if (E <= 8) MK_ENS_CASE(8);
+    else MK_ENS_CASE(16);
+#undef MK_ENS_CASE
+}
+
 }  // namespace
 
 extern "C" long long mk_ens_workspace(int B, int C, int H) {
@@ -288,6 +414,38 @@ extern "C" int mk_ens_sums(const void* ens, int dtype, long long bstride, long l
     const long long n = (long long)B * C * kK;
     hipLaunchKernelGGL(slab_finalize_kernel<256>, dim3((unsigned)mk::ceil_div_ll(n, 256 / 64)), dim3(256), 0, st, workspace, sums,
                        mk::ceil_div(H, kRows), n);
+    MK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mk_ens_crps_bwd(const void* ens, int dtype, long long bstride, long long estride, const float* tar, const float* wrow,
+                               const double* gs, void* gens, long long gbstride, long long gestride, int B, int E, int C, int H,
+                               int W, void* stream) {
+    MK_REQUIRE(ens && tar && wrow && gs && gens, "null pointer");
+    MK_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16)");
+    MK_REQUIRE(B >= 1 && C >= 1 && H >= 1 && W >= 1, "bad sizes");
+    MK_REQUIRE(E >= 2 && E <= kMaxLossE, "E outside 2 ... 16 (all pairs of a point are compared in registers)");
+    MK_REQUIRE(B <= 65535 && C <= 65535, "B or C beyond the grid range");
+    MK_REQUIRE((long long)kRows * W <= 0x7fffffffLL, "a workgroup's points (8 rows of W) beyond the 32-bit range");
+    const long long chw = (long long)C * H * W;
+    MK_REQUIRE(chw < (1LL << 40), "field too large");
+    MK_REQUIRE(estride >= chw && bstride >= chw && gestride >= chw && gbstride >= chw,
+               "a member's [C][H][W] block must be contiguous: strides below C * H * W");
+    MK_REQUIRE(estride < (1LL << 44) && bstride < (1LL << 44) && gestride < (1LL << 44) && gbstride < (1LL << 44), "stride too large");
+    MK_REQUIRE(bstride >= (long long)E * estride || estride >= (long long)B * bstride || B == 1,
+               "members of different samples overlap: need bstride >= E * estride or estride >= B * bstride");
+    MK_REQUIRE(gbstride >= (long long)E * gestride || gestride >= (long long)B * gbstride || B == 1,
+               "gradients of different samples overlap: need gbstride >= E * gestride or gestride >= B * gbstride");
+    MK_REQUIRE(mk::aligned_to(ens, dtype == 0 ? 4 : 2) && mk::aligned_to(gens, dtype == 0 ? 4 : 2),
+               "ensemble or its gradient not aligned to its element");
+    MK_REQUIRE(mk::aligned<4>(tar, wrow), "fp32 stream not 4-byte aligned");
+    MK_REQUIRE(mk::aligned<8>(gs), "64-bit buffer not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 0)
+        launch_bwd<float>((const float*)ens, tar, wrow, gs, (float*)gens, bstride, estride, gbstride, gestride, B, E, C, H, W, st);
+    else
+        launch_bwd<__hip_bfloat16>((const __hip_bfloat16*)ens, tar, wrow, gs, (__hip_bfloat16*)gens, bstride, estride, gbstride,
+                                   gestride, B, E, C, H, W, st);
     MK_LAUNCH_CHECK();
     return 0;
 }

@@ -15,11 +15,16 @@ tensors with ``MK_ENSEMBLE=hip``) and an epilogue on ``[B, C]`` that stays on th
 Under spatial parallelism the ``[B, C, 4]`` float64 sums are all-reduced over ``"spatial"`` per update (the roots come after
 the reduction); the rank counts add up over shards and are reduced once, in ``finalize``.  All scores are linear in a
 channel's scale, so scoring runs on normalised fields and ``finalize(stds)`` scales the curves.
+
+``EnsembleCRPSLoss`` is the same score as a training loss (``ops.ensemble_crps_sums``: the forward pass above, and one HIP pass
+for the gradient with respect to the members), selected by the ``crps`` strings of ``losses.LossHandler``; ``perturb_members``
+makes the E members of a training step the way ``EnsembleRollout`` makes those of a rollout.
 """
 import math
 
 import torch
 import torch.distributed as dist
+from torch import nn
 
 from . import comm, ops
 from .distributed import compute_split_shapes
@@ -106,3 +111,63 @@ class EnsembleScores:
             out["spread_skill"] = math.sqrt((E + 1) / E) * out["spread"] / out["ens_mean_rmse"]
             out["rank_histogram"], out["skipped"] = ranks, skipped
         return out
+
+
+def perturb_members(x, members, noise_std, generator=None):
+    """``[B * E, ...]`` from ``x`` ``[B, ...]``: each sample E = ``members`` times (member fastest), ``noise_std * N(0, 1)``
+    (``torch.randn`` with ``generator``) added to members 1 ... E - 1; member 0 is the unperturbed control.  A new tensor.  A
+    training step of an ensemble is ``perturb_members`` -> the stepper at batch ``B * E`` -> ``LossHandler`` with a ``crps`` loss."""
+    B, E = x.shape[0], int(members)
+    out = x.repeat_interleave(E, dim=0)
+    if E > 1 and noise_std != 0.0:
+        noise = torch.randn((B, E - 1) + tuple(x.shape[1:]), generator=generator, device=x.device, dtype=x.dtype)
+        out.view((B, E) + tuple(x.shape[1:]))[:, 1:] += noise_std * noise
+    return out
+
+
+class EnsembleCRPSLoss(nn.Module):
+    """The CRPS of the members' empirical distribution as a training loss: per point ``a - (kappa / 2) g`` with
+    ``a = mean_e |x_e - y|``, ``g = mean_ef |x_e - x_f|`` and ``kappa = 1 + alpha / (E - 1)`` -- ``alpha = 0`` the CRPS, ``alpha = 1``
+    the fair CRPS (unbiased in E), in between the almost-fair CRPS -- integrated with the latitude weights ``GeometricLpLoss``
+    uses (normalised, ``pole_mask`` rows zero) and reduced as its absolute, not squared ``p = 1`` form: ``forward(prd, tar, chw)``
+    is ``sum_bc chw_c (S0 - kappa / 2 S1)`` in fp32, so E equal members give the ``absolute geometric l1`` loss of the same fields.
+
+    ``prd`` is ``[B * E, C, H, W]`` (member fastest) or ``[B, E, C, H, W]``, ``tar`` ``[B, C, H, W]``.  The two integrals come from
+    ``ops.ensemble_crps_sums`` (``MK_ENS_LOSS=hip``: one HIP pass each way); they add up over spatial shards (``sums`` with
+    ``rows``), so a sharded caller all-reduces ``[B, C, 2]`` and calls ``from_sums``.  ``last_sums`` is the detached ``[B, C, 4]``
+    (``ops.ENSEMBLE_SUMS``) of the latest call over the rows it was given: spread and ensemble-mean error for a log."""
+
+    def __init__(self, img_shape, crop_shape, crop_offset, members, alpha=0.0, pole_mask=0, quadrature_rule="naive"):
+        super().__init__()
+        self.members, self.alpha = int(members), float(alpha)
+        if self.members < 1:
+            raise ValueError(f"EnsembleCRPSLoss: members must be at least 1, got {members}")
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"EnsembleCRPSLoss: alpha must lie in [0, 1], got {alpha}")
+        if self.members == 1 and self.alpha != 0.0:
+            raise ValueError("EnsembleCRPSLoss: the fair forms need at least 2 members")
+        self.kappa = 1.0 + (self.alpha / (self.members - 1) if self.members > 1 else 0.0)
+        self.quadrature = GridQuadrature(quadrature_rule, img_shape=img_shape, crop_shape=crop_shape, crop_offset=crop_offset,
+                                         normalize=True, pole_mask=pole_mask)
+        wrow = self.quadrature.quad_weight[0, 0, :, 0].contiguous()
+        self.register_buffer("wrow", wrow, persistent=False)
+        self.register_buffer("wrow32", wrow.float(), persistent=False)
+        self.last_sums = None
+
+    def sums(self, prd, tar, rows=None):
+        """``[B, C, 2]`` float64 integrals of ``a`` and ``g`` over the fields' latitude rows ``rows`` (a slice of the cropped
+        grid's rows; all of them by default) -- they add up over spatial shards."""
+        if prd.numel() != self.members * tar.numel():
+            raise ValueError(f"EnsembleCRPSLoss: prediction {tuple(prd.shape)} is not {self.members} members of a target "
+                             f"{tuple(tar.shape)}")
+        wrow = self.wrow32 if prd.is_cuda else self.wrow
+        s, self.last_sums = ops.ensemble_crps_sums(prd, tar, wrow if rows is None else wrow[rows], with_sums=True)
+        return s
+
+    def from_sums(self, sums, chw):
+        """The loss (fp32) from the integrals of the whole field."""
+        s0, s1 = sums.unbind(-1)
+        return torch.sum(chw * (s0 - (0.5 * self.kappa) * s1)).float()
+
+    def forward(self, prd, tar, chw):
+        return self.from_sums(self.sums(prd, tar), chw)

@@ -35,6 +35,7 @@ import torch.distributed as dist
 from . import comm, ops
 from .mappings import gather_from_parallel_region
 from .distributed import compute_split_shapes
+from .ensemble import perturb_members
 from .stepper import _engine_input_dtype
 
 
@@ -326,13 +327,7 @@ class EnsembleRollout(Rollout):
 
     def perturb(self, inp, generator=None):
         """``[B * E, T * C, H, W]``: each initial condition E times, noise on members 1 ... E - 1 (a new tensor)."""
-        inpt = self.preprocessor.flatten_history(inp)
-        B, E = inpt.shape[0], self.members
-        x = inpt.repeat_interleave(E, dim=0)
-        if E > 1 and self.noise_std != 0.0:
-            noise = torch.randn((B, E - 1) + tuple(inpt.shape[1:]), generator=generator, device=inpt.device, dtype=inpt.dtype)
-            x.view((B, E) + tuple(inpt.shape[1:]))[:, 1:] += self.noise_std * noise
-        return x
+        return perturb_members(self.preprocessor.flatten_history(inp), self.members, self.noise_std, generator)
 
     def run(self, inp, tar=None, steps=None, generator=None, inp_times=None, tar_times=None, output_channels=None,
             output_stats=None):

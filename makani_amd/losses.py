@@ -253,7 +253,12 @@ class LossHandler(nn.Module):
     """losses.py:33-172 for the Lp family: parses ``params.loss`` ("l2", "geometric l2", "absolute squared geometric l2",
     "weighted ...", "pole-masked ...", "l1" ...), builds channel / multistep weights and calls the loss object.  Under
     spatial parallelism both families all-reduce their per-shard sums (CPU tensors of the H1 loss are gathered).  ``params`` is
-    the trainer's parameter object (attribute access)."""
+    the trainer's parameter object (attribute access).
+
+    A loss string with the word ``crps`` ("ensemble crps", "fair ensemble crps", "almost-fair ensemble crps"; not in the
+    reference) selects ``ensemble.EnsembleCRPSLoss`` with ``params.ensemble_size`` members: ``prd`` is then ``[B * E, C', H, W]``
+    (member fastest) for a ``tar`` ``[B, C', H, W]``.  "fair" is ``alpha = 1``, "almost-fair" ``alpha = params.crps_alpha`` (0.95);
+    "weighted", "temp-std" and "pole-masked" act as for "l1"; "squared" is an error.  Sharded, the ``[B, C', 2]`` sums are all-reduced."""
 
     def __init__(self, params):
         super().__init__()
@@ -288,7 +293,18 @@ class LossHandler(nn.Module):
         self.register_buffer("channel_weights", channel_weights)
         rule = "legendre-gauss" if params.model_grid_type == "legendre_gauss" else "naive"
         common = dict(absolute=absolute, pole_mask=pole_mask)
-        if "l2" in loss_type:
+        if "crps" in loss_type:
+            # the one loss with E predictions per target: prd [B * E, C', H, W] (member fastest) against tar [B, C', H, W]
+            from .ensemble import EnsembleCRPSLoss          # ensemble.py imports this module
+            if squared:
+                raise ValueError(f"Unknown loss function: {self.loss_type} (the CRPS has no squared form)")
+            members = getattr(params, "ensemble_size", None)
+            if members is None:
+                raise ValueError(f"loss {self.loss_type!r} needs params.ensemble_size, the number of members per target")
+            alpha = float(getattr(params, "crps_alpha", 0.95)) if "almost-fair" in loss_type else 1.0 if "fair" in loss_type else 0.0
+            self.loss_obj = EnsembleCRPSLoss(self.img_shape, self.crop_shape, self.crop_offset, members, alpha=alpha,
+                                             pole_mask=pole_mask, quadrature_rule=rule)
+        elif "l2" in loss_type:
             if "geometric" in loss_type:
                 self.loss_obj = GeometricLpLoss(self.img_shape, self.crop_shape, self.crop_offset, p=2, squared=squared,
                                                 quadrature_rule=rule, **common)
@@ -330,6 +346,11 @@ class LossHandler(nn.Module):
     def forward(self, prd, tar, inp=None):
         chw = self.channel_weights
         chw = (chw * self.multistep_weight).reshape(1, -1) if self.training else chw.reshape(1, -1)
+        if "crps" in self.loss_type.split():
+            if not self.do_gather_input:
+                return self.loss_obj(prd, tar, chw)
+            sums = self.loss_obj.sums(prd, tar, self.shard_rows)      # this rank's rows; [B, C', 2] add up, no field is gathered
+            return self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
         if self.do_gather_input:
             if isinstance(self.loss_obj, GeometricLpLoss) and self.loss_obj.has_sums(prd, tar):
                 sums = self.loss_obj.sums(prd, tar, self.shard_rows)

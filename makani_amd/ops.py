@@ -37,7 +37,7 @@ _HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
 # free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
 KNOBS = {
     **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
-                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ROWSUM"),
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_ROWSUM"),
                     _HIP_TORCH),
     "MK_SPEC_DIAG": ("fused", "public"),
     "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
@@ -2616,6 +2616,134 @@ def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
     _lib.check(lib.mk_ens_sums(ens.data_ptr(), _pw_dtype(ens), bstride, ens.stride(1), tar.data_ptr(), wrow.data_ptr(),
                                ws.data_ptr(), out.data_ptr(), _ptr(ranks), _ptr(skipped), B, E, C, H, W, _stream()), "mk_ens_sums")
     return out
+
+
+# ----------------------------------------------------------------------------
+# the ensemble CRPS as a training loss (csrc/ens.hip: mk_ens_sums forward, mk_ens_crps_bwd backward)
+# ----------------------------------------------------------------------------
+ENS_LOSS_DEFAULT = "hip"        # MK_ENS_LOSS: hip | torch.  No row of tools/ens_loss_bench.py is slower than torch
+ENS_LOSS_MAX_MEMBERS = 16       # what mk_ens_crps_bwd takes: a thread compares all pairs of its point's members in registers
+
+
+def _ens_crps_chunk(x, y, w):
+    """``[B, c, 4]`` float64 of a channel chunk, ``x`` ``[B, E, c, H, W]``: a and g from ALL PAIRS, differentiable; q and v
+    detached, NaN where the point is.
+
+    ``sum_ef |x_e - x_f|`` is written as ``2 sum_e (x_e - y) r_e`` with ``r_e = sum_f sgn(x_e - x_f) = L_e - G_e`` summed as integers
+    and detached (``sum_e r_e = 0``, so the target drops out; it only keeps the terms small).  The value and the gradient are those
+    of ``abs`` under autograd, ``abs'(0) = 0`` included, but the backward multiplies the upstream gradient u by ``r_e`` ONCE: it is
+    exactly zero where ``L_e = G_e``.  The backward of the plain ``abs`` adds E terms ``+-u`` per member, and those sums round
+    (3 u is not a float64 number), which leaves 1e-17 where the definition has zero from E = 5 on."""
+    E = x.shape[1]
+    x, y = x.double(), y.double()
+    d = x - y.unsqueeze(1)
+    a = d.abs().sum(dim=1) / E
+    with torch.no_grad():
+        r = torch.sign(x.unsqueeze(1) - x.unsqueeze(2)).sum(dim=1)          # [b, f, e] = x_e - x_f, summed over f
+    g = ((x - y.detach().unsqueeze(1)) * r).sum(dim=1) * (2.0 / (E * E))
+    with torch.no_grad():
+        m = x.sum(dim=1) / E
+        q = (m - y) ** 2
+        v = ((x - m.unsqueeze(1)) ** 2).sum(dim=1) / (E - 1) if E > 1 else torch.full_like(m, float("nan"))
+        # 1 at a good point, NaN where the target or a member is NaN.  As a factor it makes all four values of such a point NaN
+        # and, in the backward, the gradient of EVERY member of the point (torch's abs' is sgn, and sgn(NaN) is 0: without the
+        # factor a NaN point would hand its members zeros and finite values)
+        mark = 1.0 + 0.0 * (y + x.sum(dim=1))
+        q, v = q * mark, v * mark
+    a, g = a * mark, g * mark
+    return torch.stack([(w * f).sum(dim=(-2, -1)) for f in (a, g, q, v)], dim=-1)
+
+
+def _ensemble_crps_sums_torch(ens, tar, wrow):
+    """``[B, C, 4]`` float64 in the order of ``ENSEMBLE_SUMS`` on the tensors' device (``ens`` ``[B, E, C, H, W]``); the first two,
+    ``a`` and ``g``, are the all-pairs expression under ordinary autograd (``abs'(0) = 0``: tied members get equal gradients; see
+    ``_ens_crps_chunk`` for how the pairs are written), the other two are detached.  The channels are walked in chunks so that an ``E^2`` temporary holds at most ``_ENS_TORCH_CHUNK``
+    elements; under autograd a chunk is recomputed in the backward instead of kept (``torch.utils.checkpoint``)."""
+    B, E, C, H, W = ens.shape
+    w = wrow.detach().double().reshape(1, 1, H, 1)
+    step = max(1, _ENS_TORCH_CHUNK // max(1, B * E * E * H * W))
+    keep = torch.is_grad_enabled() and (ens.requires_grad or tar.requires_grad)
+    out = []
+    for c0 in range(0, C, step):
+        x, y = ens[:, :, c0:c0 + step], tar[:, c0:c0 + step]
+        if keep and step < C:
+            from torch.utils.checkpoint import checkpoint
+            out.append(checkpoint(_ens_crps_chunk, x, y, w, use_reentrant=False))
+        else:
+            out.append(_ens_crps_chunk(x, y, w))
+    return torch.cat(out, dim=1)
+
+
+class _EnsCrpsSums(torch.autograd.Function):
+    """([B, C, 2] float64 (sum w a, sum w g), the detached [B, C, 4] of the same pass); mk_ens_sums forward, mk_ens_crps_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, ens, tar, wrow):
+        B, E, C, H, W = ens.shape
+        lib = _lib.load()
+        ws = torch.empty(lib.mk_ens_workspace(B, C, H), dtype=torch.float64, device=ens.device)
+        out = torch.empty(B, C, 4, dtype=torch.float64, device=ens.device)
+        ctx.bstride = ens.stride(0) if B > 1 else E * ens.stride(1)      # a stride of a size-1 axis means nothing
+        _lib.check(lib.mk_ens_sums(ens.data_ptr(), _pw_dtype(ens), ctx.bstride, ens.stride(1), tar.data_ptr(), wrow.data_ptr(),
+                                   ws.data_ptr(), out.data_ptr(), None, None, B, E, C, H, W, _stream()), "mk_ens_sums")
+        ctx.save_for_backward(ens, tar, wrow)
+        ctx.mark_non_differentiable(out)
+        return out[..., :2].contiguous(), out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        ens, tar, wrow = ctx.saved_tensors
+        B, E, C, H, W = ens.shape
+        gens = torch.empty(ens.shape, dtype=ens.dtype, device=ens.device)
+        g = g.double().contiguous()
+        _lib.check(_lib.load().mk_ens_crps_bwd(ens.data_ptr(), _pw_dtype(ens), ctx.bstride, ens.stride(1), tar.data_ptr(),
+                                               wrow.data_ptr(), g.data_ptr(), gens.data_ptr(), E * C * H * W, C * H * W,
+                                               B, E, C, H, W, _stream()), "mk_ens_crps_bwd")
+        return gens, None, None
+
+
+def ensemble_crps_sums(ens, tar, wrow, with_sums=False):
+    """The two latitude-weighted integrals the ensemble CRPS losses are made of, ``[B, C, 2]`` float64, differentiable in the
+    members: ``S[b, c] = (sum_hw w a, sum_hw w g)`` with ``a = mean_e |x_e - y|``, ``g = mean_ef |x_e - x_f|`` over all E^2 pairs
+    and ``w = wrow[h]``, of an ensemble ``ens`` ``[B, E, C, H, W]`` (a ``[B * E, C, H, W]`` model output is viewed, member fastest)
+    against a target ``tar`` ``[B, C, H, W]``.  The loss of a point is ``a - (kappa / 2) g``: ``kappa = 1`` the CRPS,
+    ``kappa = E / (E - 1)`` the fair CRPS.  The gradient is that of the all-pairs expression,
+
+        ``d/dx_e = w (gS0 sgn(x_e - y) / E + gS1 2 (L_e - G_e) / E^2)``,   ``L_e, G_e`` the members below and above ``x_e``,
+
+    equal among tied members; a point whose target or one of whose members is NaN gives NaN to every member of that point and
+    to the sums of its ``(b, c)``.  ``with_sums=True`` returns ``(S, sums)`` with the detached ``[B, C, 4]`` in the order of
+    ``ENSEMBLE_SUMS`` from the same pass (spread and ensemble-mean error for a training log).
+
+    ``MK_ENS_LOSS=hip`` (read on every call): CUDA fp32 / bf16 members, 2 to ``ENS_LOSS_MAX_MEMBERS`` of them, take
+    ``mk_ens_sums`` forward and one ``mk_ens_crps_bwd`` launch backward, which writes a contiguous gradient in the members' dtype
+    (the members are read in place through their batch and member strides; the same bits every run, capturable).  CPU tensors,
+    ``E = 1``, more members, other dtypes, a target that requires a gradient and ``MK_ENS_LOSS=torch`` take
+    ``_ensemble_crps_sums_torch``."""
+    hip = _hip_or_torch("MK_ENS_LOSS", ENS_LOSS_DEFAULT)
+    if tar.dim() != 4:
+        raise ValueError(f"ensemble_crps_sums: the target must be [B, C, H, W], got {tuple(tar.shape)}")
+    B, C, H, W = tar.shape
+    if ens.dim() == 4 and B >= 1 and ens.shape[0] % B == 0 and tuple(ens.shape[1:]) == (C, H, W):
+        ens = ens.view(B, ens.shape[0] // B, C, H, W) if ens.is_contiguous() else ens.reshape(B, ens.shape[0] // B, C, H, W)
+    if ens.dim() != 5 or ens.shape[0] != B or tuple(ens.shape[2:]) != (C, H, W) or ens.shape[1] < 1 or min(B, C, H, W) < 1:
+        raise ValueError(f"ensemble_crps_sums: ensemble {tuple(ens.shape)} must be [B, E, C, H, W] or [B * E, C, H, W] for a target "
+                         f"{tuple(tar.shape)}")
+    E = ens.shape[1]
+    dev = ens.device
+    if tar.device != dev or wrow.device != dev:
+        raise ValueError(f"ensemble_crps_sums: ensemble on {dev}, target on {tar.device}, wrow on {wrow.device}")
+    if wrow.numel() != H:
+        raise ValueError(f"ensemble_crps_sums: wrow has {wrow.numel()} weights for {H} latitude rows")
+    if not (hip and ens.is_cuda and 2 <= E <= ENS_LOSS_MAX_MEMBERS and ens.dtype in _LOWP and not tar.requires_grad):
+        out = _ensemble_crps_sums_torch(ens, tar, wrow)
+        s, sums = out[..., :2], out.detach()
+    else:
+        if ens.stride()[2:] != (H * W, W, 1) or min(ens.stride(0), ens.stride(1)) < C * H * W:
+            ens = ens.contiguous()         # every member's [C, H, W] block contiguous; the batch and member strides are free
+        s, sums = _EnsCrpsSums.apply(ens, tar.detach().float().contiguous(), wrow.detach().float().contiguous())
+    return (s, sums) if with_sums else s
 
 
 # ----------------------------------------------------------------------------
