@@ -707,6 +707,31 @@ int mk_ens_crps_bwd(const void* ens, int dtype, long long bstride, long long est
                     const double* gs, void* gens, long long gbstride, long long gestride, int B, int E, int C, int H, int W,
                     void* stream);
 
+/* ---- latitude interpolation (csrc/grid.hip): P planes [Hs][W] onto Hd destination rows, what GridConverter does between
+ * an equiangular archive and a Legendre-Gauss model grid.  Fields are fp32 (dtype 0) or bf16 (1), each side with a dtype, a
+ * plane stride and a row stride (elements) of its own; rows are contiguous along W, start at any element-aligned address,
+ * and only the W columns of a row are touched.  Tables (device): idx [Hd] int32 local source rows in [0, Hs - 2], wgt [Hd]
+ * fp32, any finite value; their contents are not checked here.  With a = x'[p][idx[k]], b = x'[p][idx[k] + 1], d = fl(b - a):
+ *   y[p][k] = |wgt[k]| < 0.5 ? fma(wgt[k], d, a) : fma(fl(wgt[k] - 1), d, b)
+ * x' = x, or with bias and scale [C] fp32 (both or neither) x' = fl(fl(x - bias[c]) / scale[c]), c = p mod C, an IEEE
+ * division.  bf16 widens exactly, the store rounds once.  One launch, no atomics, no workspace, the same bits every run;
+ * 64-bit offsets; fp contraction off.  A refusal (null or misaligned pointer, dtype outside the table, Hs < 2, W < 1, a row
+ * stride below W, overlapping output planes) returns 1 before any launch. */
+int mk_lat_lerp_fwd(const void* x, int xdtype, long long xpstride, long long xrstride, void* y, int ydtype, long long ypstride,
+                    long long yrstride, const int* idx, const float* wgt, const float* bias, const float* scale, int C,
+                    long long P, int Hs, int Hd, int W, void* stream);
+/* The gradient with respect to x, a gather over the transposed table in CSR form: rowptr [Hs + 1], and per term a
+ * destination row term_row and a coefficient term_coef (1 - w for the a-term, w for the b-term, each rounded once to fp32
+ * from the float64 weight), terms of a source
+ * row by ascending destination row, a-term first:
+ *   gx[p][j] = (fma chain from 0, in that order, of term_coef[t] * gy[p][term_row[t]]) / scale[p mod C]
+ * (scale NULL: no division).  A source row without terms gets zeros.  gy [P][Hd][W], gx [P][Hs][W]; rules as above. */
+int mk_lat_lerp_bwd(const void* gy, int gydtype, long long gypstride, long long gyrstride, void* gx, int gxdtype,
+                    long long gxpstride, long long gxrstride, const int* rowptr, const int* term_row, const float* term_coef,
+                    const float* scale, int C, long long P, int Hs, int Hd, int W, void* stream);
+/* Columns of a row one wave of the two kernels takes (the tests choose a width beyond it). */
+int mk_lat_lerp_chunk(void);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

@@ -18,6 +18,8 @@ Mirrors the reference's interfaces for the hot path only:
 * ``makani_amd.histograms``           DatasetHistograms (per-channel value histograms, equal to np.histogram's, on one HIP pass)
 * ``makani_amd.ensemble``             EnsembleScores (CRPS, spread, ensemble-mean RMSE and rank histogram per lead time, on one HIP pass;
                                       ``inference.EnsembleRollout`` runs and scores the perturbed members)
+* ``makani_amd.grids``                GridConverter (equiangular -> Legendre-Gauss latitude interpolation of the loaders, with the
+                                      loader's normalisation, on one HIP pass)
 
 All arithmetic of the spectral path runs in libmakani_amd.so (include/makani_amd.h).
 """

@@ -37,7 +37,7 @@ _HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
 # free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
 KNOBS = {
     **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
-                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_ROWSUM"),
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_GRID", "MK_ROWSUM"),
                     _HIP_TORCH),
     "MK_SPEC_DIAG": ("fused", "public"),
     "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
@@ -2744,6 +2744,189 @@ def ensemble_crps_sums(ens, tar, wrow, with_sums=False):
             ens = ens.contiguous()         # every member's [C, H, W] block contiguous; the batch and member strides are free
         s, sums = _EnsCrpsSums.apply(ens, tar.detach().float().contiguous(), wrow.detach().float().contiguous())
     return (s, sums) if with_sums else s
+
+
+# ----------------------------------------------------------------------------
+# latitude interpolation (csrc/grid.hip: mk_lat_lerp_fwd forward, mk_lat_lerp_bwd backward): the arithmetic of grids.GridConverter
+# ----------------------------------------------------------------------------
+GRID_DEFAULT = "hip"            # MK_GRID: hip | torch.  No row of tools/grid_bench.py is slower than torch
+
+
+class LatInterpTables:
+    """What ``lat_interp`` reads, on one device: ``idx`` int32 ``[Hd]`` local source rows, ``wgt`` fp32 ``[Hd]``, the CSR transpose
+    (``rowptr`` int32 ``[Hs + 1]``, ``term_row`` int32 and ``term_coef`` fp32 ``[2 Hd]``: per source row its terms by ascending
+    destination row, ``1 - w`` for the a-term and ``w`` for the b-term, each rounded once from float64 to fp32), and for the torch formulation ``index``
+    int64 ``[Hd]`` and ``weights`` float64 ``[Hd, 1]``.  ``n_src_rows`` = Hs, ``n_dst_rows`` = Hd."""
+
+    def __init__(self, local, weights64, n_src_rows, device):
+        hd = local.shape[0]
+        w32 = weights64.astype(np.float32)
+        rows = np.stack([local, local + 1], axis=1).reshape(-1)
+        # 1 - w from the float64 weight, rounded once: fl(1 - fl(w)) carries the rounding of w as an ABSOLUTE error, which is
+        # not small against 1 - w where w is close to 1 (the rows next to the equator)
+        coef = np.stack([(1.0 - weights64).astype(np.float32), w32], axis=1).reshape(-1)
+        order = np.argsort(rows, kind="stable")              # by source row; within one, ascending k (and a before b)
+        rowptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n_src_rows))])
+        dev = torch.device(device)
+        self.n_src_rows, self.n_dst_rows, self.device = int(n_src_rows), int(hd), dev
+        self.idx = torch.from_numpy(local.astype(np.int32)).to(dev)
+        self.wgt = torch.from_numpy(w32).to(dev)
+        self.rowptr = torch.from_numpy(rowptr.astype(np.int32)).to(dev)
+        self.term_row = torch.from_numpy((np.repeat(np.arange(hd), 2)[order]).astype(np.int32)).to(dev)
+        self.term_coef = torch.from_numpy(coef[order].astype(np.float32)).to(dev)
+        self.index = torch.from_numpy(local.astype(np.int64)).to(dev)
+        self.weights = torch.from_numpy(weights64.astype(np.float64).reshape(-1, 1)).to(dev)
+
+
+def lat_interp_tables(indices, weights, n_src_rows, src_row0=0, device="cpu"):
+    """The tables of ``lat_interp`` for the destination rows whose GLOBAL source rows are ``indices`` (integers) with ``weights``
+    (float64; any finite value: outside [0, 1] extrapolates) -- a whole table or any slice of one -- on a slab of ``n_src_rows``
+    source rows that starts at global row ``src_row0``.  Every pair must lie in the slab: ``src_row0 <= i`` and
+    ``i + 1 < src_row0 + n_src_rows``, else ``ValueError``.  The contents are checked here, once, and not by the kernels."""
+    i = np.asarray(indices.detach().cpu() if torch.is_tensor(indices) else indices).astype(np.int64).reshape(-1)
+    w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+    n_src_rows, src_row0 = int(n_src_rows), int(src_row0)
+    if i.shape[0] < 1 or i.shape != w.shape:
+        raise ValueError(f"lat_interp_tables: {i.shape[0]} indices and {w.shape[0]} weights (need as many, at least one)")
+    if n_src_rows < 2:
+        raise ValueError(f"lat_interp_tables: {n_src_rows} source rows (a destination row blends two)")
+    if not np.isfinite(w).all():
+        raise ValueError("lat_interp_tables: a weight is not finite")
+    if (i < src_row0).any() or (i + 1 >= src_row0 + n_src_rows).any():
+        raise ValueError(f"lat_interp_tables: source rows {int(i.min())} ... {int(i.max()) + 1} leave the slab "
+                         f"[{src_row0}, {src_row0 + n_src_rows})")
+    return LatInterpTables(i - src_row0, w, n_src_rows, device)
+
+
+def _lat_interp_torch(x, tables, bias=None, scale=None):
+    """The reference's expression (``makani/utils/grids.py``: ``GridConverter.forward`` after the loader's ``(x - bias) / scale``):
+    ``torch.lerp(x[..., i, :], x[..., i + 1, :], w.to(x.dtype))``, ``bias`` / ``scale`` broadcast over the channel axis.  A bf16
+    input is widened to fp32 and blended with the fp32 weights (the result is fp32; the caller rounds it once)."""
+    if x.dtype == torch.bfloat16:
+        x = x.float()
+    if bias is not None:
+        x = (x - bias.to(x.dtype).reshape(-1, 1, 1)) / scale.to(x.dtype).reshape(-1, 1, 1)
+    i = tables.index
+    return torch.lerp(x[..., i, :], x[..., i + 1, :], tables.weights.to(dtype=x.dtype))
+
+
+def _row_contiguous(t):
+    H, W = t.shape[-2:]
+    return (W == 1 or t.stride(-1) == 1) and (H == 1 or t.stride(-2) >= W)
+
+
+def _plane_groups(a, b):
+    """``a`` ``[..., Ha, W]`` and ``b`` ``[..., Hb, W]`` with the same leading shape, as launches: the trailing leading axes that have ONE
+    plane stride in both tensors form the planes of a launch (always at least the last, the channel axis), the axes in front
+    are walked on the host.  Yields ``(address of a, address of b, P, plane stride of a, of b)``."""
+    if a.dim() == 2:
+        a, b = a.unsqueeze(0), b.unsqueeze(0)
+    lead = tuple(a.shape[:-2])
+    m = len(lead) - 1
+
+    def planes(t, q):
+        try:
+            return t.view(*lead[:q], -1, *t.shape[-2:])
+        except RuntimeError:
+            return None
+
+    for q in range(m + 1):
+        va, vb = planes(a, q), planes(b, q)
+        if va is not None and vb is not None:
+            break
+    P = va.shape[q]
+    for outer in np.ndindex(*lead[:q]):
+        oa = sum(int(o) * va.stride(d) for d, o in enumerate(outer))
+        ob = sum(int(o) * vb.stride(d) for d, o in enumerate(outer))
+        yield (a.data_ptr() + oa * a.element_size(), b.data_ptr() + ob * b.element_size(), P, va.stride(q), vb.stride(q))
+
+
+def _lat_lerp_fwd_raw(x, tables, bias, scale, out):
+    """``mk_lat_lerp_fwd`` of ``x`` ``[..., Hs, W]`` into ``out`` ``[..., Hd, W]`` (both row contiguous, any other strides)."""
+    lib = _lib.load()
+    W, C = x.shape[-1], (x.shape[-3] if x.dim() >= 3 else 1)
+    for px, py, P, sx, sy in _plane_groups(x, out):
+        _lib.check(lib.mk_lat_lerp_fwd(px, _pw_dtype(x), sx, x.stride(-2), py, _pw_dtype(out), sy, max(out.stride(-2), W),
+                                       tables.idx.data_ptr(), tables.wgt.data_ptr(), _ptr(bias), _ptr(scale), C, P,
+                                       tables.n_src_rows, tables.n_dst_rows, W, _stream()), "mk_lat_lerp_fwd")
+    return out
+
+
+class _LatInterp(torch.autograd.Function):
+    """``mk_lat_lerp_fwd`` forward, ``mk_lat_lerp_bwd`` backward; no gradient to the tables, ``bias`` or ``scale``."""
+
+    @staticmethod
+    def forward(ctx, x, tables, bias, scale, out, out_dtype):
+        if out is None:
+            out = torch.empty(*x.shape[:-2], tables.n_dst_rows, x.shape[-1], dtype=out_dtype, device=x.device)
+        else:
+            ctx.mark_dirty(out)
+        ctx.tables, ctx.scale, ctx.x_shape, ctx.x_dtype = tables, scale, x.shape, x.dtype
+        return _lat_lerp_fwd_raw(x, tables, bias, scale, out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        tables, scale = ctx.tables, ctx.scale
+        gy = _lowp(gy)
+        if not _row_contiguous(gy):
+            gy = gy.contiguous()
+        gx = torch.empty(ctx.x_shape, dtype=ctx.x_dtype, device=gy.device)
+        lib = _lib.load()
+        W, C = gx.shape[-1], (gx.shape[-3] if gx.dim() >= 3 else 1)
+        for pg, px, P, sg, sx in _plane_groups(gy, gx):
+            _lib.check(lib.mk_lat_lerp_bwd(pg, _pw_dtype(gy), sg, max(gy.stride(-2), W), px, _pw_dtype(gx), sx, W,
+                                           tables.rowptr.data_ptr(), tables.term_row.data_ptr(), tables.term_coef.data_ptr(),
+                                           _ptr(scale), C, P, tables.n_src_rows, tables.n_dst_rows, W, _stream()), "mk_lat_lerp_bwd")
+        return gx, None, None, None, None, None
+
+
+def lat_interp(x, tables, bias=None, scale=None, out=None, out_dtype=None):
+    """Interpolation along latitude: ``y[..., k, :] = lerp(x'[..., i_k, :], x'[..., i_k + 1, :], w_k)`` for ``x`` ``[..., Hs, W]`` and the
+    ``tables`` of ``lat_interp_tables`` (``Hs`` source rows, ``Hd`` destination rows, on ``x``'s device), with ``x' = x`` or, given
+    ``bias`` and ``scale`` (both, ``C`` elements each, e.g. the ``[1, C, 1, 1]`` statistics files; ``C`` the last leading axis of
+    ``x``), ``x' = (x - bias[c]) / scale[c]`` -- the loader's fp32 expression, a subtraction and an IEEE division.  ``out``, if
+    given, is ``[..., Hd, W]`` with contiguous rows and any other strides (a channel slice of a larger buffer); ``out_dtype``
+    (default: ``out``'s, else ``x``'s) may be fp32 or bf16 for either input.  Differentiable in ``x`` only.
+
+    ``MK_GRID=hip`` (read on every call): CUDA fp32 / bf16 tensors take one ``mk_lat_lerp_fwd`` launch per run of planes with a
+    single stride (one for a contiguous tensor), and one ``mk_lat_lerp_bwd`` launch backward: each source row read once per
+    band of rows, each destination row written once, the same bits every run, capturable.  CPU tensors, float64 and
+    ``MK_GRID=torch`` take ``_lat_interp_torch``, for fp32 the reference's ``torch.lerp`` expression exactly.  Deviation: for
+    bf16 data the reference would round the weights to bf16 and blend in bf16; both paths here widen the data to fp32, blend
+    with the fp32 weights and round the result once."""
+    hip = _hip_or_torch("MK_GRID", GRID_DEFAULT)
+    if not isinstance(tables, LatInterpTables):
+        raise TypeError("lat_interp: tables must come from lat_interp_tables")
+    if x.dim() < 2 or x.shape[-2] != tables.n_src_rows:
+        raise ValueError(f"lat_interp: input {tuple(x.shape)} must be [..., {tables.n_src_rows}, W]")
+    if x.device != tables.device:
+        raise ValueError(f"lat_interp: input on {x.device}, tables on {tables.device}")
+    if (bias is None) != (scale is None):
+        raise ValueError("lat_interp: bias and scale come together")
+    C = x.shape[-3] if x.dim() >= 3 else 1
+    if bias is not None and (bias.numel() != C or scale.numel() != C):
+        raise ValueError(f"lat_interp: bias / scale with {bias.numel()} / {scale.numel()} elements for {C} channels")
+    shape = (*x.shape[:-2], tables.n_dst_rows, x.shape[-1])
+    if out is not None:
+        if tuple(out.shape) != shape or out.device != x.device or not _row_contiguous(out):
+            raise ValueError(f"lat_interp: out {tuple(out.shape)} on {out.device} must be {shape} on {x.device} with contiguous rows")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"lat_interp: out is {out.dtype}, out_dtype {out_dtype}")
+        out_dtype = out.dtype
+    elif out_dtype is None:
+        out_dtype = x.dtype
+    if not (hip and x.is_cuda and x.dtype in _LOWP and out_dtype in _LOWP) or x.numel() == 0:
+        y = _lat_interp_torch(x, tables, bias, scale).to(out_dtype)
+        return y if out is None else out.copy_(y)
+    if not _row_contiguous(x):
+        x = x.contiguous()
+    bias, scale = (_f32(bias).to(x.device).reshape(-1), _f32(scale).to(x.device).reshape(-1)) if bias is not None else (None, None)
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=x.device)
+        return _lat_lerp_fwd_raw(x.detach(), tables, bias, scale, out)
+    return _LatInterp.apply(x, tables, bias, scale, out, out_dtype)
 
 
 # ----------------------------------------------------------------------------
