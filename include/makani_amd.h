@@ -732,6 +732,30 @@ int mk_lat_lerp_bwd(const void* gy, int gydtype, long long gypstride, long long 
 /* Columns of a row one wave of the two kernels takes (the tests choose a width beyond it). */
 int mk_lat_lerp_chunk(void);
 
+/* ---- correlated spherical noise (csrc/noise.hip): one step of an isotropic Gaussian random field, drawn straight into the
+ * packed spectrum state [L][M][BC] (complex64, BC fastest) that legendre_inv / inverse_packed synthesise.  The reference has
+ * no such component (its perturbation is white grid noise); this goes beyond it.  The shard holds degrees l_off ... l_off + L - 1
+ * and orders m_off ... m_off + M - 1 of rows row0 ... row0 + BC - 1.  With gl = l_off + l, gm = m_off + m, q = (row0 + bc) >> 1 and
+ * T = t + (t_dev ? *t_dev : 0) mod 2^32 (t_dev: a device int32, read by the kernel, so a captured launch draws anew on replay):
+ *   words = Philox4x32-10(counter (q, gl, gm, T), key (low, high 32 bits of seed));  the seed is the two's complement long long of
+ *           an integer in [0, 2^64).  Row 2q takes words (0, 1) as (a, b), row 2q + 1 words (2, 3)
+ *   u1 = ((a >> 8) + 1) 2^-24,  u2 = (b >> 8) 2^-24,  rad = sqrtf(-2 logf(u1)),  (z_re, z_im) = rad (cospi(2 u2), sinpi(2 u2))
+ *   xi = gm == 0 ? (s sigma_l[l]) z_re + 0 i : (s fl(sigma_l[l] / sqrt 2)) (z_re + i z_im),   s = row_scale ? row_scale[bc] : 1
+ *   phi == 0:     state = xi                       (the old state is not read and may hold NaN)
+ *   0 < phi < 1:  state = fl(fl(phi state) + fl(fl(sqrt(1 - phi^2)) xi))        (AR(1) with stationary variance sigma_l^2)
+ * and every entry with gl < gm is written as exact zero.  sigma_l [L] and row_scale [BC] (or NULL) are device fp32.  The counter
+ * names global indices only: a shard's draw is bitwise the slice of the unsharded draw.  logf, sqrtf and sincospif are the
+ * accurate ones (no fast-math), contraction is off.  One thread per (l, m, q), one 16-byte store per pair for even BC, 8-byte
+ * stores for odd BC.  One launch, no atomics, no workspace, the same bits every run.  Every refusal (null or not 16-byte
+ * aligned state, null sigma_l, L, M or BC below 1, a negative offset, odd or negative row0, q reaching 2^32, phi outside
+ * [0, 1), L M ceil(BC / 2) of 2^31 or more: the kernel's thread index is 32-bit) returns 1 before any launch. */
+int mk_noise_spectrum(void* state, const float* sigma_l, const float* row_scale, int L, int M, long long BC, int l_off, int m_off,
+                      long long row0, long long seed, int t, const int* t_dev, float phi, void* stream);
+/* The four Philox words of counter (q, l, m, t) (global indices) under `seed`, computed on the host by the code the kernel
+ * runs (csrc/philox.h); l, m and t are taken as their 32 bits (a word above 2^31 travels as a negative int) and out4 receives
+ * the words the same way.  q outside [0, 2^32) and a null out4 are refused.  No launch, no GPU needed. */
+int mk_noise_words(long long seed, long long q, int l, int m, int t, int* out4);
+
 /* ---- cosine of the solar zenith angle (csrc/zenith.hip), the unpredicted channel of the production configs, from
  * per-time scalars: fp32, all on the device,
  *   eph [n][4] = (sin dec, cos dec, GMST, right ascension; radians),  sin_lat, cos_lat [H],  lon_rad [W],

@@ -20,6 +20,8 @@ Mirrors the reference's interfaces for the hot path only:
                                       ``inference.EnsembleRollout`` runs and scores the perturbed members)
 * ``makani_amd.grids``                GridConverter (equiangular -> Legendre-Gauss latitude interpolation of the loaders, with the
                                       loader's normalisation, on one HIP pass)
+* ``makani_amd.noise``                SphericalNoise (isotropic Gaussian random fields with a prescribed spectrum, white or AR(1) in
+                                      time, drawn into the packed spectrum on one HIP pass: the perturbation of ensemble members)
 
 All arithmetic of the spectral path runs in libmakani_amd.so (include/makani_amd.h).
 """

@@ -113,13 +113,32 @@ class EnsembleScores:
         return out
 
 
-def perturb_members(x, members, noise_std, generator=None):
+def member_noise(noise, shape, members, dtype):
+    """``[B, E - 1, ...]`` fields of ``noise`` (a ``noise.SphericalNoise``) for members 1 ... E - 1 of ``shape`` = ``[B, ..., H, W]``: one
+    call of ``noise.sample`` with ``B (E - 1) prod(...)`` rows, ordered (sample, member - 1, the remaining leading dims)."""
+    B, lead = shape[0], tuple(shape[1:-2])
+    rows = B * (int(members) - 1) * math.prod(lead)
+    z = noise.sample(rows, batch=B * (int(members) - 1))
+    if tuple(z.shape[-2:]) != tuple(shape[-2:]):
+        raise ValueError(f"perturb_members: the noise is on a {tuple(z.shape[-2:])} grid, the fields on {tuple(shape[-2:])}")
+    return z.view((B, int(members) - 1) + lead + tuple(z.shape[-2:])).to(dtype)
+
+
+def perturb_members(x, members, noise_std, generator=None, noise=None):
     """``[B * E, ...]`` from ``x`` ``[B, ...]``: each sample E = ``members`` times (member fastest), ``noise_std * N(0, 1)``
     (``torch.randn`` with ``generator``) added to members 1 ... E - 1; member 0 is the unperturbed control.  A new tensor.  A
-    training step of an ensemble is ``perturb_members`` -> the stepper at batch ``B * E`` -> ``LossHandler`` with a ``crps`` loss."""
+    training step of an ensemble is ``perturb_members`` -> the stepper at batch ``B * E`` -> ``LossHandler`` with a ``crps`` loss.
+
+    With ``noise`` (a ``noise.SphericalNoise`` on the grid of ``x`` ``[B, ..., H, W]``) the perturbation is ``noise_std`` times one
+    ``noise.sample`` of ``B (E - 1) prod(x.shape[1:-2])`` rows instead: row ``(b (E - 1) + (e - 1)) prod(...) + j`` is the field added
+    to member e of sample b at flat index j of the remaining leading dims (sample, member - 1, leading dims: C order).
+    ``generator`` is then unused."""
     B, E = x.shape[0], int(members)
     out = x.repeat_interleave(E, dim=0)
     if E > 1 and noise_std != 0.0:
+        if noise is not None:
+            out.view((B, E) + tuple(x.shape[1:]))[:, 1:] += noise_std * member_noise(noise, x.shape, E, x.dtype)
+            return out
         noise = torch.randn((B, E - 1) + tuple(x.shape[1:]), generator=generator, device=x.device, dtype=x.dtype)
         out.view((B, E) + tuple(x.shape[1:]))[:, 1:] += noise_std * noise
     return out

@@ -35,7 +35,7 @@ import torch.distributed as dist
 from . import comm, ops
 from .mappings import gather_from_parallel_region
 from .distributed import compute_split_shapes
-from .ensemble import perturb_members
+from .ensemble import member_noise, perturb_members
 from .stepper import _engine_input_dtype
 
 
@@ -304,10 +304,16 @@ class EnsembleRollout(Rollout):
     launch follows the replay on the same stream.  ``Rollout``'s deterministic scores (``metrics``, ``loss``, the RMSE
     accumulators) are not kept here: they are scores of ONE forecast.
 
+    ``noise`` (a ``noise.SphericalNoise`` on the model grid) replaces the white initial perturbation by ``noise_std`` times a
+    correlated field per member, history step and channel (``perturb_members``).  With ``step_noise_std > 0`` the state fed back
+    after every step is ``pred + step_noise_std * noise.sample(...)`` for members 1 ... E - 1 (``feedback``): a stochastic forcing,
+    correlated from step to step where the module's ``phi > 0``; the scored and emitted ``pred`` stays as the tail wrote it.
+    Both run outside the captured step graph, like the initial perturbation.
+
     The unpredicted channels: ``inp_times`` / ``tar_times`` are repeated per member before they are cached; fields that
     the caller cached for B samples are replaced by their per-member repeats."""
 
-    def __init__(self, params, stepper, scores, members, noise_std=None, capture=False):
+    def __init__(self, params, stepper, scores, members, noise_std=None, capture=False, noise=None, step_noise_std=0.0):
         super().__init__(params, stepper, metrics=None, loss=None, capture=capture)
         self.members = int(members)
         if self.members < 1:
@@ -316,6 +322,11 @@ class EnsembleRollout(Rollout):
             raise ValueError(f"EnsembleRollout: {self.members} members, the scores were built for {scores.members}")
         self.scores = scores
         self.noise_std = float(getattr(params, "noise_std", 0.0) or 0.0) if noise_std is None else float(noise_std)
+        self.noise, self.step_noise_std = noise, float(step_noise_std)
+        if self.step_noise_std < 0.0:
+            raise ValueError(f"EnsembleRollout: step_noise_std must not be negative, got {step_noise_std}")
+        if self.step_noise_std > 0.0 and noise is None:
+            raise ValueError("EnsembleRollout: step_noise_std needs a noise module (noise.SphericalNoise)")
 
     def _repeat_times(self, times):
         if times is None:
@@ -327,7 +338,20 @@ class EnsembleRollout(Rollout):
 
     def perturb(self, inp, generator=None):
         """``[B * E, T * C, H, W]``: each initial condition E times, noise on members 1 ... E - 1 (a new tensor)."""
-        return perturb_members(self.preprocessor.flatten_history(inp), self.members, self.noise_std, generator)
+        return perturb_members(self.preprocessor.flatten_history(inp), self.members, self.noise_std, generator, self.noise)
+
+    def feedback(self, pred):
+        """The state the next step starts from: ``pred`` ``[B * E, C, H, W]`` itself, or with ``step_noise_std > 0`` a copy with
+        ``step_noise_std * noise.sample(...)`` added to members 1 ... E - 1 (rows ordered sample, member - 1, channel, as in
+        ``perturb_members``).  ``pred``, which is scored and emitted, is not touched."""
+        E = self.members
+        if self.step_noise_std == 0.0 or E < 2:
+            return pred
+        B = pred.shape[0] // E
+        fed = pred.clone()
+        fed.view((B, E) + tuple(pred.shape[1:]))[:, 1:] += self.step_noise_std * member_noise(
+            self.noise, (B,) + tuple(pred.shape[1:]), E, pred.dtype)
+        return fed
 
     def run(self, inp, tar=None, steps=None, generator=None, inp_times=None, tar_times=None, output_channels=None,
             output_stats=None):
@@ -371,7 +395,7 @@ class EnsembleRollout(Rollout):
                         out = torch.empty((nsteps, B, E) + tuple(emitted.shape[1:]), dtype=torch.float32,
                                           pin_memory=device.type == "cuda")
                     out[idt].copy_(emitted.view((B, E) + tuple(emitted.shape[1:])), non_blocking=True)
-                x = pp.append_history(x, pred, idt)
+                x = pp.append_history(x, self.feedback(pred), idt)
             if device.type == "cuda":
                 torch.cuda.current_stream(device).synchronize()         # once, for the host copies
         return out

@@ -37,7 +37,7 @@ _HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
 # free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
 KNOBS = {
     **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
-                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_GRID", "MK_ROWSUM"),
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_GRID", "MK_NOISE", "MK_ROWSUM"),
                     _HIP_TORCH),
     "MK_SPEC_DIAG": ("fused", "public"),
     "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
@@ -2927,6 +2927,127 @@ def lat_interp(x, tables, bias=None, scale=None, out=None, out_dtype=None):
             out = torch.empty(shape, dtype=out_dtype, device=x.device)
         return _lat_lerp_fwd_raw(x.detach(), tables, bias, scale, out)
     return _LatInterp.apply(x, tables, bias, scale, out, out_dtype)
+
+
+# ----------------------------------------------------------------------------
+# correlated spherical noise (csrc/noise.hip: mk_noise_spectrum): the draw behind noise.SphericalNoise
+# ----------------------------------------------------------------------------
+NOISE_DEFAULT = "hip"           # MK_NOISE: hip | torch.  No row of tools/noise_bench.py is slower than torch
+
+_U32 = 0xFFFFFFFF
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def noise_words(seed, q, l, m, t):
+    """The four Philox4x32-10 words of counter ``(q, l, m, t)`` (each in [0, 2^32)) under ``seed`` (an int in [0, 2^64)), from the
+    host code the kernel shares (``mk_noise_words``; no GPU needed), as Python ints in [0, 2^32)."""
+    for v in (q, l, m, t):
+        if not 0 <= v <= _U32:
+            raise ValueError(f"noise_words: counter word {v} outside [0, 2^32)")
+    out = (ctypes.c_int * 4)()
+    l, m, t = (v - (1 << 32) if v >= 1 << 31 else v for v in (l, m, t))         # the ABI's ints carry the 32 bits
+    _lib.check(_lib.load().mk_noise_words(_seed_ll(seed), q, l, m, t, ctypes.addressof(out)), "mk_noise_words")
+    return [v & _U32 for v in out]
+
+
+def _seed_ll(seed):
+    """``seed`` in [0, 2^64) as the two's complement long long the C ABI takes."""
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"noise: seed {seed} outside [0, 2^64)")
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
+
+
+def _philox_torch(c0, c1, c2, c3, seed):
+    """Philox4x32-10 on int64 tensors holding 32-bit values (broadcast against each other): the four output words.  A 32 x 32-bit
+    product passes int63, but the low 64 bits of the wrapped int64 product are the product's: the high word is masked after
+    the (arithmetic) shift."""
+    k0, k1 = seed & _U32, seed >> 32
+    for _ in range(10):
+        p0, p1 = c0 * _PHILOX_M0, c2 * _PHILOX_M1
+        c0, c1, c2, c3 = ((p1 >> 32) & _U32) ^ c1 ^ k0, p1 & _U32, ((p0 >> 32) & _U32) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W0) & _U32, (k1 + _PHILOX_W1) & _U32
+    return c0, c1, c2, c3
+
+
+def _noise_spectrum_torch(state, sigma_l, row_scale, l_off, m_off, row0, seed, t, t_dev, phi):
+    """``mk_noise_spectrum`` restated with torch ops on ``state``'s device: the same counters, words, ``u1`` and ``u2`` (integer
+    ops), Box-Muller and the amplitude in float64, rounded ONCE to fp32; the AR(1) step then in fp32 as the kernel has it.  No
+    host synchronisation (``t_dev`` stays on the device)."""
+    L, M, BC = state.shape
+    dev = state.device
+    nq = (BC + 1) // 2
+    i64 = dict(dtype=torch.int64, device=dev)
+    q = (torch.arange(nq, **i64) + (row0 >> 1)).view(1, 1, nq)
+    gl = (torch.arange(L, **i64) + l_off).view(L, 1, 1)
+    gm = (torch.arange(M, **i64) + m_off).view(1, M, 1)
+    T = torch.full((1, 1, 1), int(t) & _U32, **i64)
+    if t_dev is not None:
+        T = (T + t_dev.to(torch.int64).view(1, 1, 1)) & _U32
+    w0, w1, w2, w3 = _philox_torch(q, gl, gm, T, int(seed))
+    shape = (L, M, 2 * nq)
+    a = torch.stack([w0.expand(L, M, nq), w2.expand(L, M, nq)], dim=-1).reshape(shape)[..., :BC]
+    b = torch.stack([w1.expand(L, M, nq), w3.expand(L, M, nq)], dim=-1).reshape(shape)[..., :BC]
+    u1 = ((a >> 8) + 1).double() * 2.0 ** -24
+    u2 = (b >> 8).double() * 2.0 ** -24
+    rad = torch.sqrt(-2.0 * torch.log(u1))
+    sig = sigma_l.double().view(L, 1, 1)
+    amp = torch.where(gm == 0, sig, sig * math.sqrt(0.5))
+    if row_scale is not None:
+        amp = amp * row_scale.double().view(1, 1, BC)
+    amp = torch.where(gl >= gm, amp * rad, torch.zeros((), dtype=torch.float64, device=dev))
+    ang = (2.0 * math.pi) * u2
+    xi = torch.complex((amp * torch.cos(ang)).float(), torch.where(gm == 0, torch.zeros_like(amp), amp * torch.sin(ang)).float())
+    if phi == 0.0:
+        return state.copy_(xi)
+    phi32 = torch.tensor(phi, dtype=torch.float32, device=dev)
+    c32 = torch.tensor(math.sqrt(1.0 - float(phi32) ** 2), dtype=torch.float32, device=dev)
+    upd = torch.view_as_complex(phi32 * torch.view_as_real(state) + c32 * torch.view_as_real(xi))
+    return state.copy_(torch.where(gl >= gm, upd, torch.zeros((), dtype=torch.complex64, device=dev)))
+
+
+@torch.no_grad()
+def noise_spectrum(state, sigma_l, seed, t=0, t_dev=None, phi=0.0, row_scale=None, l_off=0, m_off=0, row0=0):
+    """One step of an isotropic Gaussian random field in spectral space, in place: ``state`` (complex64 ``[L, M, BC]``, the packed
+    spectrum, contiguous) becomes ``xi`` (``phi == 0``; the old contents are not read) or ``phi state + sqrt(1 - phi^2) xi``
+    (``0 < phi < 1``), and exact zero where the global degree is below the global order.  ``xi`` for global degree ``l_off + l``,
+    order ``m_off + m`` and global row ``row0 + bc`` comes from Philox4x32-10 with key ``seed`` (an int in [0, 2^64)) and counter
+    ``(row >> 1, degree, order, T)``, ``T = t + t_dev[0]`` modulo 2^32 (``t_dev``: a device int32 tensor read on the device, so a
+    captured call draws anew on replay), through Box-Muller, times ``row_scale[bc] * sigma_l[l]`` (order 0, real) or that over
+    ``sqrt 2`` (include/makani_amd.h has every formula).  A shard's draw is bitwise the slice of the unsharded draw; ``row0`` must be
+    even.  ``sigma_l`` fp32 ``[L]``, ``row_scale`` fp32 ``[BC]`` or None, both on ``state``'s device.
+
+    ``MK_NOISE=hip`` (read on every call): CUDA tensors take one ``mk_noise_spectrum`` launch on the current stream, capturable,
+    the same bits every run.  CPU tensors and ``MK_NOISE=torch`` take ``_noise_spectrum_torch``: the same random words, float64
+    Box-Muller rounded once, so the two agree to the rounding of the kernel's fp32 functions."""
+    hip = _hip_or_torch("MK_NOISE", NOISE_DEFAULT)
+    if state.dtype != torch.complex64 or state.dim() != 3 or not state.is_contiguous() or state.numel() == 0:
+        raise ValueError(f"noise_spectrum: state must be a contiguous non-empty complex64 [L, M, BC] tensor, got {state.dtype} {tuple(state.shape)}")
+    L, M, BC = state.shape
+    seed_ll = _seed_ll(seed)
+    phi = float(phi)
+    if not 0.0 <= phi < 1.0:
+        raise ValueError(f"noise_spectrum: phi {phi} outside [0, 1)")
+    if row0 < 0 or row0 % 2 or l_off < 0 or m_off < 0:
+        raise ValueError(f"noise_spectrum: row0 {row0} must be even and non-negative, offsets ({l_off}, {m_off}) non-negative")
+    t = int(t)
+    if not 0 <= t < 1 << 31:
+        raise ValueError(f"noise_spectrum: t {t} outside [0, 2^31)")
+    if (row0 >> 1) + (BC + 1) // 2 > 1 << 32:
+        raise ValueError("noise_spectrum: the row pair index passes 2^32")
+    if tuple(sigma_l.shape) != (L,) or sigma_l.device != state.device:
+        raise ValueError(f"noise_spectrum: sigma_l {tuple(sigma_l.shape)} on {sigma_l.device} must be [{L}] on {state.device}")
+    if row_scale is not None and (tuple(row_scale.shape) != (BC,) or row_scale.device != state.device):
+        raise ValueError(f"noise_spectrum: row_scale {tuple(row_scale.shape)} on {row_scale.device} must be [{BC}] on {state.device}")
+    if t_dev is not None and (t_dev.dtype != torch.int32 or t_dev.numel() != 1 or t_dev.device != state.device):
+        raise ValueError("noise_spectrum: t_dev must be an int32 tensor of one element on the state's device")
+    sigma_l, row_scale = _f32(sigma_l), _f32(row_scale)
+    if not (hip and state.is_cuda):
+        return _noise_spectrum_torch(state, sigma_l, row_scale, l_off, m_off, row0, seed, t, t_dev, phi)
+    _lib.check(_lib.load().mk_noise_spectrum(state.data_ptr(), sigma_l.data_ptr(), _ptr(row_scale), L, M, BC, l_off, m_off, row0,
+                                             seed_ll, t, _ptr(t_dev), phi, _stream()),
+               "mk_noise_spectrum")
+    return state
 
 
 # ----------------------------------------------------------------------------
