@@ -809,6 +809,36 @@ long long mk_degree_power_workspace(int L, int M, int BC);
 int mk_degree_power(const float* c, double* workspace, double* P, int L, int M, int BC, int l_off, int m_off, void* stream);
 int mk_degree_power_bwd(const float* c, const double* gP, float* gc, int L, int M, int BC, int l_off, int m_off, void* stream);
 
+/* ---- the spectral ensemble CRPS (csrc/spec_crps.hip): the CRPS terms of the spherical-harmonic coefficients of E ensemble
+ * members against a target, summed per degree, and their gradient with respect to the members.  Not in the reference.
+ *   cp [L][M][B E C] complex64, row (b E + e) C + c: forward_packed of a prediction [B E, C, H, W], member fastest;
+ *   ct [L][M][B C]   complex64, row b C + c;   l_off / m_off the shard's global offsets as for mk_degree_power.
+ * Rows with l_off + l < m_off + m may hold anything, they are never loaded.  For every stored coefficient, every (b, c) and
+ * each component k in {re, im} taken as a real number, with x_e the members and y the target widened to fp64 (exact),
+ *   a_k = (1/E) sum_e |x_e - y|,      g_k = (1/E^2) sum_{e,f} |x_e - x_f|,
+ *   S[l][b C + c][0] = sum_m w(m_off + m) (a_re + a_im),   S[l][b C + c][1] = sum_m w(m_off + m) (g_re + g_im),
+ *   w(0) = 1, w(m > 0) = 2,   S [L][B C][2] fp64.
+ * The order of the fp64 additions: per coefficient and component sum_e |x_e - y| in ascending e and sum_{e < f} |x_e - x_f| in
+ * lexicographic (e, f); re + im; acc += w (.) in ascending m within chunks of a fixed number of local orders; the chunks
+ * of (l, b, c) in ascending order by a finishing launch, which multiplies by 1 / E and 2 / E^2.  Deterministic (no atomics),
+ * independent of l_off: the rows of an l slice carry the bits of the same rows of the whole; the sums add up over m shards.
+ * A NaN component in a member or in the target makes both sums of that (b, c, l) NaN.  E is 2 ... 16.  Two launches, no
+ * allocation, synchronisation or host copy: `workspace` holds mk_spec_crps_workspace(L, M, B C) doubles (no need to clear it).
+ * Backward, gS [L][B C][2] fp64 on the device (the upstream gradient of S): with L_e = #{f : x_f < x_e} and
+ * G_e = #{f : x_f > x_e} per component,
+ *   gcp[l][m][(b E + e) C + c] (component k) = w(m_off + m) (gS0 sgn(x_e - y) / E + gS1 2 (L_e - G_e) / E^2),   sgn(0) = 0,
+ * the gradient of the all-pairs expression (abs'(0) = 0) in torch's complex convention (d/d re + i d/d im): tied members get
+ * equal values, the zero imaginary parts of m = 0 an exact zero.  Comparisons in fp32 (exact), counts integers, the value
+ * formed in fp64 and rounded once to fp32.  Exact zeros where l_off + l < m_off + m.  A NaN component in a member or in the
+ * target makes both components of every member's gradient of that coefficient NaN.  No gradient goes to the target.  One
+ * launch, no workspace, no atomics.  Both: 64-bit offsets, fp contraction off; every refusal (null pointer, a buffer not
+ * 8-byte aligned, E outside 2 ... 16, sizes below 1, negative offsets, L M B E C of 2^38 or more) returns 1 before any launch. */
+long long mk_spec_crps_workspace(int L, int M, int BC);
+int mk_spec_crps_sums(const float* cp, const float* ct, double* workspace, double* S, int L, int M, int B, int E, int C, int l_off,
+                      int m_off, void* stream);
+int mk_spec_crps_bwd(const float* cp, const float* ct, const double* gS, float* gcp, int L, int M, int B, int E, int C, int l_off,
+                     int m_off, void* stream);
+
 /* ---- scaled-dot-product attention (csrc/attn.hip): F.scaled_dot_product_attention of the ViT attention module
  * (makani/models/networks/vit.py:44-55), non-causal, no mask, no dropout.  bf16 operands, fp32 scores, softmax and accumulators:
  *   o[b,h,i,:] = sum_j P[i,j] v[b,h,j,:],   P = softmax_j(scale q[b,h,i,:] . k[b,h,j,:]),   lse[b,h,i] = ln sum_j exp(scale s_ij).

@@ -19,6 +19,9 @@ channel's scale, so scoring runs on normalised fields and ``finalize(stds)`` sca
 ``EnsembleCRPSLoss`` is the same score as a training loss (``ops.ensemble_crps_sums``: the forward pass above, and one HIP pass
 for the gradient with respect to the members), selected by the ``crps`` strings of ``losses.LossHandler``; ``perturb_members``
 makes the E members of a training step the way ``EnsembleRollout`` makes those of a rollout.
+
+``EnsembleSpectralCRPSLoss`` is the CRPS of the members' spherical-harmonic coefficients (``ops.spectral_crps_sums`` on the
+transform's packed spectra, one HIP pass each way), selected by the words ``spectral`` and ``combined`` of the ``crps`` strings.
 """
 import math
 
@@ -185,6 +188,89 @@ class EnsembleCRPSLoss(nn.Module):
 
     def from_sums(self, sums, chw):
         """The loss (fp32) from the integrals of the whole field."""
+        s0, s1 = sums.unbind(-1)
+        return torch.sum(chw * (s0 - (0.5 * self.kappa) * s1)).float()
+
+    def forward(self, prd, tar, chw):
+        return self.from_sums(self.sums(prd, tar), chw)
+
+
+class EnsembleSpectralCRPSLoss(nn.Module):
+    """The CRPS of the members' spherical-harmonic coefficients as a training loss.  A CRPS per grid point says nothing about
+    how the members' variance is spread over scales; this term does.  For every coefficient, its real and imaginary part each
+    taken as a real number, ``a = mean_e |x_e - y|`` and ``g = mean_ef |x_e - x_f|``; they are summed over the orders with the
+    weight of every spectral norm here (``m > 0`` twice), over the degrees with ``degree_weights`` ``[lmax]`` (ones by default)
+    and multiplied by ``scale``:
+
+        ``forward(prd, tar, chw) = sum_bc chw_c (S0 - kappa / 2 S1)`` in fp32,   ``kappa = 1 + alpha / (E - 1)`` as in ``EnsembleCRPSLoss``.
+
+    ``scale`` defaults to ``1 / sqrt(4 pi)``: the harmonics are orthonormal, a spatially constant field ``v`` has the one
+    coefficient ``c_00 = sqrt(4 pi) v``, so a constant error costs here what it costs in the grid-space loss.
+
+    ``prd`` is ``[B * E, C, H, W]`` (member fastest) or ``[B, E, C, H, W]``, ``tar`` ``[B, C, H, W]``, fp32 or bf16, on the whole
+    sphere ``img_shape``.  The transform is ``RealSHT`` -- ``DistributedRealSHT`` when ``comm.get_size("spatial") > 1``, fed with
+    the rank's own shard -- and its packed spectra go straight into ``ops.spectral_crps_sums`` (``MK_SPEC_CRPS=hip``: one HIP pass
+    each way); the degree weights act in torch on the small per-degree tensor.  Sharded, ``sums`` returns the partial sums of
+    the rank's degrees and orders: they add up, so the caller all-reduces ``[B, C, 2]`` over ``"spatial"`` and calls
+    ``from_sums``.  ``last_degree_sums`` is the detached ``[B, C, L, 2]`` of the latest call, scaled by ``scale`` but not by the
+    degree weights: ``[..., 0] - kappa / 2 [..., 1]`` is the CRPS per degree, for a log."""
+
+    def __init__(self, img_shape, members, alpha=0.0, grid="equiangular", degree_weights=None, scale=None):
+        super().__init__()
+        self.members, self.alpha = int(members), float(alpha)
+        if self.members < 1:
+            raise ValueError(f"EnsembleSpectralCRPSLoss: members must be at least 1, got {members}")
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"EnsembleSpectralCRPSLoss: alpha must lie in [0, 1], got {alpha}")
+        if self.members == 1 and self.alpha != 0.0:
+            raise ValueError("EnsembleSpectralCRPSLoss: the fair forms need at least 2 members")
+        self.kappa = 1.0 + (self.alpha / (self.members - 1) if self.members > 1 else 0.0)
+        self.sharded = comm.get_size("spatial") > 1
+        if self.sharded:
+            from .distributed import DistributedRealSHT
+            self.sht = DistributedRealSHT(*img_shape, grid=grid).float()
+        else:
+            from .sht import RealSHT
+            self.sht = RealSHT(*img_shape, grid=grid).float()
+        if degree_weights is None:
+            degree_weights = torch.ones(self.sht.lmax, dtype=torch.float64)
+        degree_weights = torch.as_tensor(degree_weights, dtype=torch.float64).reshape(-1)
+        if degree_weights.numel() != self.sht.lmax:
+            raise ValueError(f"EnsembleSpectralCRPSLoss: {degree_weights.numel()} degree weights for lmax = {self.sht.lmax}")
+        self.register_buffer("degree_weights", degree_weights, persistent=False)
+        self.scale = 1.0 / math.sqrt(4.0 * math.pi) if scale is None else float(scale)
+        self.last_degree_sums = None
+
+    def sums_from_spectrum(self, cp, ct, batch, l_off=0, m_off=0):
+        """``[batch, C, 2]`` float64 from packed spectra ``cp`` ``[L_loc, M_loc, batch * E * C]`` and ``ct`` ``[L_loc, M_loc, batch * C]`` of the
+        degrees from ``l_off`` and the orders from ``m_off`` on.  They add up over the shards of a spectrum."""
+        s = ops.spectral_crps_sums(cp, ct, self.members, l_off, m_off, batch) * self.scale        # [batch * C, L_loc, 2]
+        nl = s.shape[1]
+        self.last_degree_sums = s.detach().reshape(batch, -1, nl, 2)
+        wl = self.degree_weights[l_off:l_off + nl].reshape(1, nl, 1)                              # of the GLOBAL degree
+        return (s * wl).sum(dim=1).reshape(batch, -1, 2)
+
+    def sums(self, prd, tar):
+        """``[B, C, 2]`` float64 of the fields (this rank's shard of them under spatial parallelism, where the sums are those of
+        the rank's degrees and orders)."""
+        if tar.dim() != 4 or prd.numel() != self.members * tar.numel() or tuple(prd.shape[-3:]) != tuple(tar.shape[-3:]):
+            raise ValueError(f"EnsembleSpectralCRPSLoss: prediction {tuple(prd.shape)} is not {self.members} members of a target "
+                             f"{tuple(tar.shape)}")
+        B, C, H, W = tar.shape
+        want = (self.sht.nlat_local, self.sht.nlon_local) if self.sharded else (self.sht.nlat, self.sht.nlon)
+        if (H, W) != want:
+            raise ValueError(f"EnsembleSpectralCRPSLoss: expected [..., {want[0]}, {want[1]}], got {tuple(tar.shape)}")
+        prd, tar = ops._lowp(prd), ops._lowp(tar)
+        if self.sharded:
+            cp = self.sht.forward_packed(prd.reshape(B * self.members, C, H, W).contiguous())
+            ct = self.sht.forward_packed(tar.contiguous())
+            return self.sums_from_spectrum(cp, ct, B, self.sht.l_off, self.sht.m_off)
+        cp = self.sht.forward_packed(prd.reshape(-1, H, W).contiguous())
+        ct = self.sht.forward_packed(tar.reshape(-1, H, W).contiguous())
+        return self.sums_from_spectrum(cp, ct, B)
+
+    def from_sums(self, sums, chw):
+        """The loss (fp32) from the sums of the whole spectrum."""
         s0, s1 = sums.unbind(-1)
         return torch.sum(chw * (s0 - (0.5 * self.kappa) * s1)).float()
 

@@ -258,7 +258,11 @@ class LossHandler(nn.Module):
     A loss string with the word ``crps`` ("ensemble crps", "fair ensemble crps", "almost-fair ensemble crps"; not in the
     reference) selects ``ensemble.EnsembleCRPSLoss`` with ``params.ensemble_size`` members: ``prd`` is then ``[B * E, C', H, W]``
     (member fastest) for a ``tar`` ``[B, C', H, W]``.  "fair" is ``alpha = 1``, "almost-fair" ``alpha = params.crps_alpha`` (0.95);
-    "weighted", "temp-std" and "pole-masked" act as for "l1"; "squared" is an error.  Sharded, the ``[B, C', 2]`` sums are all-reduced."""
+    "weighted", "temp-std" and "pole-masked" act as for "l1"; "squared" is an error.  Sharded, the ``[B, C', 2]`` sums are all-reduced.
+    With ``crps``, the word ``spectral`` selects ``ensemble.EnsembleSpectralCRPSLoss`` (the CRPS of the members' spherical-harmonic
+    coefficients) alone and ``combined`` the sum ``EnsembleCRPSLoss + params.crps_spectral_weight * EnsembleSpectralCRPSLoss``.  The
+    spectral term needs the whole sphere: a crop is an error, and so is "pole-masked" with "spectral" (with "combined" it acts on
+    the grid-space term only).  Sharded, its ``[B, C', 2]`` sums are all-reduced over ``"spatial"`` once."""
 
     def __init__(self, params):
         super().__init__()
@@ -302,8 +306,31 @@ class LossHandler(nn.Module):
             if members is None:
                 raise ValueError(f"loss {self.loss_type!r} needs params.ensemble_size, the number of members per target")
             alpha = float(getattr(params, "crps_alpha", 0.95)) if "almost-fair" in loss_type else 1.0 if "fair" in loss_type else 0.0
-            self.loss_obj = EnsembleCRPSLoss(self.img_shape, self.crop_shape, self.crop_offset, members, alpha=alpha,
-                                             pole_mask=pole_mask, quadrature_rule=rule)
+            # "spectral": the CRPS of the spherical-harmonic coefficients alone; "combined": the grid-space CRPS plus
+            # params.crps_spectral_weight times the spectral one
+            self.crps_spectral, self.crps_combined = "spectral" in loss_type, "combined" in loss_type
+            self.spectral_obj = None
+            if self.crps_spectral and self.crps_combined:
+                raise ValueError(f"loss {self.loss_type!r}: 'spectral' and 'combined' exclude each other")
+            if self.crps_spectral or self.crps_combined:
+                from .ensemble import EnsembleSpectralCRPSLoss
+                if tuple(self.crop_shape) != tuple(self.img_shape) or tuple(self.crop_offset) != (0, 0):
+                    raise ValueError(f"loss {self.loss_type!r}: the spectral CRPS needs the whole sphere {self.img_shape}, got the crop "
+                                     f"{self.crop_shape} at {self.crop_offset}")
+                if self.crps_spectral and pole_mask:
+                    raise ValueError(f"loss {self.loss_type!r}: 'pole-masked' has no meaning for the spectral CRPS")
+                if self.crps_combined:
+                    weight = getattr(params, "crps_spectral_weight", None)
+                    if weight is None:
+                        raise ValueError(f"loss {self.loss_type!r} needs params.crps_spectral_weight, the weight of the spectral term")
+                    self.crps_spectral_weight = float(weight)
+                self.spectral_obj = EnsembleSpectralCRPSLoss(self.img_shape, members, alpha=alpha,
+                                                             grid="legendre-gauss" if rule == "legendre-gauss" else "equiangular")
+            if self.crps_spectral:
+                self.loss_obj = self.spectral_obj
+            else:
+                self.loss_obj = EnsembleCRPSLoss(self.img_shape, self.crop_shape, self.crop_offset, members, alpha=alpha,
+                                                 pole_mask=pole_mask, quadrature_rule=rule)
         elif "l2" in loss_type:
             if "geometric" in loss_type:
                 self.loss_obj = GeometricLpLoss(self.img_shape, self.crop_shape, self.crop_offset, p=2, squared=squared,
@@ -343,14 +370,28 @@ class LossHandler(nn.Module):
     def is_distributed(self):
         return False
 
+    def _spectral_crps(self, prd, tar, chw):
+        """The spectral CRPS term: sharded, the rank's shard is transformed by the loss's own distributed transform and the
+        ``[B, C', 2]`` partial sums of its degrees and orders are all-reduced once; no field or spectrum is gathered."""
+        sums = self.spectral_obj.sums(prd, tar)
+        if self.do_gather_input:
+            sums = reduce_from_parallel_region(sums, "spatial")
+        return self.spectral_obj.from_sums(sums, chw)
+
     def forward(self, prd, tar, inp=None):
         chw = self.channel_weights
         chw = (chw * self.multistep_weight).reshape(1, -1) if self.training else chw.reshape(1, -1)
         if "crps" in self.loss_type.split():
+            if self.crps_spectral:
+                return self._spectral_crps(prd, tar, chw)
             if not self.do_gather_input:
-                return self.loss_obj(prd, tar, chw)
-            sums = self.loss_obj.sums(prd, tar, self.shard_rows)      # this rank's rows; [B, C', 2] add up, no field is gathered
-            return self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
+                loss = self.loss_obj(prd, tar, chw)
+            else:
+                sums = self.loss_obj.sums(prd, tar, self.shard_rows)      # this rank's rows; [B, C', 2] add up, no field is gathered
+                loss = self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
+            if self.crps_combined:
+                loss = loss + self.crps_spectral_weight * self._spectral_crps(prd, tar, chw)
+            return loss
         if self.do_gather_input:
             if isinstance(self.loss_obj, GeometricLpLoss) and self.loss_obj.has_sums(prd, tar):
                 sums = self.loss_obj.sums(prd, tar, self.shard_rows)

@@ -37,7 +37,7 @@ _HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
 # free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
 KNOBS = {
     **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
-                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_GRID", "MK_NOISE", "MK_ROWSUM"),
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_GRID", "MK_NOISE", "MK_ROWSUM", "MK_SPEC_CRPS"),
                     _HIP_TORCH),
     "MK_SPEC_DIAG": ("fused", "public"),
     "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
@@ -2744,6 +2744,128 @@ def ensemble_crps_sums(ens, tar, wrow, with_sums=False):
             ens = ens.contiguous()         # every member's [C, H, W] block contiguous; the batch and member strides are free
         s, sums = _EnsCrpsSums.apply(ens, tar.detach().float().contiguous(), wrow.detach().float().contiguous())
     return (s, sums) if with_sums else s
+
+
+# ----------------------------------------------------------------------------
+# the spectral ensemble CRPS (csrc/spec_crps.hip: mk_spec_crps_sums forward, mk_spec_crps_bwd backward)
+# ----------------------------------------------------------------------------
+SPEC_CRPS_DEFAULT = "hip"       # MK_SPEC_CRPS: hip | torch.  No row of tools/spec_crps_bench.py is slower than torch
+SPEC_CRPS_MAX_MEMBERS = 16      # what the kernels take: a thread holds the members of its coefficient in registers
+
+
+def _spec_crps_chunk(x, y, w):
+    """``[l, B, C, 2]`` float64 of a slice of degrees: ``x`` ``[l, M, B, E, C, 2]`` and ``y`` ``[l, M, B, C, 2]`` the (re, im)
+    components with the unstored triangle already set to zero, ``w`` ``[l, M]`` float64 the order weights (zero there).
+
+    As in ``_ens_crps_chunk``, ``sum_ef |x_e - x_f|`` is written as ``2 sum_e (x_e - c) r_e`` with ``r_e = L_e - G_e`` summed as
+    integers and detached, so the backward multiplies the upstream gradient by ``r_e`` once: equal among tied members and
+    exactly zero where ``L_e = G_e``.  ``sum_e r_e = 0``, so any constant ``c`` drops out; the detached member mean keeps
+    ``sum_e |x_e - c| |r_e|`` below ``sum_ef |x_e - x_f|``."""
+    E = x.shape[3]
+    x, y = x.double(), y.double()
+    a = (x - y.unsqueeze(3)).abs().sum(dim=3) / E
+    with torch.no_grad():
+        r = torch.sign(x.unsqueeze(3) - x.unsqueeze(4)).sum(dim=3)          # [l, M, B, f, e, C, 2] = x_e - x_f, summed over f
+        c = x.sum(dim=3, keepdim=True) / E
+        # 1 at a good coefficient, NaN where a component of the target or of a member is: both terms and, in the backward,
+        # both components of every member's gradient become NaN there (sgn(NaN) is 0 in torch's abs')
+        mark = (1.0 + 0.0 * (y.sum(dim=-1) + x.sum(dim=(3, -1)))).unsqueeze(-1)
+    g = ((x - c) * r).sum(dim=3) * (2.0 / (E * E))
+    w = w.reshape(w.shape + (1, 1))
+    return torch.stack([(w * (f * mark).sum(dim=-1)).sum(dim=1) for f in (a, g)], dim=-1)
+
+
+def _spectral_crps_sums_torch(cp, ct, members, l_off=0, m_off=0, batch=1):
+    """``spectral_crps_sums`` in torch float64 on the tensors' device under ordinary autograd: the all-pairs expression (see
+    ``_spec_crps_chunk`` for how the pairs are written), over the stored triangle only -- the rows with
+    ``l_off + l < m_off + m`` are replaced by zeros before any arithmetic and get zero gradients.  The degrees are walked in
+    slices so that an ``E^2`` temporary holds at most ``_ENS_TORCH_CHUNK`` elements; under autograd a slice is recomputed in the
+    backward instead of kept (``torch.utils.checkpoint``)."""
+    L, M, BC = ct.shape
+    E, B = int(members), int(batch)
+    C = BC // B
+    l = torch.arange(L, device=cp.device).reshape(L, 1) + l_off
+    m = torch.arange(M, device=cp.device).reshape(1, M) + m_off
+    stored = l >= m
+    w = torch.where(stored, torch.where(m == 0, 1.0, 2.0).to(torch.float64).expand(L, M), torch.zeros((), dtype=torch.float64, device=cp.device))
+    x = torch.view_as_real(cp).reshape(L, M, B, E, C, 2)
+    y = torch.view_as_real(ct).reshape(L, M, B, C, 2)
+    x = torch.where(stored.reshape(L, M, 1, 1, 1, 1), x, torch.zeros_like(x))
+    y = torch.where(stored.reshape(L, M, 1, 1, 1), y, torch.zeros_like(y))
+    step = max(1, _ENS_TORCH_CHUNK // max(1, 2 * M * B * E * E * C))
+    keep = torch.is_grad_enabled() and (cp.requires_grad or ct.requires_grad)
+    out = []
+    for l0 in range(0, L, step):
+        args = (x[l0:l0 + step], y[l0:l0 + step], w[l0:l0 + step])
+        if keep and step < L:
+            from torch.utils.checkpoint import checkpoint
+            out.append(checkpoint(_spec_crps_chunk, *args, use_reentrant=False))
+        else:
+            out.append(_spec_crps_chunk(*args))
+    return torch.cat(out, dim=0).permute(1, 2, 0, 3).reshape(BC, L, 2)
+
+
+class _SpecCrpsSums(torch.autograd.Function):
+    """[BC, L, 2] float64 of packed spectra cp [L, M, B E C] and ct [L, M, BC]; mk_spec_crps_sums forward, mk_spec_crps_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, cp, ct, B, E, C, l_off, m_off):
+        L, M, BC = ct.shape
+        lib = _lib.load()
+        ws = torch.empty(lib.mk_spec_crps_workspace(L, M, BC), dtype=torch.float64, device=cp.device)
+        out = torch.empty(L, BC, 2, dtype=torch.float64, device=cp.device)
+        _lib.check(lib.mk_spec_crps_sums(cp.data_ptr(), ct.data_ptr(), ws.data_ptr(), out.data_ptr(), L, M, B, E, C, l_off, m_off,
+                                         _stream()), "mk_spec_crps_sums")
+        ctx.save_for_backward(cp, ct)
+        ctx.dims = (B, E, C, l_off, m_off)
+        return out.permute(1, 0, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        cp, ct = ctx.saved_tensors
+        L, M, _ = ct.shape
+        gs = g.permute(1, 0, 2).to(torch.float64).contiguous()      # [L, BC, 2], as the kernel wrote S
+        gcp = torch.empty_like(cp)
+        _lib.check(_lib.load().mk_spec_crps_bwd(cp.data_ptr(), ct.data_ptr(), gs.data_ptr(), gcp.data_ptr(), L, M, *ctx.dims,
+                                                _stream()), "mk_spec_crps_bwd")
+        return gcp, None, None, None, None, None, None
+
+
+def spectral_crps_sums(cp, ct, members, l_off=0, m_off=0, batch=1):
+    """The per-degree sums the spectral ensemble CRPS is made of, ``[B C, L, 2]`` float64, differentiable in the members' spectra.
+    ``cp`` is the packed spectrum ``[L, M, B E C]`` complex64 of the predictions (row ``(b E + e) C + c``: ``forward_packed`` of
+    ``[B E, C, H, W]``, member fastest), ``ct`` ``[L, M, B C]`` that of the target, ``members`` = E and ``batch`` = B (the rows
+    alone do not say how they split into samples and channels).  For every stored coefficient (``l_off + l >= m_off + m``), each
+    component ``k`` of it taken as a real number, ``a_k = mean_e |x_e - y|`` and ``g_k = mean_ef |x_e - x_f|`` over all E^2 pairs,
+
+        ``S[bc, l, 0] = sum_m w (a_re + a_im)``,   ``S[bc, l, 1] = sum_m w (g_re + g_im)``,   ``w(0) = 1``, ``w(m > 0) = 2``.
+
+    The rows the Legendre kernels leave unwritten are never read.  The sums concatenate over ``l`` shards and add up over ``m``
+    shards, as ``degree_power``'s do.  The gradient is that of the all-pairs expression, per component
+    ``w (gS0 sgn(x_e - y) / E + gS1 2 (L_e - G_e) / E^2)`` in torch's complex convention: equal among tied members, exactly zero
+    for the zero imaginary parts of ``m = 0`` and in the unstored triangle.  A NaN component of a member or the target makes the
+    gradients of that coefficient's members and the sums of its ``(b, c, l)`` NaN.
+
+    ``MK_SPEC_CRPS=hip`` (read on every call): CUDA tensors with 2 to ``SPEC_CRPS_MAX_MEMBERS`` members take ``mk_spec_crps_sums``
+    (a streaming pass and a fixed-order finalize: the same bits every run, capturable) and one ``mk_spec_crps_bwd`` launch
+    backward; no gradient flows to the target there.  CPU tensors, ``E = 1``, more members, a target that requires a gradient
+    and ``MK_SPEC_CRPS=torch`` take ``_spectral_crps_sums_torch``."""
+    hip = _hip_or_torch("MK_SPEC_CRPS", SPEC_CRPS_DEFAULT)
+    E, B, l_off, m_off = int(members), int(batch), int(l_off), int(m_off)
+    for name, t in (("cp", cp), ("ct", ct)):
+        if t.dim() != 3 or t.dtype != torch.complex64 or min(t.shape) < 1:
+            raise ValueError(f"spectral_crps_sums: {name} must be a non-empty complex64 spectrum [L, M, rows], got {t.dtype} {tuple(t.shape)}")
+    if E < 1 or B < 1 or ct.shape[2] % B or tuple(cp.shape) != (ct.shape[0], ct.shape[1], E * ct.shape[2]):
+        raise ValueError(f"spectral_crps_sums: {tuple(cp.shape)} is not the spectrum of {E} members of a target {tuple(ct.shape)} "
+                         f"of {B} samples")
+    if l_off < 0 or m_off < 0:
+        raise ValueError(f"spectral_crps_sums: offsets must not be negative, got l_off={l_off}, m_off={m_off}")
+    if cp.device != ct.device:
+        raise ValueError(f"spectral_crps_sums: predictions on {cp.device}, target on {ct.device}")
+    if not (hip and cp.is_cuda and 2 <= E <= SPEC_CRPS_MAX_MEMBERS and not ct.requires_grad):
+        return _spectral_crps_sums_torch(cp, ct, E, l_off, m_off, B)
+    return _SpecCrpsSums.apply(cp.contiguous(), ct.detach().contiguous(), B, E, ct.shape[2] // B, l_off, m_off)
 
 
 # ----------------------------------------------------------------------------
