@@ -21,7 +21,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import comm, ops
-from .sht import _SHTBase
+from .sht import RealSHT, _SHTBase
 
 
 def compute_split_shapes(size, num_chunks):
@@ -34,6 +34,22 @@ def compute_split_shapes(size, num_chunks):
         chunk = size // num_chunks
         last = size - chunk * (num_chunks - 1)
     return [chunk] * (num_chunks - 1) + [last]
+
+
+def shard_span(size, axis):
+    """``(offset, length)`` of this rank's part of an axis of ``size`` split over the comm axis ``axis`` (``"h"`` or ``"w"``):
+    ``(0, size)`` when that axis has one rank."""
+    shapes = compute_split_shapes(size, comm.get_size(axis))
+    rank = comm.get_rank(axis)
+    return sum(shapes[:rank]), shapes[rank]
+
+
+def all_reduce_spatial(t):
+    """Sum ``t`` in place over the ``"spatial"`` group when it has more than one rank; nothing otherwise.  No autograd:
+    the losses reduce with ``mappings.reduce_from_parallel_region``, whose backward is the identity."""
+    if comm.get_size("spatial") > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))
+    return t
 
 
 def split_tensor_along_dim(tensor, dim, num_chunks):
@@ -204,13 +220,24 @@ class DistributedRealSHT(_DistSHTBase):
             c = distributed_transpose_polar.apply(c, (0, 3), compute_split_shapes(C, self.comm_size_polar))
         return c.reshape(c.shape[0], c.shape[1], B * C).contiguous()
 
+    def forward_packed_fields(self, x4):
+        """``RealSHT.forward_packed_fields`` for this rank's shard ``[B, C, nlat_loc, nlon_loc]``: the offsets are the shard's."""
+        return self.forward_packed(x4.contiguous()), self.l_off, self.m_off
+
     def forward(self, x):
         if x.dim() != 4:
             raise ValueError("DistributedRealSHT expects [B, C, nlat_loc, nlon_loc]")
-        x = ops._lowp(x)
         B, C = x.shape[:2]
-        c = ops.spec_unpack(self.forward_packed(x.contiguous()), self.l_off, self.m_off)
+        c = ops.spec_unpack(*self.forward_packed_fields(ops._lowp(x)))
         return c.reshape(B, C, self.lmax_local, self.mmax_local)
+
+
+def real_sht(img_shape, grid):
+    """The fp32 forward transform of ``img_shape`` fields for a caller that feeds it ``[B, C, H, W]`` through
+    ``forward_packed_fields``: ``DistributedRealSHT`` (fed with the rank's shard) when the ``"spatial"`` group has more than one
+    rank, ``RealSHT`` otherwise."""
+    cls = DistributedRealSHT if comm.get_size("spatial") > 1 else RealSHT
+    return cls(*img_shape, grid=grid).float()
 
 
 class DistributedInverseRealSHT(_DistSHTBase):

@@ -30,7 +30,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import comm, ops
-from .distributed import compute_split_shapes
+from .distributed import all_reduce_spatial, real_sht, shard_span
 from .losses import GridQuadrature
 
 
@@ -51,13 +51,8 @@ class EnsembleScores:
         self.crop_offset = (params.img_crop_offset_x, params.img_crop_offset_y)
         rule = "legendre-gauss" if params.model_grid_type == "legendre_gauss" else "naive"
         quad = GridQuadrature(rule, img_shape=self.img_shape, crop_shape=self.crop_shape, crop_offset=self.crop_offset, normalize=True)
-        wrow = quad.quad_weight[0, 0, :, 0]
-        self.spatial_size = comm.get_size("spatial")
-        if self.spatial_size > 1:
-            hs = compute_split_shapes(self.crop_shape[0], comm.get_size("h"))
-            h0 = sum(hs[:comm.get_rank("h")])
-            wrow = wrow[h0:h0 + hs[comm.get_rank("h")]]
-        self.wrow = wrow.float().contiguous().to(self.device)
+        h0, hs = shard_span(self.crop_shape[0], "h")
+        self.wrow = quad.row_weights[h0:h0 + hs].float().contiguous().to(self.device)
         C, E = self.N_out_channels, self.members
         self.sums = torch.zeros(self.steps, C, 4, dtype=torch.float64, device=self.device)      # over samples: A, G, sqrt Q, sqrt V
         self.counter = torch.zeros(self.steps, dtype=torch.float64, device=self.device)          # samples per lead time
@@ -79,9 +74,7 @@ class EnsembleScores:
             if ens.numel() != self.members * tar.numel():
                 raise ValueError(f"EnsembleScores.update: ensemble {tuple(ens.shape)} is not {self.members} members of a target "
                                  f"{tuple(tar.shape)}")
-            s = ops.ensemble_sums(ens, tar, self.wrow, self.rank_histogram[idt], self.skipped[idt])
-            if self.spatial_size > 1:
-                dist.all_reduce(s, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))
+            s = all_reduce_spatial(ops.ensemble_sums(ens, tar, self.wrow, self.rank_histogram[idt], self.skipped[idt]))
             self.sums[idt, :, :2] += s[..., :2].sum(dim=0)
             self.sums[idt, :, 2:] += torch.sqrt(s[..., 2:]).sum(dim=0)
             self.counter[idt] += B
@@ -96,13 +89,11 @@ class EnsembleScores:
         with torch.no_grad():
             sums, n = self.sums.clone(), self.counter.clone()
             ranks, skipped = self.rank_histogram.clone(), self.skipped.clone()
-            if dist.is_initialized():
-                if self.spatial_size > 1:       # every spatial rank counted its own shard; the sums are whole already
-                    for t in (ranks, skipped):
-                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))
-                if comm.get_size("data") > 1:
-                    for t in (sums, n, ranks, skipped):
-                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=comm.get_group("data"))
+            for t in (ranks, skipped):          # every spatial rank counted its own shard; the sums are whole already
+                all_reduce_spatial(t)
+            if dist.is_initialized() and comm.get_size("data") > 1:
+                for t in (sums, n, ranks, skipped):
+                    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=comm.get_group("data"))
             mean = sums / n.reshape(-1, 1, 1)
             A, G, rmse, spread = mean.unbind(dim=-1)
             nan = torch.full_like(A, float("nan"))
@@ -147,7 +138,32 @@ def perturb_members(x, members, noise_std, generator=None, noise=None):
     return out
 
 
-class EnsembleCRPSLoss(nn.Module):
+class _EnsembleCRPSBase(nn.Module):
+    """What the two CRPS losses share: the checks on ``members`` and ``alpha``, ``kappa = 1 + alpha / (E - 1)``, and the loss
+    ``sum_bc chw_c (S0 - kappa / 2 S1)`` in fp32 from the ``[B, C, 2]`` float64 sums of the subclass's ``sums``."""
+
+    def __init__(self, members, alpha):
+        super().__init__()
+        name = type(self).__name__
+        self.members, self.alpha = int(members), float(alpha)
+        if self.members < 1:
+            raise ValueError(f"{name}: members must be at least 1, got {members}")
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"{name}: alpha must lie in [0, 1], got {alpha}")
+        if self.members == 1 and self.alpha != 0.0:
+            raise ValueError(f"{name}: the fair forms need at least 2 members")
+        self.kappa = 1.0 + (self.alpha / (self.members - 1) if self.members > 1 else 0.0)
+
+    def from_sums(self, sums, chw):
+        """The loss (fp32) from the sums of the whole field (of the whole spectrum)."""
+        s0, s1 = sums.unbind(-1)
+        return torch.sum(chw * (s0 - (0.5 * self.kappa) * s1)).float()
+
+    def forward(self, prd, tar, chw):
+        return self.from_sums(self.sums(prd, tar), chw)
+
+
+class EnsembleCRPSLoss(_EnsembleCRPSBase):
     """The CRPS of the members' empirical distribution as a training loss: per point ``a - (kappa / 2) g`` with
     ``a = mean_e |x_e - y|``, ``g = mean_ef |x_e - x_f|`` and ``kappa = 1 + alpha / (E - 1)`` -- ``alpha = 0`` the CRPS, ``alpha = 1``
     the fair CRPS (unbiased in E), in between the almost-fair CRPS -- integrated with the latitude weights ``GeometricLpLoss``
@@ -160,18 +176,10 @@ class EnsembleCRPSLoss(nn.Module):
     (``ops.ENSEMBLE_SUMS``) of the latest call over the rows it was given: spread and ensemble-mean error for a log."""
 
     def __init__(self, img_shape, crop_shape, crop_offset, members, alpha=0.0, pole_mask=0, quadrature_rule="naive"):
-        super().__init__()
-        self.members, self.alpha = int(members), float(alpha)
-        if self.members < 1:
-            raise ValueError(f"EnsembleCRPSLoss: members must be at least 1, got {members}")
-        if not 0.0 <= self.alpha <= 1.0:
-            raise ValueError(f"EnsembleCRPSLoss: alpha must lie in [0, 1], got {alpha}")
-        if self.members == 1 and self.alpha != 0.0:
-            raise ValueError("EnsembleCRPSLoss: the fair forms need at least 2 members")
-        self.kappa = 1.0 + (self.alpha / (self.members - 1) if self.members > 1 else 0.0)
+        super().__init__(members, alpha)
         self.quadrature = GridQuadrature(quadrature_rule, img_shape=img_shape, crop_shape=crop_shape, crop_offset=crop_offset,
                                          normalize=True, pole_mask=pole_mask)
-        wrow = self.quadrature.quad_weight[0, 0, :, 0].contiguous()
+        wrow = self.quadrature.row_weights.contiguous()
         self.register_buffer("wrow", wrow, persistent=False)
         self.register_buffer("wrow32", wrow.float(), persistent=False)
         self.last_sums = None
@@ -186,16 +194,8 @@ class EnsembleCRPSLoss(nn.Module):
         s, self.last_sums = ops.ensemble_crps_sums(prd, tar, wrow if rows is None else wrow[rows], with_sums=True)
         return s
 
-    def from_sums(self, sums, chw):
-        """The loss (fp32) from the integrals of the whole field."""
-        s0, s1 = sums.unbind(-1)
-        return torch.sum(chw * (s0 - (0.5 * self.kappa) * s1)).float()
 
-    def forward(self, prd, tar, chw):
-        return self.from_sums(self.sums(prd, tar), chw)
-
-
-class EnsembleSpectralCRPSLoss(nn.Module):
+class EnsembleSpectralCRPSLoss(_EnsembleCRPSBase):
     """The CRPS of the members' spherical-harmonic coefficients as a training loss.  A CRPS per grid point says nothing about
     how the members' variance is spread over scales; this term does.  For every coefficient, its real and imaginary part each
     taken as a real number, ``a = mean_e |x_e - y|`` and ``g = mean_ef |x_e - x_f|``; they are summed over the orders with the
@@ -216,22 +216,9 @@ class EnsembleSpectralCRPSLoss(nn.Module):
     degree weights: ``[..., 0] - kappa / 2 [..., 1]`` is the CRPS per degree, for a log."""
 
     def __init__(self, img_shape, members, alpha=0.0, grid="equiangular", degree_weights=None, scale=None):
-        super().__init__()
-        self.members, self.alpha = int(members), float(alpha)
-        if self.members < 1:
-            raise ValueError(f"EnsembleSpectralCRPSLoss: members must be at least 1, got {members}")
-        if not 0.0 <= self.alpha <= 1.0:
-            raise ValueError(f"EnsembleSpectralCRPSLoss: alpha must lie in [0, 1], got {alpha}")
-        if self.members == 1 and self.alpha != 0.0:
-            raise ValueError("EnsembleSpectralCRPSLoss: the fair forms need at least 2 members")
-        self.kappa = 1.0 + (self.alpha / (self.members - 1) if self.members > 1 else 0.0)
+        super().__init__(members, alpha)
         self.sharded = comm.get_size("spatial") > 1
-        if self.sharded:
-            from .distributed import DistributedRealSHT
-            self.sht = DistributedRealSHT(*img_shape, grid=grid).float()
-        else:
-            from .sht import RealSHT
-            self.sht = RealSHT(*img_shape, grid=grid).float()
+        self.sht = real_sht(img_shape, grid)
         if degree_weights is None:
             degree_weights = torch.ones(self.sht.lmax, dtype=torch.float64)
         degree_weights = torch.as_tensor(degree_weights, dtype=torch.float64).reshape(-1)
@@ -260,19 +247,6 @@ class EnsembleSpectralCRPSLoss(nn.Module):
         want = (self.sht.nlat_local, self.sht.nlon_local) if self.sharded else (self.sht.nlat, self.sht.nlon)
         if (H, W) != want:
             raise ValueError(f"EnsembleSpectralCRPSLoss: expected [..., {want[0]}, {want[1]}], got {tuple(tar.shape)}")
-        prd, tar = ops._lowp(prd), ops._lowp(tar)
-        if self.sharded:
-            cp = self.sht.forward_packed(prd.reshape(B * self.members, C, H, W).contiguous())
-            ct = self.sht.forward_packed(tar.contiguous())
-            return self.sums_from_spectrum(cp, ct, B, self.sht.l_off, self.sht.m_off)
-        cp = self.sht.forward_packed(prd.reshape(-1, H, W).contiguous())
-        ct = self.sht.forward_packed(tar.reshape(-1, H, W).contiguous())
-        return self.sums_from_spectrum(cp, ct, B)
-
-    def from_sums(self, sums, chw):
-        """The loss (fp32) from the sums of the whole spectrum."""
-        s0, s1 = sums.unbind(-1)
-        return torch.sum(chw * (s0 - (0.5 * self.kappa) * s1)).float()
-
-    def forward(self, prd, tar, chw):
-        return self.from_sums(self.sums(prd, tar), chw)
+        cp = self.sht.forward_packed_fields(ops._lowp(prd).reshape(B * self.members, C, H, W))[0]
+        ct, l_off, m_off = self.sht.forward_packed_fields(ops._lowp(tar))
+        return self.sums_from_spectrum(cp, ct, B, l_off, m_off)

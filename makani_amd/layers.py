@@ -933,6 +933,10 @@ class RealFFT2(_PlanarFFT2Base):
         xf = ops.rfft(x3, self.twiddles, self.mmax, True, scale=1.0 / math.sqrt(self.nlon))
         return ops.lat_dft(xf, self.dft_table, self.lmax)
 
+    def forward_packed_fields(self, x4):
+        """``RealSHT.forward_packed_fields`` for the planar spectrum: x4 [B, C, nlat, nlon] -> ``(spectrum, 0, 0)``."""
+        return self.forward_packed(x4.reshape(-1, *x4.shape[-2:]).contiguous()), 0, 0
+
     def _forward_torch(self, x):
         y = torch.fft.rfft2(x, s=(self.nlat, self.nlon), dim=(-2, -1), norm="ortho")
         if self.truncate:

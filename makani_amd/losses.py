@@ -31,7 +31,7 @@ import torch
 from torch import nn
 
 from . import comm, ops
-from .distributed import compute_split_shapes
+from .distributed import compute_split_shapes, real_sht, shard_span
 from .mappings import gather_from_parallel_region, reduce_from_parallel_region
 
 
@@ -74,6 +74,12 @@ class GridQuadrature(nn.Module):
         H, W = quad_weight.shape
         self.register_buffer("quad_weight", quad_weight.reshape(1, 1, H, W))
 
+    @property
+    def row_weights(self):
+        """``[H]``: the weight of each latitude row.  Every rule tiles one column over the longitudes, so the weights do not vary
+        along a row and the streaming passes read one per row (a view of ``quad_weight``: nothing is derived again)."""
+        return self.quad_weight[0, 0, :, 0]
+
     def forward(self, x):
         return torch.sum(x * self.quad_weight, dim=(-2, -1))
 
@@ -91,8 +97,8 @@ class GeometricLpLoss(nn.Module):
         self.quadrature = GridQuadrature(quadrature_rule, img_shape=img_shape, crop_shape=crop_shape, crop_offset=crop_offset,
                                          normalize=True, pole_mask=pole_mask)
         self.uniform_chw = None     # set by the owner of the channel weights when they are all equal (see _fused_abs_sq_l2)
-        # the weights do not vary along a latitude row: one per row, as built (CPU float64 path) and in fp32 (kernels)
-        wrow = self.quadrature.quad_weight[0, 0, :, 0].contiguous()
+        # one weight per row, as built (CPU float64 path) and in fp32 (kernels)
+        wrow = self.quadrature.row_weights.contiguous()
         self.register_buffer("wrow", wrow, persistent=False)
         self.register_buffer("wrow32", wrow.float(), persistent=False)
 
@@ -184,12 +190,7 @@ class GeometricH1Loss(nn.Module):
         self.reduction, self.size_average = reduction, size_average
         self.absolute, self.squared, self.alpha = absolute, squared, alpha
         self.sharded = comm.get_size("spatial") > 1
-        if self.sharded:
-            from .distributed import DistributedRealSHT
-            self.sht = DistributedRealSHT(*img_shape, grid="equiangular").float()
-        else:
-            from .sht import RealSHT
-            self.sht = RealSHT(*img_shape, grid="equiangular").float()
+        self.sht = real_sht(img_shape, "equiangular")
         h1_weights = torch.arange(self.sht.lmax).float()
         self.register_buffer("h1_weights", h1_weights * (h1_weights + 1))
 
@@ -208,15 +209,12 @@ class GeometricH1Loss(nn.Module):
         n = x.size()[0]
         if x.is_cuda:
             x = ops._lowp(x)
-            nlat, nlon = x.shape[-2:]
+            if not self.sharded and tuple(x.shape[-2:]) != (self.sht.nlat, self.sht.nlon):
+                raise ValueError(f"expected [..., {self.sht.nlat}, {self.sht.nlon}], got {tuple(x.shape)}")
+            c, l_off, m_off = self.sht.forward_packed_fields(x.reshape(n, -1, *x.shape[-2:]))
+            sums = self.norms_from_spectrum(c, n, l_off, m_off)
             if self.sharded:
-                c = self.sht.forward_packed(x.reshape(n, -1, nlat, nlon).contiguous())
-                sums = self.norms_from_spectrum(c, n, self.sht.l_off, self.sht.m_off)
                 sums = reduce_from_parallel_region(sums, "spatial")
-            else:
-                if nlat != self.sht.nlat or nlon != self.sht.nlon:
-                    raise ValueError(f"expected [..., {self.sht.nlat}, {self.sht.nlon}], got {tuple(x.shape)}")
-                sums = self.norms_from_spectrum(self.sht.forward_packed(x.reshape(-1, nlat, nlon).contiguous()), n)
             return sums[:, 0], sums[:, 1]
         c = torch.view_as_real(self.sht(x))
         c = c[..., 0] ** 2 + c[..., 1] ** 2
@@ -297,7 +295,8 @@ class LossHandler(nn.Module):
         self.register_buffer("channel_weights", channel_weights)
         rule = "legendre-gauss" if params.model_grid_type == "legendre_gauss" else "naive"
         common = dict(absolute=absolute, pole_mask=pole_mask)
-        if "crps" in loss_type:
+        self.crps = "crps" in loss_type
+        if self.crps:
             # the one loss with E predictions per target: prd [B * E, C', H, W] (member fastest) against tar [B, C', H, W]
             from .ensemble import EnsembleCRPSLoss          # ensemble.py imports this module
             if squared:
@@ -355,13 +354,15 @@ class LossHandler(nn.Module):
         cw_eval = channel_weights.reshape(-1)
         self._uniform = {True: float(cw_train[0]) if bool((cw_train == cw_train[0]).all()) else None,
                          False: float(cw_eval[0]) if bool((cw_eval == cw_eval[0]).all()) else None}
+        # the Lp and CRPS terms are formed from sums that add up over shards; the H1 loss transforms and reduces by itself
+        self.h1 = isinstance(self.loss_obj, GeometricH1Loss)
         self.do_gather_input = comm.get_size("spatial") > 1
         if self.do_gather_input:
             self.gather_shapes_h = compute_split_shapes(self.crop_shape[0], comm.get_size("h"))
             self.gather_shapes_w = compute_split_shapes(self.crop_shape[1], comm.get_size("w"))
-            # this rank's latitude rows of the cropped grid (a w shard holds whole rows' weights: nothing to slice)
-            h0 = sum(self.gather_shapes_h[:comm.get_rank("h")])
-            self.shard_rows = slice(h0, h0 + self.gather_shapes_h[comm.get_rank("h")])
+        # this rank's latitude rows of the cropped grid (a w shard holds whole rows' weights: nothing to slice)
+        h0, hs = shard_span(self.crop_shape[0], "h")
+        self.shard_rows = slice(h0, h0 + hs)
 
     def _gather_input(self, x):
         xh = gather_from_parallel_region(x, -2, self.gather_shapes_h, "h")
@@ -370,39 +371,35 @@ class LossHandler(nn.Module):
     def is_distributed(self):
         return False
 
-    def _spectral_crps(self, prd, tar, chw):
-        """The spectral CRPS term: sharded, the rank's shard is transformed by the loss's own distributed transform and the
-        ``[B, C', 2]`` partial sums of its degrees and orders are all-reduced once; no field or spectrum is gathered."""
-        sums = self.spectral_obj.sums(prd, tar)
+    def _from_shard(self, obj, prd, tar, chw, *rows):
+        """``obj``'s term from this rank's shard: its sums (over ``rows`` of the latitude weights, where it takes them), which add
+        up over shards, ONE all-reduce of them over ``"spatial"`` (its gradient is the identity), the loss.  Nothing is gathered."""
+        sums = obj.sums(prd, tar, *rows)
         if self.do_gather_input:
             sums = reduce_from_parallel_region(sums, "spatial")
-        return self.spectral_obj.from_sums(sums, chw)
+        return obj.from_sums(sums, chw)
 
     def forward(self, prd, tar, inp=None):
         chw = self.channel_weights
         chw = (chw * self.multistep_weight).reshape(1, -1) if self.training else chw.reshape(1, -1)
-        if "crps" in self.loss_type.split():
+        if self.crps:
             if self.crps_spectral:
-                return self._spectral_crps(prd, tar, chw)
-            if not self.do_gather_input:
-                loss = self.loss_obj(prd, tar, chw)
-            else:
-                sums = self.loss_obj.sums(prd, tar, self.shard_rows)      # this rank's rows; [B, C', 2] add up, no field is gathered
-                loss = self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
+                return self._from_shard(self.spectral_obj, prd, tar, chw)
+            loss = self._from_shard(self.loss_obj, prd, tar, chw, self.shard_rows)
             if self.crps_combined:
-                loss = loss + self.crps_spectral_weight * self._spectral_crps(prd, tar, chw)
+                loss = loss + self.crps_spectral_weight * self._from_shard(self.spectral_obj, prd, tar, chw)
             return loss
-        if self.do_gather_input:
-            if isinstance(self.loss_obj, GeometricLpLoss) and self.loss_obj.has_sums(prd, tar):
-                sums = self.loss_obj.sums(prd, tar, self.shard_rows)
-                return self.loss_obj.from_sums(reduce_from_parallel_region(sums, "spatial"), chw)
-            if isinstance(self.loss_obj, GeometricH1Loss) and prd.is_cuda and tar.is_cuda:
-                return self.loss_obj(prd, tar)      # transforms its own shard, all-reduces [B, 2] sums (no mask: see below)
-            prd, tar = self._gather_input(prd), self._gather_input(tar)
-        if isinstance(self.loss_obj, GeometricLpLoss):
-            self.loss_obj.uniform_chw = self._uniform[bool(self.training)]
-        if isinstance(self.loss_obj, GeometricH1Loss):
+        if self.h1:
             # the H1 loss reduces over channels itself ([B] norms): its ``mask`` is per SAMPLE, the per-channel weights of
-            # the Lp family do not apply (losses.py:331-345); passing them broadcast only for B == 1 or B == C
+            # the Lp family do not apply (losses.py:331-345); passing them broadcast only for B == 1 or B == C.  Sharded, it
+            # transforms its own shard and all-reduces [B, 2] sums; the transform has no CPU path, so CPU shards are gathered
+            if self.do_gather_input and not (prd.is_cuda and tar.is_cuda):
+                prd, tar = self._gather_input(prd), self._gather_input(tar)
             return self.loss_obj(prd, tar)
+        if self.do_gather_input:
+            if self.loss_obj.has_sums(prd, tar):
+                return self._from_shard(self.loss_obj, prd, tar, chw, self.shard_rows)
+            prd, tar = self._gather_input(prd), self._gather_input(tar)
+        # unsharded, the loss object's own forward: the fused single pass where it applies (other bits than ``from_sums``)
+        self.loss_obj.uniform_chw = self._uniform[bool(self.training)]
         return self.loss_obj(prd, tar, chw)

@@ -22,7 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import comm, ops
-from .distributed import compute_split_shapes
+from .distributed import all_reduce_spatial, compute_split_shapes, shard_span
 from .mappings import gather_from_parallel_region
 from .metrics import GeometricACC, GeometricL1, GeometricRMSE, Quadrature
 
@@ -83,20 +83,13 @@ class MetricsHandler:
         self.acc_eps = self.acc_handle.eps
 
         # this rank's shard of the latitude weights and of the climatology ([C, H, W] over the crop)
-        wrow = self.rmse_handle.quadrature.quad_weight[0, 0, :, 0]
-        clim = clim.to(self.device, dtype=torch.float32)
-        self.spatial_size = comm.get_size("spatial")
-        self.do_gather_input = self.spatial_size > 1
+        (h0, hs), (w0, ws) = shard_span(self.crop_shape[0], "h"), shard_span(self.crop_shape[1], "w")
+        self.wrow = self.rmse_handle.quadrature.row_weights[h0:h0 + hs].float().contiguous()
+        self.clim = clim.to(self.device, dtype=torch.float32)[..., h0:h0 + hs, w0:w0 + ws].contiguous()
+        self.do_gather_input = comm.get_size("spatial") > 1
         if self.do_gather_input:
             self.gather_shapes_h = compute_split_shapes(self.crop_shape[0], comm.get_size("h"))
             self.gather_shapes_w = compute_split_shapes(self.crop_shape[1], comm.get_size("w"))
-            h0 = sum(self.gather_shapes_h[:comm.get_rank("h")])
-            w0 = sum(self.gather_shapes_w[:comm.get_rank("w")])
-            hs, ws = self.gather_shapes_h[comm.get_rank("h")], self.gather_shapes_w[comm.get_rank("w")]
-            wrow = wrow[h0:h0 + hs]
-            clim = clim[..., h0:h0 + hs, w0:w0 + ws]
-        self.wrow = wrow.float().contiguous()
-        self.clim = clim.contiguous()
 
     def _gather_input(self, x):
         """gather the spatial shards of x over h, then w"""
@@ -131,10 +124,7 @@ class MetricsHandler:
 
     def _global_sums(self, prediction, target):
         """[B, C, 5] float64 sums over the whole (cropped) field: this rank's shard, all-reduced over the spatial group."""
-        sums = ops.geo_metric_sums(prediction, target, self.clim, self.wrow)
-        if self.spatial_size > 1:
-            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=comm.get_group("spatial"))
-        return sums
+        return all_reduce_spatial(ops.geo_metric_sums(prediction, target, self.clim, self.wrow))
 
     def update(self, prediction, target, loss, idt):
         """accumulate one autoregressive step; no host synchronisation"""

@@ -35,16 +35,12 @@ class _GeometricMetric(torch.nn.Module):
         self.channel_reduction = channel_reduction
         self.batch_reduction = batch_reduction
 
-    def _wrow(self):
-        """The weight of each latitude row (the weights do not vary along a row)."""
-        return self.quadrature.quad_weight[0, 0, :, 0]
-
     def _use_kernel(self, x, y):
         need_grad = torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)
         return x.is_cuda and y.is_cuda and x.dim() == 4 and not need_grad
 
     def _sums(self, x, y):
-        return ops.geo_metric_sums(x, y, None, self._wrow())
+        return ops.geo_metric_sums(x, y, None, self.quadrature.row_weights)
 
     def _out_dtype(self, x, y):
         return torch.promote_types(torch.promote_types(x.dtype, y.dtype), self.quadrature.quad_weight.dtype)

@@ -1994,17 +1994,24 @@ def geo_lp_sums(prd, tar, wrow, p):
 # ----------------------------------------------------------------------------
 # per-degree power of a packed spectrum (csrc/specnorm.hip)
 # ----------------------------------------------------------------------------
+def _stored_triangle(L, M, l_off, m_off, device):
+    """Of an ``[L, M]`` shard of a packed spectrum from degree ``l_off`` and order ``m_off`` on: ``stored`` (bool), the entries
+    with ``l_off + l >= m_off + m``, and ``w`` (float64), the order weights there (1 for ``m = 0``, 2 for ``m > 0``), zero elsewhere."""
+    l = torch.arange(L, device=device).reshape(L, 1) + l_off
+    m = torch.arange(M, device=device).reshape(1, M) + m_off
+    stored = l >= m
+    w = torch.where(m == 0, 1.0, 2.0).to(torch.float64).expand(L, M)
+    return stored, torch.where(stored, w, torch.zeros_like(w))
+
+
 def _degree_power_torch(c, l_off, m_off):
     """The degree sums in torch float64 on the tensor's device, differentiable by ordinary autograd; the rows with
     ``l_off + l < m_off + m`` are masked out before they are squared (they may hold anything, NaN included)."""
     L, M, _ = c.shape
-    l = torch.arange(L, device=c.device).reshape(L, 1) + l_off
-    m = torch.arange(M, device=c.device).reshape(1, M) + m_off
-    w = torch.where(m == 0, 1.0, 2.0).to(torch.float64).expand(L, M)
-    w = torch.where(l >= m, w, torch.zeros_like(w)).unsqueeze(-1)
+    stored, w = _stored_triangle(L, M, l_off, m_off, c.device)
     ri = torch.view_as_real(c).to(torch.float64)
-    ri = torch.where((w > 0).unsqueeze(-1), ri, torch.zeros_like(ri))
-    return (w * (ri[..., 0] ** 2 + ri[..., 1] ** 2)).sum(dim=1).t()
+    ri = torch.where(stored.reshape(L, M, 1, 1), ri, torch.zeros_like(ri))
+    return (w.unsqueeze(-1) * (ri[..., 0] ** 2 + ri[..., 1] ** 2)).sum(dim=1).t()
 
 
 class _DegreePower(torch.autograd.Function):
@@ -2562,6 +2569,41 @@ def _ensemble_sums_torch(ens, tar, wrow, ranks=None, skipped=None):
     return out
 
 
+def _ensemble_operands(op, ens, tar, wrow):
+    """The checks ``ensemble_sums`` and ``ensemble_crps_sums`` share on an ensemble, its target ``[B, C, H, W]`` and the row
+    weights, under the name ``op``; returns the ensemble as ``[B, E, C, H, W]`` (a ``[B * E, C, H, W]`` one viewed, member fastest)."""
+    if tar.dim() != 4:
+        raise ValueError(f"{op}: the target must be [B, C, H, W], got {tuple(tar.shape)}")
+    B, C, H, W = tar.shape
+    if ens.dim() == 4 and B >= 1 and ens.shape[0] % B == 0 and tuple(ens.shape[1:]) == (C, H, W):
+        ens = ens.view(B, ens.shape[0] // B, C, H, W) if ens.is_contiguous() else ens.reshape(B, ens.shape[0] // B, C, H, W)
+    if ens.dim() != 5 or ens.shape[0] != B or tuple(ens.shape[2:]) != (C, H, W) or ens.shape[1] < 1 or min(B, C, H, W) < 1:
+        raise ValueError(f"{op}: ensemble {tuple(ens.shape)} must be [B, E, C, H, W] or [B * E, C, H, W] for a target "
+                         f"{tuple(tar.shape)}")
+    if tar.device != ens.device or wrow.device != ens.device:
+        raise ValueError(f"{op}: ensemble on {ens.device}, target on {tar.device}, wrow on {wrow.device}")
+    if wrow.numel() != H:
+        raise ValueError(f"{op}: wrow has {wrow.numel()} weights for {H} latitude rows")
+    return ens
+
+
+def _ens_sums_launch(ens, tar, wrow, ranks=None, skipped=None):
+    """One ``mk_ens_sums`` pass over fp32 / bf16 members ``[B, E, C, H, W]``, ``tar`` and ``wrow`` fp32 and contiguous: the
+    ``[B, C, 4]`` float64 sums, and the members and the batch stride the kernel read them with (``mk_ens_crps_bwd`` reads them
+    the same way).  Every member's ``[C, H, W]`` block must be contiguous -- else the ensemble is copied --; the batch and member
+    strides are free."""
+    B, E, C, H, W = ens.shape
+    if ens.stride()[2:] != (H * W, W, 1) or min(ens.stride(0), ens.stride(1)) < C * H * W:
+        ens = ens.contiguous()
+    lib = _lib.load()
+    ws = torch.empty(lib.mk_ens_workspace(B, C, H), dtype=torch.float64, device=ens.device)
+    out = torch.empty(B, C, 4, dtype=torch.float64, device=ens.device)
+    bstride = ens.stride(0) if B > 1 else E * ens.stride(1)      # a stride of a size-1 axis means nothing
+    _lib.check(lib.mk_ens_sums(ens.data_ptr(), _pw_dtype(ens), bstride, ens.stride(1), tar.data_ptr(), wrow.data_ptr(),
+                               ws.data_ptr(), out.data_ptr(), _ptr(ranks), _ptr(skipped), B, E, C, H, W, _stream()), "mk_ens_sums")
+    return out, ens, bstride
+
+
 @torch.no_grad()
 def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
     """Latitude-weighted integrals of the ensemble scores, ``[B, C, 4]`` float64 in the order of ``ENSEMBLE_SUMS``, of an
@@ -2583,20 +2625,8 @@ def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
     the same bits every run, capturable).  CPU tensors, ``E = 1``, more members and ``MK_ENSEMBLE=torch`` take
     ``_ensemble_sums_torch``.  No gradient flows through this op."""
     hip = _hip_or_torch("MK_ENSEMBLE", ENSEMBLE_DEFAULT)
-    if tar.dim() != 4:
-        raise ValueError(f"ensemble_sums: the target must be [B, C, H, W], got {tuple(tar.shape)}")
-    B, C, H, W = tar.shape
-    if ens.dim() == 4 and B >= 1 and ens.shape[0] % B == 0 and tuple(ens.shape[1:]) == (C, H, W):
-        ens = ens.view(B, ens.shape[0] // B, C, H, W) if ens.is_contiguous() else ens.reshape(B, ens.shape[0] // B, C, H, W)
-    if ens.dim() != 5 or ens.shape[0] != B or tuple(ens.shape[2:]) != (C, H, W) or ens.shape[1] < 1 or min(B, C, H, W) < 1:
-        raise ValueError(f"ensemble_sums: ensemble {tuple(ens.shape)} must be [B, E, C, H, W] or [B * E, C, H, W] for a target "
-                         f"{tuple(tar.shape)}")
-    E = ens.shape[1]
-    dev = ens.device
-    if tar.device != dev or wrow.device != dev:
-        raise ValueError(f"ensemble_sums: ensemble on {dev}, target on {tar.device}, wrow on {wrow.device}")
-    if wrow.numel() != H:
-        raise ValueError(f"ensemble_sums: wrow has {wrow.numel()} weights for {H} latitude rows")
+    ens = _ensemble_operands("ensemble_sums", ens, tar, wrow)
+    E, C, dev = ens.shape[1], ens.shape[2], ens.device
     for name, t, shape in (("ranks", ranks, (C, E + 1)), ("skipped", skipped, (C,))):
         if t is not None and (tuple(t.shape) != shape or t.dtype != torch.int64 or not t.is_contiguous() or t.device != dev):
             raise ValueError(f"ensemble_sums: {name} must be a contiguous int64 {list(shape)} on {dev}, got {t.dtype} "
@@ -2604,18 +2634,7 @@ def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
     ens, tar = ens.detach(), tar.detach()
     if not (hip and ens.is_cuda and 2 <= E <= ENSEMBLE_MAX_MEMBERS):
         return _ensemble_sums_torch(ens, tar, wrow, ranks, skipped)
-    ens = _lowp(ens)
-    if ens.stride()[2:] != (H * W, W, 1) or min(ens.stride(0), ens.stride(1)) < C * H * W:
-        ens = ens.contiguous()             # every member's [C, H, W] block contiguous; the batch and member strides are free
-    tar = tar.float().contiguous()
-    wrow = wrow.float().contiguous()
-    lib = _lib.load()
-    ws = torch.empty(lib.mk_ens_workspace(B, C, H), dtype=torch.float64, device=dev)
-    out = torch.empty(B, C, 4, dtype=torch.float64, device=dev)
-    bstride = ens.stride(0) if B > 1 else E * ens.stride(1)      # a stride of a size-1 axis means nothing
-    _lib.check(lib.mk_ens_sums(ens.data_ptr(), _pw_dtype(ens), bstride, ens.stride(1), tar.data_ptr(), wrow.data_ptr(),
-                               ws.data_ptr(), out.data_ptr(), _ptr(ranks), _ptr(skipped), B, E, C, H, W, _stream()), "mk_ens_sums")
-    return out
+    return _ens_sums_launch(_lowp(ens), tar.float().contiguous(), wrow.float().contiguous(), ranks, skipped)[0]
 
 
 # ----------------------------------------------------------------------------
@@ -2623,6 +2642,21 @@ def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
 # ----------------------------------------------------------------------------
 ENS_LOSS_DEFAULT = "hip"        # MK_ENS_LOSS: hip | torch.  No row of tools/ens_loss_bench.py is slower than torch
 ENS_LOSS_MAX_MEMBERS = 16       # what mk_ens_crps_bwd takes: a thread compares all pairs of its point's members in registers
+
+
+def _walk_chunks(fn, pieces, n, step, needs_grad, dim):
+    """``fn(*pieces(s))`` for the slices ``s`` of ``step`` out of ``n``, concatenated along ``dim``.  Under autograd, with more than
+    one slice, a slice is recomputed in the backward instead of kept (``torch.utils.checkpoint``)."""
+    keep = torch.is_grad_enabled() and needs_grad
+    out = []
+    for i0 in range(0, n, step):
+        args = pieces(slice(i0, i0 + step))
+        if keep and step < n:
+            from torch.utils.checkpoint import checkpoint
+            out.append(checkpoint(fn, *args, use_reentrant=False))
+        else:
+            out.append(fn(*args))
+    return torch.cat(out, dim=dim)
 
 
 def _ens_crps_chunk(x, y, w):
@@ -2662,16 +2696,7 @@ def _ensemble_crps_sums_torch(ens, tar, wrow):
     B, E, C, H, W = ens.shape
     w = wrow.detach().double().reshape(1, 1, H, 1)
     step = max(1, _ENS_TORCH_CHUNK // max(1, B * E * E * H * W))
-    keep = torch.is_grad_enabled() and (ens.requires_grad or tar.requires_grad)
-    out = []
-    for c0 in range(0, C, step):
-        x, y = ens[:, :, c0:c0 + step], tar[:, c0:c0 + step]
-        if keep and step < C:
-            from torch.utils.checkpoint import checkpoint
-            out.append(checkpoint(_ens_crps_chunk, x, y, w, use_reentrant=False))
-        else:
-            out.append(_ens_crps_chunk(x, y, w))
-    return torch.cat(out, dim=1)
+    return _walk_chunks(_ens_crps_chunk, lambda s: (ens[:, :, s], tar[:, s], w), C, step, ens.requires_grad or tar.requires_grad, 1)
 
 
 class _EnsCrpsSums(torch.autograd.Function):
@@ -2679,13 +2704,9 @@ class _EnsCrpsSums(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ens, tar, wrow):
-        B, E, C, H, W = ens.shape
-        lib = _lib.load()
-        ws = torch.empty(lib.mk_ens_workspace(B, C, H), dtype=torch.float64, device=ens.device)
-        out = torch.empty(B, C, 4, dtype=torch.float64, device=ens.device)
-        ctx.bstride = ens.stride(0) if B > 1 else E * ens.stride(1)      # a stride of a size-1 axis means nothing
-        _lib.check(lib.mk_ens_sums(ens.data_ptr(), _pw_dtype(ens), ctx.bstride, ens.stride(1), tar.data_ptr(), wrow.data_ptr(),
-                                   ws.data_ptr(), out.data_ptr(), None, None, B, E, C, H, W, _stream()), "mk_ens_sums")
+        out, ens, ctx.bstride = _ens_sums_launch(ens, tar, wrow)
+        # ``ens`` is what the kernel read: the argument, or its contiguous copy where the strides did not fit (made in here, not
+        # by the caller; the gradient is contiguous with the argument's shape either way)
         ctx.save_for_backward(ens, tar, wrow)
         ctx.mark_non_differentiable(out)
         return out[..., :2].contiguous(), out
@@ -2722,26 +2743,11 @@ def ensemble_crps_sums(ens, tar, wrow, with_sums=False):
     ``E = 1``, more members, other dtypes, a target that requires a gradient and ``MK_ENS_LOSS=torch`` take
     ``_ensemble_crps_sums_torch``."""
     hip = _hip_or_torch("MK_ENS_LOSS", ENS_LOSS_DEFAULT)
-    if tar.dim() != 4:
-        raise ValueError(f"ensemble_crps_sums: the target must be [B, C, H, W], got {tuple(tar.shape)}")
-    B, C, H, W = tar.shape
-    if ens.dim() == 4 and B >= 1 and ens.shape[0] % B == 0 and tuple(ens.shape[1:]) == (C, H, W):
-        ens = ens.view(B, ens.shape[0] // B, C, H, W) if ens.is_contiguous() else ens.reshape(B, ens.shape[0] // B, C, H, W)
-    if ens.dim() != 5 or ens.shape[0] != B or tuple(ens.shape[2:]) != (C, H, W) or ens.shape[1] < 1 or min(B, C, H, W) < 1:
-        raise ValueError(f"ensemble_crps_sums: ensemble {tuple(ens.shape)} must be [B, E, C, H, W] or [B * E, C, H, W] for a target "
-                         f"{tuple(tar.shape)}")
-    E = ens.shape[1]
-    dev = ens.device
-    if tar.device != dev or wrow.device != dev:
-        raise ValueError(f"ensemble_crps_sums: ensemble on {dev}, target on {tar.device}, wrow on {wrow.device}")
-    if wrow.numel() != H:
-        raise ValueError(f"ensemble_crps_sums: wrow has {wrow.numel()} weights for {H} latitude rows")
-    if not (hip and ens.is_cuda and 2 <= E <= ENS_LOSS_MAX_MEMBERS and ens.dtype in _LOWP and not tar.requires_grad):
+    ens = _ensemble_operands("ensemble_crps_sums", ens, tar, wrow)
+    if not (hip and ens.is_cuda and 2 <= ens.shape[1] <= ENS_LOSS_MAX_MEMBERS and ens.dtype in _LOWP and not tar.requires_grad):
         out = _ensemble_crps_sums_torch(ens, tar, wrow)
         s, sums = out[..., :2], out.detach()
     else:
-        if ens.stride()[2:] != (H * W, W, 1) or min(ens.stride(0), ens.stride(1)) < C * H * W:
-            ens = ens.contiguous()         # every member's [C, H, W] block contiguous; the batch and member strides are free
         s, sums = _EnsCrpsSums.apply(ens, tar.detach().float().contiguous(), wrow.detach().float().contiguous())
     return (s, sums) if with_sums else s
 
@@ -2784,25 +2790,14 @@ def _spectral_crps_sums_torch(cp, ct, members, l_off=0, m_off=0, batch=1):
     L, M, BC = ct.shape
     E, B = int(members), int(batch)
     C = BC // B
-    l = torch.arange(L, device=cp.device).reshape(L, 1) + l_off
-    m = torch.arange(M, device=cp.device).reshape(1, M) + m_off
-    stored = l >= m
-    w = torch.where(stored, torch.where(m == 0, 1.0, 2.0).to(torch.float64).expand(L, M), torch.zeros((), dtype=torch.float64, device=cp.device))
+    stored, w = _stored_triangle(L, M, l_off, m_off, cp.device)
     x = torch.view_as_real(cp).reshape(L, M, B, E, C, 2)
     y = torch.view_as_real(ct).reshape(L, M, B, C, 2)
     x = torch.where(stored.reshape(L, M, 1, 1, 1, 1), x, torch.zeros_like(x))
     y = torch.where(stored.reshape(L, M, 1, 1, 1), y, torch.zeros_like(y))
     step = max(1, _ENS_TORCH_CHUNK // max(1, 2 * M * B * E * E * C))
-    keep = torch.is_grad_enabled() and (cp.requires_grad or ct.requires_grad)
-    out = []
-    for l0 in range(0, L, step):
-        args = (x[l0:l0 + step], y[l0:l0 + step], w[l0:l0 + step])
-        if keep and step < L:
-            from torch.utils.checkpoint import checkpoint
-            out.append(checkpoint(_spec_crps_chunk, *args, use_reentrant=False))
-        else:
-            out.append(_spec_crps_chunk(*args))
-    return torch.cat(out, dim=0).permute(1, 2, 0, 3).reshape(BC, L, 2)
+    out = _walk_chunks(_spec_crps_chunk, lambda s: (x[s], y[s], w[s]), L, step, cp.requires_grad or ct.requires_grad, 0)
+    return out.permute(1, 2, 0, 3).reshape(BC, L, 2)
 
 
 class _SpecCrpsSums(torch.autograd.Function):

@@ -63,6 +63,12 @@ class RealSHT(_SHTBase):
         xf = ops.rfft(x3, self.twiddles, self.mmax, km)
         return ops.legendre_fwd(xf, self.weights, self.lmax, 0, km)
 
+    def forward_packed_fields(self, x4):
+        """x4 [B, C, nlat, nlon] (fp32 or bf16) -> ``(spectrum [lmax, mmax, B*C], l_off, m_off)``, the call the sharded and the
+        planar transform take too; the offsets are those of the spectrum's first degree and order: ``0, 0`` here.  A
+        contiguous x4 reaches ``forward_packed`` as a view."""
+        return self.forward_packed(x4.reshape(-1, *x4.shape[-2:]).contiguous()), 0, 0
+
     def forward(self, x):
         if x.shape[-2] != self.nlat or x.shape[-1] != self.nlon:
             raise ValueError(f"expected [..., {self.nlat}, {self.nlon}], got {tuple(x.shape)}")

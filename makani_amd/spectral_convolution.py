@@ -150,11 +150,7 @@ class SpectralConv(nn.Module):
         # planar spectrum: every (l, m) entry is data -- a degree offset >= mmax switches the kernel's triangle off
         l_off = self.modes_lon if self._planar else self.l_off
         xin = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
-        xin = xin.contiguous()
-        if isinstance(ft, DistributedRealSHT):
-            c = ft.forward_packed(xin)
-        else:
-            c = ft.forward_packed(xin.view(B * C, xin.shape[2], xin.shape[3]))
+        c = ft.forward_packed_fields(xin.contiguous())[0]
         if premix is not None:
             # the bias-free convolution in front of this layer commutes with the analysis: sht(W x) = W sht(x)
             c = ops.spec_mix(c, premix.weight, B, self.l_off, self.m_off)
@@ -458,11 +454,7 @@ class SpectralAttention(nn.Module):
         # planar spectrum: every (l, m) entry is data -- a degree offset >= mmax switches the kernels' triangle off
         l_off = self.modes_lon if self._planar else self.l_off
         xin = x if x.dtype in (torch.float32, torch.bfloat16) else x.float()
-        xin = xin.contiguous()
-        if isinstance(ft, DistributedRealSHT):
-            c = ft.forward_packed(xin)
-        else:
-            c = ft.forward_packed(xin.view(B * C, xin.shape[2], xin.shape[3]))
+        c = ft.forward_packed_fields(xin.contiguous())[0]
         odt = dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32
         residual = x
         if self.scale_residual:

@@ -50,7 +50,7 @@ import torch
 import torch.distributed as dist
 
 from . import comm, ops
-from .distributed import compute_split_shapes
+from .distributed import shard_span
 from .losses import GridQuadrature
 
 FILES = ("global_means", "global_stds", "mins", "maxs", "time_means", "time_diff_means", "time_diff_stds")
@@ -87,15 +87,9 @@ class DatasetStats:
         self.C = int(num_channels)
         self.img_shape = (int(img_shape[0]), int(img_shape[1]))
         self.carry = bool(carry)
-        wrow = GridQuadrature(quadrature_rule, self.img_shape, normalize=True).quad_weight[0, 0, :, 0]
-        self.H, self.W = self.img_shape
-        if comm.get_size("spatial") > 1:
-            hs = compute_split_shapes(self.H, comm.get_size("h"))
-            ws = compute_split_shapes(self.W, comm.get_size("w"))
-            h0 = sum(hs[:comm.get_rank("h")])
-            self.H, self.W = hs[comm.get_rank("h")], ws[comm.get_rank("w")]
-            wrow = wrow[h0:h0 + self.H]
-        self.wrow = wrow.float().contiguous()
+        (h0, self.H), (_, self.W) = shard_span(self.img_shape[0], "h"), shard_span(self.img_shape[1], "w")
+        wrow = GridQuadrature(quadrature_rule, self.img_shape, normalize=True).row_weights
+        self.wrow = wrow[h0:h0 + self.H].float().contiguous()
         self.sw = float(self.wrow.double().sum()) * self.W            # sum of the weights over one sample (this shard)
         self.wind_pairs = None
         if wind_pairs is not None and len(wind_pairs[0]) > 0:

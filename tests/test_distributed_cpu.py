@@ -533,3 +533,25 @@ def test_ddp_wrapper_model_parallel():
 @pytest.mark.parametrize("h", [4, 8])
 def test_production_grid_shards(h):
     _run(h, h, 1, "sht721")
+
+
+@pytest.mark.parametrize("ranks", [1, 2, 3, 4, 8])
+@pytest.mark.parametrize("size", [1, 5, 33, 60, 721])
+def test_shard_span_is_this_ranks_entry_of_the_split_shapes(size, ranks, monkeypatch):
+    """``shard_span`` for every rank of an axis, the comm sizes and ranks patched: the offset is the sum of the earlier
+    ``compute_split_shapes`` entries, the length this rank's entry, and the parts tile the axis.  The other axis has one rank
+    and gives ``(0, size)``."""
+    from makani_amd import comm
+    from makani_amd.distributed import compute_split_shapes, shard_span
+    shapes = compute_split_shapes(size, ranks)
+    assert len(shapes) == ranks and sum(shapes) == size
+    for axis, other in (("h", "w"), ("w", "h")):
+        end = 0
+        for rank in range(ranks):
+            monkeypatch.setattr(comm, "get_size", lambda name: ranks if name == axis else 1)
+            monkeypatch.setattr(comm, "get_rank", lambda name: rank if name == axis else 0)
+            off, length = shard_span(size, axis)
+            assert (off, length) == (sum(shapes[:rank]), shapes[rank]) and off == end
+            assert shard_span(size, other) == (0, size)
+            end = off + length
+        assert end == size

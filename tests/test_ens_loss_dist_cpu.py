@@ -13,7 +13,7 @@ import torch.multiprocessing as mp
 
 import ens_loss_checks as lc
 from test_lploss_cpu import make_params
-from test_lploss_dist_cpu import _free_port, _no_gather
+from test_lploss_dist_cpu import _free_port, _no_gather, count_reduces
 
 H, W, B, C, E = 33, 60, 2, 6, 3
 SPEC = "weighted ensemble crps"
@@ -39,6 +39,7 @@ def _worker(rank, world, port, q):
         from makani_amd.distributed import split_tensor_along_dim
         comm.init(model_parallel_sizes=[world, 1, 1, 1], backend="gloo")
         losses.gather_from_parallel_region = _no_gather
+        reduces = count_reduces(losses)
         prd, tar = _problem()
         hr = comm.get_rank("h")
         shard = lambda x: split_tensor_along_dim(x, -2, comm.get_size("h"))[hr].contiguous()
@@ -46,6 +47,7 @@ def _worker(rank, world, port, q):
         assert handler.do_gather_input
         x = shard(prd).clone().requires_grad_(True)
         loss = handler(x, shard(tar), None)
+        assert reduces == ["spatial"], reduces      # ONE all-reduce of the [B, C, 2] sums per forward (and no gather: it raises)
         loss.backward()
         dist.barrier()
         q.put((rank, (hr, float(loss.detach()), x.grad.clone(), handler.loss_obj.last_sums.clone())))

@@ -319,3 +319,26 @@ def test_sharded_h1_loss_equals_single_process_without_gather(dev, along_w):
             print(f"rank {r} ({i}, {j}) '{spec}': value {e_val:.3e}, gradient {e_grad:.3e}")
             assert grad.shape == gshard.shape
             assert e_val < 1e-5 and e_grad < 1e-5, (r, spec)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the four-dimensional transform call the losses and the spectral filters share
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("grid", ["equiangular", "legendre-gauss"])
+def test_forward_packed_fields_is_forward_packed_of_the_rows(dev, grid, dtype):
+    """``forward_packed_fields`` of ``[2, 3, 33, 64]`` fields holds the bits of ``forward_packed`` of the ``[6, 33, 64]`` rows with
+    the offsets ``(0, 0)``; a non-contiguous input gives the bits of its contiguous copy."""
+    from makani_amd.sht import RealSHT
+    H, W = 33, 64
+    sht = RealSHT(H, W, grid=grid).to(dev)
+    x = torch.randn(2, 3, H, W, generator=torch.Generator().manual_seed(5)).to(dev, dtype)
+    want = sht.forward_packed(x.reshape(-1, H, W))
+    got, l_off, m_off = sht.forward_packed_fields(x)
+    assert (l_off, m_off) == (0, 0) and got.dtype == torch.complex64 and tuple(got.shape) == (sht.lmax, sht.mmax, 6)
+    stored = _stored(tuple(got.shape), (0, 0)).to(dev)          # the Legendre kernels leave the rest unwritten
+    assert torch.equal(torch.view_as_real(got)[stored], torch.view_as_real(want)[stored])
+    strided = x.transpose(0, 1).contiguous().transpose(0, 1)
+    assert not strided.is_contiguous() and torch.equal(strided, x)
+    again = sht.forward_packed_fields(strided)[0]
+    assert torch.equal(torch.view_as_real(again)[stored], torch.view_as_real(want)[stored])

@@ -38,6 +38,19 @@ def _no_gather(*args, **kwargs):
     raise _Gathered()
 
 
+def count_reduces(losses):
+    """Wrap ``losses.reduce_from_parallel_region`` (what ``LossHandler`` all-reduces its sums with) so that every call appends
+    the name of its group to the list returned."""
+    calls, reduce = [], losses.reduce_from_parallel_region
+
+    def counted(t, name):
+        calls.append(name)
+        return reduce(t, name)
+
+    losses.reduce_from_parallel_region = counted
+    return calls
+
+
 def _worker(rank, world, port, hsize, wsize, q):
     try:
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
@@ -47,6 +60,7 @@ def _worker(rank, world, port, hsize, wsize, q):
         from makani_amd.distributed import split_tensor_along_dim
         comm.init(model_parallel_sizes=[hsize, wsize, 1, 1], backend="gloo")
         losses.gather_from_parallel_region = _no_gather
+        reduces = count_reduces(losses)
         where = (comm.get_rank("data"), comm.get_rank("h"), comm.get_rank("w"))
         prd, tar = _problem(where[0])
 
@@ -60,7 +74,9 @@ def _worker(rank, world, port, hsize, wsize, q):
             handler.train()
             assert handler.do_gather_input
             x = shard(prd).clone().requires_grad_(True)
+            del reduces[:]
             loss = handler(x, shard(tar), None)
+            assert reduces == ["spatial"], (spec, reduces)      # ONE all-reduce per forward (and no gather: it raises)
             loss.backward()
             out[spec] = (float(loss.detach()), x.grad.clone())
         # the H1 loss still gathers (before its transform, which has no CPU path)

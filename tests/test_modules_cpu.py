@@ -117,6 +117,22 @@ def test_grid_quadrature_against_oracle(rule, crop):
         assert abs(float(GridQuadrature(rule, shape).quad_weight.double().sum()) - 4 * math.pi) < 1e-5    # area of the sphere
 
 
+@pytest.mark.parametrize("rule", ["naive", "legendre-gauss", "clenshaw-curtiss"])
+@pytest.mark.parametrize("crop", [None, ((20, 48), (5, 8))])
+@pytest.mark.parametrize("pole", [0, 2])
+@pytest.mark.parametrize("normalize", [False, True])
+def test_row_weights_are_a_column_of_the_quadrature_weights(rule, crop, pole, normalize):
+    """``row_weights`` holds the bits of ``quad_weight[0, 0, :, 0]``, and every column of ``quad_weight`` holds them too: the
+    one fact the streaming passes rest on when they read one weight per latitude row."""
+    from makani_amd.losses import GridQuadrature
+    cs, co = crop if crop else (None, (0, 0))
+    q = GridQuadrature(rule, (33, 64), crop_shape=cs, crop_offset=co, normalize=normalize, pole_mask=pole)
+    rows = q.row_weights
+    assert rows.dtype == q.quad_weight.dtype and tuple(rows.shape) == (q.quad_weight.shape[2],)
+    assert torch.equal(rows, q.quad_weight[0, 0, :, 0])
+    assert torch.equal(rows.unsqueeze(1).expand_as(q.quad_weight[0, 0]), q.quad_weight[0, 0])
+
+
 @pytest.mark.parametrize("p,absolute,squared", [(2, False, False), (2, True, True), (2, True, False), (1, False, False),
                                                 (1, True, False), (2, False, True)])
 def test_geometric_lp_loss_against_oracle(p, absolute, squared):

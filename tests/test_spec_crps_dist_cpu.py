@@ -17,17 +17,19 @@ import torch.multiprocessing as mp
 import spec_crps_checks as sc
 from kernel_checks import row_rel
 from test_lploss_cpu import make_params
-from test_lploss_dist_cpu import _free_port, _no_gather
+from test_lploss_dist_cpu import _free_port, _no_gather, count_reduces
 
 L, M, B, E, C = 13, 9, 2, 3, 6
 DIMS = (L, M, B, E, C)
 H, W = L, 2 * (M - 1)
 SPEC = "weighted fair spectral ensemble crps"
+COMBINED = "weighted fair combined ensemble crps"
 
 
-def _params():
-    params = make_params(SPEC, H, W)
+def _params(spec=SPEC):
+    params = make_params(spec, H, W)
     params.ensemble_size = E
+    params.crps_spectral_weight = 0.25
     return params
 
 
@@ -57,6 +59,7 @@ def _worker(rank, world, port, hsize, wsize, q):
         from makani_amd import comm, losses
         comm.init(model_parallel_sizes=[hsize, wsize, 1, 1], backend="gloo")
         losses.gather_from_parallel_region = _no_gather
+        reduces = count_reduces(losses)
         handler = losses.LossHandler(_params()).train()
         sht = handler.spectral_obj.sht
         assert handler.do_gather_input and handler.spectral_obj.sharded and (sht.lmax, sht.mmax) == (L, M)
@@ -64,6 +67,12 @@ def _worker(rank, world, port, hsize, wsize, q):
         ls, ms = slice(sht.l_off, sht.l_off + sht.lmax_local), slice(sht.m_off, sht.m_off + sht.mmax_local)
         shard = cp[ls, ms].contiguous().requires_grad_(True)
         loss, grad, sums = _run_handler(handler, shard, ct[ls, ms].contiguous(), sht.nlat_local, sht.nlon_local)
+        assert reduces == ["spatial"], reduces              # the spectral term alone: ONE all-reduce per forward
+        # "combined": the grid term's all-reduce and the spectral term's, nothing else (and no gather: it raises)
+        del reduces[:]
+        both = losses.LossHandler(_params(COMBINED)).train()
+        _run_handler(both, shard.detach().clone().requires_grad_(True), ct[ls, ms].contiguous(), sht.nlat_local, sht.nlon_local)
+        assert reduces == ["spatial", "spatial"], reduces
         dist.barrier()
         q.put((rank, ((comm.get_rank("h"), comm.get_rank("w")), (sht.l_off, sht.m_off), tuple(shard.shape), float(loss), grad.clone(),
                       sums.clone(), handler.spectral_obj.last_degree_sums.clone())))
