@@ -707,6 +707,40 @@ int mk_ens_crps_bwd(const void* ens, int dtype, long long bstride, long long est
                     const double* gs, void* gens, long long gbstride, long long gestride, int B, int E, int C, int H, int W,
                     void* stream);
 
+/* Forecast products of an ensemble: K planes per sample and selected channel, out [B][K][Cs][H][W] (fp32: out_dtype 0, bf16:
+ * 1), from ens [B][E][C][H][W] read as mk_ens_sums reads it (dtype, bstride, estride in elements, a member's [C][H][W] block
+ * contiguous, gaps never touched), 2 <= E <= 64, 1 <= K <= 16.  A product's [Cs][H][W] block is contiguous; obstride (sample)
+ * and okstride (product) are free, in elements, and what lies between the blocks keeps its bytes.
+ * chans: device int32 [Cs], the member channel of output channel j, any order, repeats allowed; NULL: the identity, Cs == C.
+ * The grid runs over Cs: a channel that is not selected is never read.  A chans[j] outside [0, C) reads nothing and gives
+ * NaN planes.  kinds, orders, fracs: HOST arrays of length K (copied into the kernel's arguments).  Per point, with the
+ * members x_e widened to fp64 (exact):
+ *   kind 0 mean   m = (sum_e x_e) / E, summed in member order, a division (E equal members x give m = x exactly)
+ *   kind 1 std    sqrt(sum_e (x_e - m)^2 / (E - 1)), two-pass about m, fma accumulation, a division; +0 for E equal members
+ *   kind 2 order  fma(t, x_(k+1) - x_(k), x_(k)) over the members sorted ascending (ranks from 0), k = orders[i],
+ *                 t = fracs[i] in [0, 1); with t == 0 it is x_(k) itself, x_(k+1) is not read and k = E - 1 is legal.
+ *                 numpy's `linear` quantile q is k = floor(q (E - 1)), t = q (E - 1) - k
+ *   kind 3 above  #{e : x_e > thr[i][j]} / E         kind 4 below  #{e : x_e < thr[i][j]} / E
+ *                 compared in fp32 (exact), a tie counts for neither; thr device fp32 [K][Cs], read for these kinds only,
+ *                 a NaN threshold gives a NaN plane; one IEEE fp32 division of the two integers
+ * Kinds 0 - 2 are formed in fp64 and rounded ONCE to fp32 (a t == 0 order statistic is the member's value, untouched);
+ * with scale and shift (device fp32 [Cs], both or neither) the fp32 value v becomes v * scale[j] + shift[j] in fp32, two
+ * roundings, contraction off, as the rollout tail applies its emit statistics; kind 1 is multiplied by scale[j] only, kinds 3
+ * and 4 are never scaled.  A bf16 output is that fp32 value stored with round to nearest even.  If a member of a point is
+ * NaN, all K products of the point are NaN (looked for before the sort, whose min / max drop a NaN); +-inf is out of contract.
+ * Decomposition and staging of mk_ens_sums (workgroup = 8 rows of one selected channel of one sample, tiles of 256 points,
+ * 128 for E > 32, one point per thread, every member from its own 16-byte boundary); the sorted members go back into the
+ * thread's own LDS column, where the table's ranks address them, the K values of a tile into a second [K][TP] LDS region
+ * that leaves through the mirror image of the staging, every plane from its own 16-byte boundary.  At most 48 KB of LDS.
+ * One launch, no atomics, no workspace, one writer per element, the same bits every run, 64-bit element offsets, B and
+ * Cs <= 65535.  Every refusal (sizes, strides below C H W / Cs H W, overlapping samples, alignment, a kind outside 0 ... 4, a
+ * rank outside 0 ... E - 1 (E - 2 where t > 0), t outside [0, 1), a count kind without thr, scale without shift) returns 1
+ * before any launch. */
+int mk_ens_products(const void* ens, int dtype, long long bstride, long long estride, void* out, int out_dtype,
+                    long long obstride, long long okstride, const int* chans, const int* kinds, const int* orders,
+                    const double* fracs, const float* thr, const float* scale, const float* shift, int B, int E, int C, int Cs,
+                    int K, int H, int W, void* stream);
+
 /* ---- latitude interpolation (csrc/grid.hip): P planes [Hs][W] onto Hd destination rows, what GridConverter does between
  * an equiangular archive and a Legendre-Gauss model grid.  Fields are fp32 (dtype 0) or bf16 (1), each side with a dtype, a
  * plane stride and a row stride (elements) of its own; rows are contiguous along W, start at any element-aligned address,

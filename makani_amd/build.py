@@ -8,8 +8,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmakani_amd.so")
 STAMP = LIB + ".stamp"
-SOURCES = ["host.cpp", "fft.hip", "gemm.hip", "x3_legendre.hip", "x3_spectral.hip", "x3_latdft.hip", "x3_conv.hip", "x3_toklinear.hip", "x3_attn.hip", "layout.hip", "diag.hip", "spec_diag.hip", "pointwise.hip", "conv_gemm.hip", "pce.hip", "pce_mlp.hip", "adam.hip", "optim.hip", "metrics.hip", "lploss.hip", "preproc.hip", "rollout.hip", "stats.hip", "hist.hip", "ens.hip", "grid.hip", "noise.hip", "zenith.hip", "chnorm.hip", "specnorm.hip", "spec_crps.hip", "attn.hip", "toknorm.hip", "toklinear.hip", "patch.hip"]
-HEADERS = ["common.h", "mfma_tile.h", "attn_host.h", "x3_engine.h", "fft_split.h", "pce_common.h", "gelu.h", "stream_io.h", "tile_map.h", "layout_elem.h", "philox.h", os.path.join("..", "..", "include", "makani_amd.h")]
+SOURCES = ["host.cpp", "fft.hip", "gemm.hip", "x3_legendre.hip", "x3_spectral.hip", "x3_latdft.hip", "x3_conv.hip", "x3_toklinear.hip", "x3_attn.hip", "layout.hip", "diag.hip", "spec_diag.hip", "pointwise.hip", "conv_gemm.hip", "pce.hip", "pce_mlp.hip", "adam.hip", "optim.hip", "metrics.hip", "lploss.hip", "preproc.hip", "rollout.hip", "stats.hip", "hist.hip", "ens.hip", "ens_products.hip", "grid.hip", "noise.hip", "zenith.hip", "chnorm.hip", "specnorm.hip", "spec_crps.hip", "attn.hip", "toknorm.hip", "toklinear.hip", "patch.hip"]
+HEADERS = ["common.h", "mfma_tile.h", "attn_host.h", "x3_engine.h", "fft_split.h", "pce_common.h", "gelu.h", "stream_io.h", "ens_tile.h", "tile_map.h", "layout_elem.h", "philox.h", os.path.join("..", "..", "include", "makani_amd.h")]
 
 
 def _hipcc():

@@ -20,6 +20,10 @@ channel's scale, so scoring runs on normalised fields and ``finalize(stds)`` sca
 for the gradient with respect to the members), selected by the ``crps`` strings of ``losses.LossHandler``; ``perturb_members``
 makes the E members of a training step the way ``EnsembleRollout`` makes those of a rollout.
 
+``EnsembleProducts`` turns the members into the planes a forecast is delivered as -- ensemble mean, spread, quantiles, the
+probability of crossing a threshold -- in one ``ops.ensemble_products`` pass (``csrc/ens_products.hip`` with
+``MK_ENS_PRODUCTS=hip``), so that ``EnsembleRollout.run(products=...)`` copies K planes per lead time to the host, not E fields.
+
 ``EnsembleSpectralCRPSLoss`` is the CRPS of the members' spherical-harmonic coefficients (``ops.spectral_crps_sums`` on the
 transform's packed spectra, one HIP pass each way), selected by the words ``spectral`` and ``combined`` of the ``crps`` strings.
 """
@@ -105,6 +109,110 @@ class EnsembleScores:
             out["spread_skill"] = math.sqrt((E + 1) / E) * out["spread"] / out["ens_mean_rmse"]
             out["rank_histogram"], out["skipped"] = ranks, skipped
         return out
+
+
+class EnsembleProducts:
+    """The forecast products of an ensemble of ``members`` members, per point: ``__call__(ens)`` with ``ens`` ``[B, E, C, H, W]``
+    (or the model's ``[B * E, C, H, W]``, member fastest, which is viewed) returns ``[B, K, Cs, H, W]`` of ``out_dtype`` from one
+    ``ops.ensemble_products`` pass.
+
+    ``products`` is a list of K specs (at most ``ops.ENS_PRODUCTS_MAX`` on the HIP pass):
+
+    * ``"mean"``, ``"std"`` (the spread: root of the unbiased member variance), ``"min"``, ``"max"``, ``"median"``;
+    * ``("quantile", q)``: numpy's ``linear`` quantile of the members, ``0 <= q <= 1`` (``ops.quantile_position``);
+    * ``("above", thr)``, ``("below", thr)``: the fraction of members strictly above / below a threshold.  ``thr`` is a float,
+      for all selected channels, or ``{channel index: value}`` by the members' channel index; a selected channel without a value
+      gets a NaN threshold and so a NaN plane.
+
+    ``channels`` selects and orders the member channels (repeats allowed; None: all).  ``stats = (means, stds)``, one value per
+    selected channel in the order of ``channels`` as ``Rollout.run``'s ``output_stats``, de-normalises inside the pass: mean and
+    order statistics come out as ``v * std + mean``, the spread as ``v * std``, the fractions as they are; ``stds`` must be positive.
+    ``thresholds_in="output"`` (the default): thresholds are in the units of the result, physical ones with ``stats``, and are
+    converted once on the host in float64, ``(thr - mean) / std``, rounded to fp32; the event is defined on the members as they
+    are, the normalised ones.  ``thresholds_in="members"``: thresholds are in the members' units and taken as they are.
+
+    ``names`` are K strings, ``table`` the ``(kinds, orders, fracs)`` of ``ops.ensemble_products``.  The device tables (channel
+    list, thresholds, statistics) are uploaded once per device and channel count: a captured caller keeps reading the same tensors."""
+
+    def __init__(self, members, products, channels=None, stats=None, thresholds_in="output", out_dtype=torch.float32):
+        self.members = E = int(members)
+        if E < 1:
+            raise ValueError(f"EnsembleProducts: members must be at least 1, got {members}")
+        if thresholds_in not in ("output", "members"):
+            raise ValueError(f"EnsembleProducts: thresholds_in must be 'output' or 'members', got {thresholds_in!r}")
+        self.thresholds_in, self.out_dtype = thresholds_in, out_dtype
+        self.channels = None if channels is None else [int(c) for c in channels]
+        if self.channels is not None and (not self.channels or min(self.channels) < 0):
+            raise ValueError(f"EnsembleProducts: channels {self.channels} must be a non-empty list of channel indices")
+        self.means = self.stds = None
+        if stats is not None:
+            self.means, self.stds = (torch.as_tensor(t, dtype=torch.float64).reshape(-1).cpu() for t in stats)
+            if self.means.numel() != self.stds.numel() or (self.channels is not None and self.means.numel() != len(self.channels)):
+                raise ValueError(f"EnsembleProducts: stats have {self.means.numel()} means and {self.stds.numel()} stds for "
+                                 f"{'all' if self.channels is None else len(self.channels)} selected channels")
+            if not bool((self.stds > 0).all()):
+                raise ValueError("EnsembleProducts: stds must be positive")
+        kinds, orders, fracs, self.names, self._thr = [], [], [], [], []
+        fixed = {"mean": (0, 0, 0.0), "std": (1, 0, 0.0), "min": (2, 0, 0.0), "max": (2, E - 1, 0.0),
+                 "median": (2,) + ops.quantile_position(0.5, E)}
+        for spec in products:
+            thr = None
+            if isinstance(spec, str) and spec in fixed:
+                row, name = fixed[spec], spec
+            elif isinstance(spec, (tuple, list)) and len(spec) == 2 and spec[0] == "quantile":
+                row, name = (2,) + ops.quantile_position(spec[1], E), f"q{float(spec[1]):g}"
+            elif isinstance(spec, (tuple, list)) and len(spec) == 2 and spec[0] in ("above", "below"):
+                thr = {int(c): float(v) for c, v in spec[1].items()} if isinstance(spec[1], dict) else float(spec[1])
+                row, name = (3 if spec[0] == "above" else 4, 0, 0.0), spec[0] if isinstance(thr, dict) else f"{spec[0]}_{thr:g}"
+            else:
+                raise ValueError(f"EnsembleProducts: unknown product {spec!r} (mean, std, min, max, median, ('quantile', q), "
+                                 "('above', thr), ('below', thr))")
+            kinds.append(row[0]), orders.append(row[1]), fracs.append(row[2]), self.names.append(name), self._thr.append(thr)
+        if not kinds:
+            raise ValueError("EnsembleProducts: no products")
+        self.table = (kinds, orders, fracs)
+        self._tables = {}
+
+    def thresholds(self, C):
+        """``[K, Cs]`` fp32 on the host, as the pass compares them with the members of ``C`` channels (NaN where a product has no
+        threshold or a channel no value), or None without a count product."""
+        if all(t is None for t in self._thr):
+            return None
+        chans = list(range(C)) if self.channels is None else self.channels
+        out = torch.full((len(self._thr), len(chans)), float("nan"), dtype=torch.float64)
+        for i, thr in enumerate(self._thr):
+            if thr is not None:
+                for j, c in enumerate(chans):
+                    if not isinstance(thr, dict) or c in thr:
+                        out[i, j] = thr[c] if isinstance(thr, dict) else thr
+        if self.means is not None and self.thresholds_in == "output":
+            out = (out - self.means.reshape(1, -1)) / self.stds.reshape(1, -1)
+        return out.float()
+
+    def _device_tables(self, device, C):
+        key = (str(device), C)
+        if key not in self._tables:
+            if self.channels is not None and max(self.channels) >= C:
+                raise ValueError(f"EnsembleProducts: channels {self.channels} out of range for {C} channels")
+            Cs = C if self.channels is None else len(self.channels)
+            if self.means is not None and self.means.numel() != Cs:
+                raise ValueError(f"EnsembleProducts: stats have {self.means.numel()} values for {Cs} selected channels")
+            thr = self.thresholds(C)
+            self._tables[key] = (None if self.channels is None else torch.tensor(self.channels, dtype=torch.int32, device=device),
+                                 None if thr is None else thr.to(device),
+                                 None if self.stds is None else self.stds.float().to(device),
+                                 None if self.means is None else self.means.float().to(device))
+        return self._tables[key]
+
+    def __call__(self, ens, out=None):
+        E = self.members
+        if ens.dim() == 4 and ens.shape[0] % E == 0:
+            shape = (ens.shape[0] // E, E) + tuple(ens.shape[1:])
+            ens = ens.view(shape) if ens.is_contiguous() else ens.reshape(shape)
+        if ens.dim() != 5 or ens.shape[1] != E:
+            raise ValueError(f"EnsembleProducts: ensemble {tuple(ens.shape)} must be [B, {E}, C, H, W] or [B * {E}, C, H, W]")
+        chans, thr, scale, shift = self._device_tables(ens.device, ens.shape[2])
+        return ops.ensemble_products(ens, *self.table, chans=chans, thr=thr, scale=scale, shift=shift, out=out, out_dtype=self.out_dtype)
 
 
 def member_noise(noise, shape, members, dtype):

@@ -323,6 +323,7 @@ class EnsembleRollout(Rollout):
         self.scores = scores
         self.noise_std = float(getattr(params, "noise_std", 0.0) or 0.0) if noise_std is None else float(noise_std)
         self.noise, self.step_noise_std = noise, float(step_noise_std)
+        self.last_products = None           # [steps, B, K, Cs, H, W] on the host: the latest run's ``products``
         if self.step_noise_std < 0.0:
             raise ValueError(f"EnsembleRollout: step_noise_std must not be negative, got {step_noise_std}")
         if self.step_noise_std > 0.0 and noise is None:
@@ -354,12 +355,21 @@ class EnsembleRollout(Rollout):
         return fed
 
     def run(self, inp, tar=None, steps=None, generator=None, inp_times=None, tar_times=None, output_channels=None,
-            output_stats=None):
+            output_stats=None, products=None):
         """One ensemble rollout from ``inp`` (``[B, T, C, H, W]`` or flattened).  With ``tar`` ``[B, steps, C, H, W]`` every
         step is scored (``scores`` must be given); without it the ensemble runs free for ``steps`` steps.
         ``output_channels`` / ``output_stats`` as in ``Rollout.run``; the result is fp32 ``[steps, B, E, K, H, W]`` on the
-        host, or None."""
+        host, or None.
+
+        ``products`` (an ``ensemble.EnsembleProducts`` for E members): every step's ``pred``, viewed as ``[B, E, C, H, W]`` without
+        a copy, goes through one ``ops.ensemble_products`` launch behind the tail (behind the replay with ``capture=True``, on the
+        same stream, as the scores) and its ``[B, K, Cs, H, W]`` is copied without blocking into pinned host memory;
+        ``last_products`` is that ``[steps, B, K, Cs, H, W]`` tensor of the module's ``out_dtype`` after the one synchronisation
+        at the end (None without ``products``).  What ``run`` returns does not change.  Under spatial parallelism every rank
+        holds its shard of the planes: the products are pointwise."""
         pp, E = self.preprocessor, self.members
+        if products is not None and products.members != E:
+            raise ValueError(f"EnsembleRollout.run: {E} members, the products were built for {products.members}")
         with torch.no_grad():
             x = self.perturb(inp, generator)
             B, device = x.shape[0] // E, x.device
@@ -382,7 +392,7 @@ class EnsembleRollout(Rollout):
             else:
                 nsteps = int(steps) if steps is not None else self.steps
             emit = self._emit_args(output_channels, output_stats, device)
-            out = None
+            out = planes = None
             for idt in range(nsteps):
                 if self.capture and device.type == "cuda":
                     pred, _, emitted = self._captured_step(x, None, emit)
@@ -395,7 +405,13 @@ class EnsembleRollout(Rollout):
                         out = torch.empty((nsteps, B, E) + tuple(emitted.shape[1:]), dtype=torch.float32,
                                           pin_memory=device.type == "cuda")
                     out[idt].copy_(emitted.view((B, E) + tuple(emitted.shape[1:])), non_blocking=True)
+                if products is not None:
+                    made = products(pred.view((B, E) + tuple(pred.shape[1:])))
+                    if planes is None:
+                        planes = torch.empty((nsteps,) + tuple(made.shape), dtype=made.dtype, pin_memory=device.type == "cuda")
+                    planes[idt].copy_(made, non_blocking=True)
                 x = pp.append_history(x, self.feedback(pred), idt)
             if device.type == "cuda":
                 torch.cuda.current_stream(device).synchronize()         # once, for the host copies
+        self.last_products = planes
         return out

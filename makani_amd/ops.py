@@ -37,7 +37,7 @@ _HIP_TORCH, _OFF_ON = ("hip", "torch"), ("0", "1")
 # free-form variables (MK_COLLECTIVE_TIMEOUT, MK_WGRAD_SPLIT, MK_LIB_OVERRIDE, MK_EXTRA_HIPCC_FLAGS) are read where they are used.
 KNOBS = {
     **dict.fromkeys(("MK_PLANAR_FFT", "MK_SPEC_ATTN", "MK_AFNO", "MK_AFNOV1", "MK_ATTN", "MK_ATTN_FP32", "MK_TOKEN_NORM",
-                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_GRID", "MK_NOISE", "MK_ROWSUM", "MK_SPEC_CRPS"),
+                     "MK_TOKEN_LINEAR", "MK_TOKEN_LINEAR_FP32", "MK_PATCH", "MK_ROLLOUT", "MK_STATS", "MK_HIST", "MK_ENSEMBLE", "MK_ENS_LOSS", "MK_ENS_PRODUCTS", "MK_GRID", "MK_NOISE", "MK_ROWSUM", "MK_SPEC_CRPS"),
                     _HIP_TORCH),
     "MK_SPEC_DIAG": ("fused", "public"),
     "MK_SPECTRAL_GEMM": ("bf16x3", "f32"),
@@ -2635,6 +2635,190 @@ def ensemble_sums(ens, tar, wrow, ranks=None, skipped=None):
     if not (hip and ens.is_cuda and 2 <= E <= ENSEMBLE_MAX_MEMBERS):
         return _ensemble_sums_torch(ens, tar, wrow, ranks, skipped)
     return _ens_sums_launch(_lowp(ens), tar.float().contiguous(), wrow.float().contiguous(), ranks, skipped)[0]
+
+
+# ----------------------------------------------------------------------------
+# ensemble forecast products (csrc/ens.hip: mk_ens_products)
+# ----------------------------------------------------------------------------
+ENS_PRODUCTS_DEFAULT = "hip"    # MK_ENS_PRODUCTS: hip | torch.  No row of tools/ens_products_bench.py is slower than torch
+ENS_PRODUCTS_MAX = 16           # products per launch of mk_ens_products (its [K][TP] LDS region)
+ENS_PRODUCT_KINDS = ("mean", "std", "order", "above", "below")          # the kind codes of mk_ens_products, by position
+
+
+def quantile_position(q, E):
+    """``(k, t)`` of the quantile ``q`` in [0, 1] of ``E`` members by numpy's ``linear`` method: float64 ``h = q (E - 1)``,
+    ``k = floor(h)``, ``t = h - k``; the quantile is ``x_(k) + t (x_(k+1) - x_(k))`` over the members sorted ascending, ranks from 0.
+    ``q = 1`` is ``(E - 1, 0.0)``: the maximum itself, nothing is read behind it."""
+    q, E = float(q), int(E)
+    if not 0.0 <= q <= 1.0 or E < 1:
+        raise ValueError(f"quantile_position: q = {q} must lie in [0, 1] and E = {E} be at least 1")
+    if q == 1.0:
+        return E - 1, 0.0
+    h = q * (E - 1)
+    k = int(math.floor(h))
+    return k, h - k
+
+
+def _ens_product_table(kinds, orders, fracs, E):
+    """The product table as ``mk_ens_products`` takes it (int32 kinds and ranks, float64 fractions, numpy), checked as it checks it."""
+    kinds = [ENS_PRODUCT_KINDS.index(k) if isinstance(k, str) and k in ENS_PRODUCT_KINDS else k for k in kinds]
+    K = len(kinds)
+    if K < 1 or len(orders) != K or len(fracs) != K:
+        raise ValueError(f"ensemble_products: {K} kinds, {len(orders)} orders, {len(fracs)} fracs; need one of each per product")
+    for i, kind in enumerate(kinds):
+        if kind not in range(len(ENS_PRODUCT_KINDS)):
+            raise ValueError(f"ensemble_products: unknown kind {kind!r} of product {i} ({', '.join(ENS_PRODUCT_KINDS)} or 0 ... 4)")
+        if kind == 2:
+            k, t = int(orders[i]), float(fracs[i])
+            if not 0.0 <= t < 1.0 or not 0 <= k <= (E - 1 if t == 0.0 else E - 2):
+                raise ValueError(f"ensemble_products: product {i} has rank {k} and fraction {t} for {E} members: need t in [0, 1) "
+                                 "and k in 0 ... E - 1 (E - 2 with a fraction)")
+    return (np.asarray(kinds, dtype=np.int32), np.asarray([int(k) for k in orders], dtype=np.int32),
+            np.asarray([float(t) for t in fracs], dtype=np.float64))
+
+
+def _ensemble_products_torch(ens, kinds, orders, fracs, idx, thr, scale, shift, out):
+    """``ensemble_products`` as torch ops on the tensors' device by the same definitions: the members widened to float64, the sum
+    in member order, the two-pass deviation, a ``sort`` over the member axis and its planes for the order statistics, counts
+    compared in fp32, every value rounded once to fp32, then ``* scale + shift`` as two fp32 operations.  ``idx``: the selected
+    channels (int64 tensor) or None; ``out`` ``[B, K, Cs, H, W]`` is written in place, chunk of channels by chunk so that a
+    temporary holds at most ``_ENS_TORCH_CHUNK`` elements."""
+    B, E, C, H, W = ens.shape
+    Cs = out.shape[2]
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=ens.device)
+    # divisors as tensors: torch divides by a python scalar on the device as a multiplication by its reciprocal, which is not
+    # the division of the definition (E equal members must give m = x, a count over E the IEEE quotient)
+    n64, nm1, n32 = (torch.full((), v, dtype=t, device=ens.device) for v, t in ((E, torch.float64), (E - 1, torch.float64), (E, torch.float32)))
+    need_std, need_sort = bool((kinds == 1).any()), bool((kinds == 2).any())
+    step = max(1, _ENS_TORCH_CHUNK // max(1, B * E * H * W))
+    for c0 in range(0, Cs, step):
+        sel = slice(c0, min(Cs, c0 + step))
+        x32 = (ens[:, :, sel] if idx is None else ens.index_select(2, idx[sel])).float()
+        x = x32.double()
+        bad = torch.isnan(x32).any(dim=1)
+        sm = x[:, 0].clone()
+        for e in range(1, E):
+            sm += x[:, e]
+        m = sm / n64
+        if need_std:
+            sv = torch.zeros_like(m)
+            for e in range(E):
+                d = x[:, e] - m
+                sv += d * d
+            sd = torch.sqrt(sv / nm1) if E > 1 else torch.full_like(m, float("nan"))
+        if need_sort:
+            xs = torch.sort(x32, dim=1).values
+        for i, kind in enumerate(kinds.tolist()):
+            if kind == 0:
+                v = m.float()
+            elif kind == 1:
+                v = sd.float()
+            elif kind == 2:
+                k, t = int(orders[i]), float(fracs[i])
+                v = xs[:, k]
+                if t != 0.0:
+                    a, b = xs[:, k].double(), xs[:, k + 1].double()
+                    v = (a + t * (b - a)).float()
+            else:
+                th = thr[i, sel].reshape(1, -1, 1, 1)
+                cnt = ((x32 > th.unsqueeze(1)) if kind == 3 else (x32 < th.unsqueeze(1))).sum(dim=1)
+                v = torch.where(torch.isnan(th), nan, cnt.float() / n32)
+            if scale is not None and kind <= 2:
+                v = v * scale[sel].reshape(1, -1, 1, 1)
+                if kind != 1:
+                    v = v + shift[sel].reshape(1, -1, 1, 1)
+            out[:, i, sel] = torch.where(bad, nan, v)
+    return out
+
+
+def _ens_products_launch(ens, kinds, orders, fracs, chans, thr, scale, shift, out):
+    """One ``mk_ens_products`` launch: fp32 / bf16 members ``[B, E, C, H, W]`` read in place where every member's ``[C, H, W]``
+    block is contiguous (else the ensemble is copied), ``out`` ``[B, K, Cs, H, W]`` fp32 / bf16 written through its strides."""
+    B, E, C, H, W = ens.shape
+    K, Cs = out.shape[1], out.shape[2]
+    if ens.stride()[2:] != (H * W, W, 1) or min(ens.stride(0), ens.stride(1)) < C * H * W:
+        ens = ens.contiguous()
+    bstride = ens.stride(0) if B > 1 else E * ens.stride(1)      # a stride of a size-1 axis means nothing
+    okstride = out.stride(1) if K > 1 else Cs * H * W
+    obstride = out.stride(0) if B > 1 else K * okstride
+    _lib.check(_lib.load().mk_ens_products(ens.data_ptr(), _pw_dtype(ens), bstride, ens.stride(1), out.data_ptr(), _pw_dtype(out),
+                                           obstride, okstride, _ptr(chans), kinds.ctypes.data, orders.ctypes.data, fracs.ctypes.data,
+                                           _ptr(thr), _ptr(scale), _ptr(shift), B, E, C, Cs, K, H, W, _stream()), "mk_ens_products")
+    return out
+
+
+@torch.no_grad()
+def ensemble_products(ens, kinds, orders, fracs, chans=None, thr=None, scale=None, shift=None, out=None, out_dtype=torch.float32):
+    """Forecast products of an ensemble ``ens`` ``[B, E, C, H, W]``: ``[B, K, Cs, H, W]`` of ``out_dtype``, one plane per product
+    and selected channel.  A ``[B * E, C, H, W]`` model output is passed pre-viewed, ``x.view(B, E, C, H, W)`` (member fastest);
+    there is no ``members=`` argument.
+
+    ``kinds`` (names of ``ENS_PRODUCT_KINDS`` or their positions), ``orders`` and ``fracs`` are sequences of length K, at most
+    ``ENS_PRODUCTS_MAX`` on the HIP pass.  Per point, with the members ``x_e`` widened to float64:
+
+    * ``mean``: ``m = (sum_e x_e) / E``, summed in member order;
+    * ``std``: ``sqrt(sum_e (x_e - m)^2 / (E - 1))``, two-pass about ``m`` (NaN for ``E = 1``);
+    * ``order``: ``x_(k) + t (x_(k+1) - x_(k))`` over the members sorted ascending, ``k = orders[i]`` from 0, ``t = fracs[i]`` in
+      [0, 1); with ``t == 0`` the member of rank k itself (``k = E - 1`` is legal only then).  ``quantile_position`` gives the
+      pair of a quantile; min is ``(0, 0.0)``, max ``(E - 1, 0.0)``;
+    * ``above`` / ``below``: ``#{e : x_e > thr[i, j]} / E`` and ``#{e : x_e < thr[i, j]} / E``, compared in fp32, a tie counts
+      for neither; ``thr`` is an fp32 ``[K, Cs]`` tensor read for these kinds only, a NaN threshold gives a NaN plane.
+
+    ``chans`` selects and orders the channels (a list, checked against C, or a 1-D integer tensor on the device, taken as it
+    is: on the HIP pass an entry outside ``[0, C)`` gives NaN planes); repeats are allowed, None is all C.  The first three
+    kinds are rounded once to fp32; ``scale`` and ``shift`` ``[Cs]`` (both or neither) then give ``v * scale[j] + shift[j]`` in
+    fp32 as ``rollout_tail`` applies its emit statistics -- ``std`` is multiplied only, the counts are never scaled.  A bf16
+    result is the fp32 one rounded to nearest even.  A point with a NaN member is NaN in all K planes; infinite members are out
+    of contract.  ``out``, where given, is written and returned: any ``[B, K, Cs, H, W]`` view whose ``[Cs, H, W]`` blocks are
+    contiguous and do not overlap, such as a slice of a larger buffer; what lies between the blocks keeps its bytes.
+
+    ``MK_ENS_PRODUCTS=hip`` (read on every call): CUDA fp32 / bf16 members with 2 to ``ENSEMBLE_MAX_MEMBERS`` members, at most
+    ``ENS_PRODUCTS_MAX`` products and an fp32 / bf16 result take one ``mk_ens_products`` launch (members read in place through
+    their strides, no atomics, no workspace, the same bits every run, capturable).  CPU tensors, ``E = 1``, more members or
+    products, other dtypes and ``MK_ENS_PRODUCTS=torch`` take ``_ensemble_products_torch``.  No gradient flows through this op."""
+    hip = _hip_or_torch("MK_ENS_PRODUCTS", ENS_PRODUCTS_DEFAULT)
+    if ens.dim() != 5 or min(ens.shape) < 1:
+        raise ValueError(f"ensemble_products: the ensemble must be [B, E, C, H, W], got {tuple(ens.shape)}")
+    B, E, C, H, W = ens.shape
+    dev = ens.device
+    kinds, orders, fracs = _ens_product_table(kinds, orders, fracs, E)
+    K = len(kinds)
+    idx = None
+    if chans is not None:
+        if not torch.is_tensor(chans):
+            chans = [int(c) for c in chans]
+            if not chans or min(chans) < 0 or max(chans) >= C:
+                raise ValueError(f"ensemble_products: chans {chans} out of range for {C} channels")
+            chans = torch.tensor(chans, dtype=torch.int32, device=dev)
+        if chans.dim() != 1 or chans.numel() < 1 or chans.device != dev or chans.dtype.is_floating_point:
+            raise ValueError(f"ensemble_products: chans must be a 1-D integer tensor on {dev}, got {chans.dtype} {tuple(chans.shape)} "
+                             f"on {chans.device}")
+    Cs = C if chans is None else chans.numel()
+    if bool(((kinds == 3) | (kinds == 4)).any()):
+        if thr is None or tuple(thr.shape) != (K, Cs) or thr.device != dev:
+            raise ValueError(f"ensemble_products: a count product needs thr [K, Cs] = [{K}, {Cs}] on {dev}")
+    if (scale is None) != (shift is None):
+        raise ValueError("ensemble_products: scale and shift come together or not at all")
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None and (t.numel() != Cs or t.device != dev):
+            raise ValueError(f"ensemble_products: {name} {tuple(t.shape)} on {t.device} needs Cs = {Cs} elements on {dev}")
+    thr, scale, shift = _f32(thr), _f32(None if scale is None else scale.reshape(-1)), _f32(None if shift is None else shift.reshape(-1))
+    if out is None:
+        out = torch.empty(B, K, Cs, H, W, dtype=out_dtype, device=dev)
+    elif tuple(out.shape) != (B, K, Cs, H, W) or out.device != dev:
+        raise ValueError(f"ensemble_products: out {tuple(out.shape)} on {out.device} must be {[B, K, Cs, H, W]} on {dev}")
+    ens = ens.detach()
+    if not (hip and ens.is_cuda and 2 <= E <= ENSEMBLE_MAX_MEMBERS and K <= ENS_PRODUCTS_MAX and ens.dtype in _LOWP
+            and out.dtype in _LOWP):
+        return _ensemble_products_torch(ens, kinds, orders, fracs, None if chans is None else chans.long(), thr, scale, shift, out)
+    chw = Cs * H * W
+    so = out.stride()
+    if (so[2:] != (H * W, W, 1) or (K > 1 and so[1] < chw) or (B > 1 and so[0] < chw)
+            or (B > 1 and K > 1 and so[0] < K * so[1] and so[1] < B * so[0])):
+        raise ValueError(f"ensemble_products: out with strides {tuple(so)} is not [B, K] separate contiguous [Cs, H, W] blocks")
+    if chans is not None:
+        chans = chans.to(torch.int32).contiguous()
+    return _ens_products_launch(ens, kinds, orders, fracs, chans, thr, scale, shift, out)
 
 
 # ----------------------------------------------------------------------------
